@@ -61,7 +61,7 @@ WORKLOADS = {
     "mixgroups": (262144, 8, 16),  # the per-instrument voice sum alone, 16 voices per instrument
     "allpass4": (131072, 16, 8),  # 4 x Allpass<PitchbendableDelay> in series per voice (8 rings of 4096 samples), per-voice delay times
     # the reference's own examples/audio-and-midi/reverb.cpp (the Aaltoverb algorithm: 10 x Allpass<PitchbendableDelay> + 2 PitchbendableDelay = 24
-    # rings, two kept DSPVectors), compiled UNCHANGED against the shim (tests/cpp/libexamples_gpu.so), one stereo reverb per voice
+    # rings, two kept DSPVectors), compiled UNCHANGED against the shim (oracle/_ref/libexamples_gpu.so), one stereo reverb per voice
     "reverb": (65536, 16, 8),
     # BASELINE.json north_star "Target": >= 10^6 SawGen -> SVF -> gain voices at 48 kHz real time on one GPU (paced, not free-running)
     "rt": (1048576, 1, 75),      # 2^20 voices, one 64-frame block per call paced at the 1333 us block period; a step = 75 blocks = 0.1 s of audio
@@ -109,6 +109,7 @@ def setup_workload(eng, name, V, T, lo, total):
         def launch():
             bank.process(T, outs[k[0] & 1], Layout.QUAD)
             k[0] += 1
+        launch.output = lambda: (outs[(k[0] - 1) & 1], V, T * 64)
         # 4 B/voice-sample written + per launch and voice
         # (4 phase + 8 ic + 12 coeff + 4 gain + 4 freq) read and 12 written
         alg = 4.0 * n + V * (4 + 8 + 12 + 4 + 4 + 12)
@@ -129,6 +130,7 @@ def setup_workload(eng, name, V, T, lo, total):
         def launch():
             bank.process(T, outs[k[0] & 1], Layout.QUAD, d_x, Layout.QUAD)
             k[0] += 1
+        launch.output = lambda: (outs[(k[0] - 1) & 1], V, T * 64)
         alg = 8.0 * n + V * (4 * (24 + 16) + 4 * 16)
         return launch, alg, bank.kernel_name, "BASELINE configs[3]: 131072 channels x 8 cascaded Lopass, streamed noise input", bank
     if name == "cfg2":
@@ -138,6 +140,7 @@ def setup_workload(eng, name, V, T, lo, total):
 
         def launch():
             eng.op_apply(Op.EXP_APPROX_OF_SIN_APPROX, d_x, None, None, d_y, n)
+        launch.output = lambda: (d_y, None, n)
         return launch, 8.0 * n, "op_kernel<22>", \
             "BASELINE configs[1]: 65536 voices x 1 DSPVector elementwise expApprox(sinApprox(x)) (32 MiB: Infinity-Cache resident)", (d_x, d_y)
     if name in ("cfg5", "cfg5full", "cfg5mix"):
@@ -166,6 +169,7 @@ def setup_workload(eng, name, V, T, lo, total):
         def launch():
             g.process(T, [d_gate], [outs_d[k[0] & 1]])
             k[0] += 1
+        launch.output = lambda: (outs_d[(k[0] - 1) & 1], None if name == "cfg5mix" else V, T * 64)
         if name == "cfg5mix":
             return launch, 4.0 * n + V * 4.0 * (5 + 14 + 19 + 19), "mlgpu_graph_kernel", (
                 "BASELINE configs[4]'s 16-node voice, 262144 voices/GPU mixed to ONE channel inside the voice kernel "
@@ -415,9 +419,9 @@ def setup_workload(eng, name, V, T, lo, total):
         return launch, alg, "mlgpu_graph_kernel", f"4 x Allpass<PitchbendableDelay> in series (8 rings per voice), per-voice delay times 400..3400 samples, {V} voices, ring layout {g.delay_layout}", (g, nb)
     if name == "reverb":
         import ctypes
-        so = os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so")
+        so = os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so")
         if not os.path.exists(so):
-            raise RuntimeError("tests/cpp/libexamples_gpu.so is not built (it is made from the reference's example source where /root/reference exists: __graft_entry__.build())")
+            raise RuntimeError("oracle/_ref/libexamples_gpu.so is not built (oracle/Makefile makes it from the reference's example source where that checkout exists)")
         X = ctypes.CDLL(so)
         X.example_reverb_gpu_open.restype = ctypes.c_void_p
         X.example_reverb_gpu_open.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
@@ -1090,6 +1094,30 @@ def live_traffic(workload, kernel_name, timeout_s=150):
                       "processes after its timed region; KiB x 1024, FETCH_SIZE x 2 (gfx950, coalesced 16 B / lane streams)"}
 
 
+# --dump-outputs: the workloads whose launch says what it handed its caller (launch.output() -> (device buffer, voices of its QUAD
+# [S/4][V][4] layout or None for a flat signal, samples per voice)), and how much of that is written
+DUMP_WORKLOADS = ("cfg3", "cfg4", "cfg2", "cfg5", "cfg5full", "cfg5mix")
+DUMP_MAX_BYTES = 32 << 20
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, launch):
+    """Writes the output of the timed path's last launch as out_dir/output.npy (float32). A voice bank's output is written voice-major
+    [voices][samples]; where all of it would exceed DUMP_MAX_BYTES, a fixed, seeded sample of voices (their indices, ascending, in
+    out_dir/voices.npy as float64). A flat signal that large keeps its first DUMP_MAX_BYTES."""
+    buf, V, S = launch.output()
+    a = buf.download(np.float32, (V or 1) * S)
+    os.makedirs(out_dir, exist_ok=True)
+    if V is None:
+        a = a[:DUMP_MAX_BYTES // 4]
+    else:
+        nv = max(1, min(V, DUMP_MAX_BYTES // (4 * S)))
+        voices = np.arange(V) if nv == V else np.sort(np.random.default_rng(DUMP_SEED).choice(V, nv, replace=False))
+        a = a.reshape(S // 4, V, 4)[:, voices, :].transpose(1, 0, 2).reshape(nv, S)
+        np.save(os.path.join(out_dir, "voices.npy"), voices.astype(np.float64))
+    np.save(os.path.join(out_dir, "output.npy"), np.ascontiguousarray(a))
+
+
 def workload_key(name, V, T):
     """What identifies one measured case in profiles/pmc_workloads.json: the workload, its variant switches and its size."""
     var = [f"{k.lower().replace('mlgpu_', '')}={os.environ[k]}" for k in ("MLGPU_DELAY_WINDOWS", "MLGPU_UNIFORM_DELAY", "MLGPU_EVENT_ROWS",
@@ -1174,6 +1202,8 @@ def run_rank(args, rank, local_rank, world, rdv):
     eng.sync()
     eng.device_sync()
     my_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # (before anything after the timed region launches again)
+        dump_outputs(args.dump_outputs, launch)
     rdv.barrier()
     elapsed = rdv.max(my_elapsed)
     ranks = rdv.gather({"rank": rank, "device": local_rank, "pci_bus_id": info["pci_bus_id"], "name": info["name"], "pid": os.getpid(),
@@ -1625,7 +1655,15 @@ def main():
                          "distribution of step and launch times to FILE (profiles/archive/r03_cfg3_sustained.json)")
     ap.add_argument("--sustained-seconds", type=float, default=30.0)
     ap.add_argument("--print-case", action="store_true", help="print the key of this case in profiles/pmc_workloads.json and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last launch computed to DIR/output.npy (float32; rank 0's voices, a seeded "
+                         f"sample of them where all would exceed {DUMP_MAX_BYTES >> 20} MiB) so that two builds can be compared on the same inputs; "
+                         f"workloads: {', '.join(DUMP_WORKLOADS)}")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and args.workload not in DUMP_WORKLOADS:
+        raise SystemExit(f"bench.py: --dump-outputs is not available for --workload {args.workload} (only {', '.join(DUMP_WORKLOADS)})")
     if args.workload == "strings":
         # per-voice delay times: the transposed ring layout is the one a host should choose (round 5; 0 and 1 for comparison)
         os.environ.setdefault("MLGPU_DELAY_WINDOWS", "2")

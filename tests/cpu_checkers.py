@@ -39,12 +39,8 @@ def build_oracle():
 
 
 def build_ref():
-    """Compile oracle/_ref/libmlref.so when /root/reference is present; else use a prebuilt one."""
+    """oracle/_ref/libmlref.so as build() made it (oracle/Makefile, where the reference checkout exists), else None."""
     so = os.path.join(ORACLE_DIR, "_ref", "libmlref.so")
-    if os.path.isdir("/root/reference/source/DSP"):
-        src = os.path.join(ORACLE_DIR, "ref_wrapper.cpp")
-        if (not os.path.exists(so)) or os.path.getmtime(so) < os.path.getmtime(src):
-            subprocess.check_call(["make", "-C", ORACLE_DIR, "_ref/libmlref.so"], stdout=subprocess.DEVNULL)
     return so if os.path.exists(so) else None
 
 
@@ -430,7 +426,7 @@ class Ref(_Checker):
     def __init__(self, path=None):
         path = path or build_ref()
         if path is None:
-            raise FileNotFoundError("oracle/_ref/libmlref.so not built and /root/reference absent")
+            raise FileNotFoundError("oracle/_ref/libmlref.so not built")
         super().__init__(path)
         L = self.lib
         sz = ctypes.c_size_t

@@ -1,7 +1,7 @@
 """The reference's OWN example programs (examples/audio-and-midi/reverb.cpp — the Aaltoverb algorithm — and sine.cpp), included
 unchanged from the reference checkout, compiled once against the reference (oracle/example_ref_*.cpp) and once against the
-MI355X shim (tests/cpp/example_gpu_*.cpp): the same source gives the same bits. The two libraries are built where the
-reference checkout exists and travel to the GPU box; nothing here reads the checkout at run time."""
+MI355X shim (tests/cpp/example_gpu_*.cpp): the same source gives the same bits. oracle/Makefile builds both libraries into
+oracle/_ref/ where the reference checkout exists; nothing here reads the checkout at run time."""
 import ctypes
 import os
 
@@ -15,7 +15,7 @@ c_f32p = ctypes.POINTER(ctypes.c_float)
 
 
 def _libs():
-    gpu_so = os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so")
+    gpu_so = os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so")
     ref_so = os.path.join(ROOT, "oracle", "_ref", "libexamples_ref.so")
     if not (os.path.exists(gpu_so) and os.path.exists(ref_so)):
         pytest.skip("the example libraries are built only where the reference checkout exists")
@@ -30,7 +30,7 @@ def _libs():
 
 
 def test_example_libraries_load_where_built():
-    gpu_so = os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so")
+    gpu_so = os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so")
     if not os.path.exists(gpu_so):
         pytest.skip("not built here")
     L = ctypes.CDLL(gpu_so)

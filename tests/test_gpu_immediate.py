@@ -59,11 +59,9 @@ def test_immediate_mode_same_source_same_bits():
 
 
 def _reftests():
-    exe = os.path.join(ROOT, "tests", "cpp", "reftests_gpu")
-    if os.path.isdir("/root/reference/Tests"):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "include", "mlgpu"), "reftests"], stdout=subprocess.DEVNULL)
+    exe = os.path.join(ROOT, "oracle", "_ref", "reftests_gpu")
     if not os.path.exists(exe):
-        pytest.skip("tests/cpp/reftests_gpu not built (it is made from the reference's Tests/ where that checkout exists)")
+        pytest.skip("oracle/_ref/reftests_gpu not built (oracle/Makefile makes it from the reference's Tests/ where that checkout exists)")
     return exe
 
 

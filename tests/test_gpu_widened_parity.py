@@ -24,7 +24,7 @@ def eng():
 def test_widened_leg_matches_cpu(eng, oracle, name):
     cases = wp.all_cases(eng, oracle)
     if name not in cases:
-        pytest.skip(f"{name}: needs the compiled reference (oracle/_ref) / tests/cpp/libexamples_gpu.so, absent here")
+        pytest.skip(f"{name}: needs the compiled reference (oracle/_ref), absent here")
     got, want, checker = cases[name]()
     assert got.shape == want.shape
     assert_bits_equal(got, want, True, f"bench workload {name} at {wp.VOICES} voices vs {checker}")
@@ -68,9 +68,9 @@ def test_reverb_example_full_bank(monkeypatch):
     compiled on the CPU. (A counted wait that were one too lax would show under load, not in a 512-voice case.)"""
     import ctypes
     from inputs import lcg_noise
-    gso, rso = os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so"), os.path.join(ROOT, "oracle", "_ref", "libexamples_ref.so")
+    gso, rso = os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so"), os.path.join(ROOT, "oracle", "_ref", "libexamples_ref.so")
     if not (os.path.exists(gso) and os.path.exists(rso)):
-        pytest.skip("tests/cpp/libexamples_gpu.so or oracle/_ref/libexamples_ref.so not built here")
+        pytest.skip("oracle/_ref/libexamples_gpu.so or oracle/_ref/libexamples_ref.so not built here")
     V, T, n = 65536, 16, 2048
     fp = ctypes.POINTER(ctypes.c_float)
     G, R = ctypes.CDLL(gso), ctypes.CDLL(rso)

@@ -145,19 +145,28 @@ int main()
 """
 
 
+SCALAR_GOLDEN = os.path.join(ROOT, "tests", "golden", "scalar_probe.txt")   # SCALAR_PROBE built against the reference's headers: its printout
+
+
+def _scalar_probe(tmp_path, name, header, inc):
+    src = tmp_path / f"probe_{name}.cpp"
+    src.write_text(SCALAR_PROBE.replace("HEADER", header))
+    exe = tmp_path / f"probe_{name}"
+    r = subprocess.run(["g++", "-std=c++17", "-O2", "-w"] + inc + [str(src), "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout.splitlines()
+
+
 def test_scalar_helpers_match_the_reference(tmp_path):
     """mlscalar.h against the reference's own MLDSPScalarMath.h / MLDSPProjections.h: one probe program, built once with each, must
-    print the same bits for a sweep of every function (const_math, the scalar templates, RandomScalarSource, the projections)."""
-    if not os.path.exists(os.path.join(REF, "source", "DSP", "MLDSPProjections.h")):
-        pytest.skip("no reference checkout here")
-    outs = []
-    for name, header, inc in (("own", '"mlscalar.h"', ["-I" + COMPAT]), ("ref", '"MLDSPProjections.h"', ["-I" + os.path.join(REF, "source", "DSP"), "-include", "iostream", "-include", "string"])):
-        src = tmp_path / f"probe_{name}.cpp"
-        src.write_text(SCALAR_PROBE.replace("HEADER", header))
-        exe = tmp_path / f"probe_{name}"
-        r = subprocess.run(["g++", "-std=c++17", "-O2", "-w"] + inc + [str(src), "-o", str(exe)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-3000:]
-        outs.append(subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout.splitlines())
-    assert len(outs[0]) == len(outs[1]) > 1500
-    bad = [(a, b) for a, b in zip(*outs) if a != b]
+    print the same bits for a sweep of every function (const_math, the scalar templates, RandomScalarSource, the projections).
+    The reference's printout is stored (tests/golden/scalar_probe.txt); where the reference checkout exists the probe is built
+    against it as well and must still print exactly the stored lines."""
+    want = open(SCALAR_GOLDEN).read().splitlines()
+    if os.path.exists(os.path.join(REF, "source", "DSP", "MLDSPProjections.h")):
+        ref = _scalar_probe(tmp_path, "ref", '"MLDSPProjections.h"', ["-I" + os.path.join(REF, "source", "DSP"), "-include", "iostream", "-include", "string"])
+        assert ref == want, "tests/golden/scalar_probe.txt is not what the reference's headers print"
+    own = _scalar_probe(tmp_path, "own", '"mlscalar.h"', ["-I" + COMPAT])
+    assert len(own) == len(want) > 1500
+    bad = [(a, b) for a, b in zip(own, want) if a != b]
     assert not bad, bad[:10]

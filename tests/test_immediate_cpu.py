@@ -1,5 +1,5 @@
 """The source shim's immediate mode without a GPU: the reference's own unit tests compile unchanged against the shim
-(include/mlgpu/Makefile: reftests - madronalib's header names are forwarded by include/mlgpu/compat/dsp) and, with no device, every
+(oracle/Makefile: _ref/reftests_gpu - madronalib's header names are forwarded by include/mlgpu/compat/dsp) and, with no device, every
 test case that does DSPVector arithmetic fails with the engine's error - there is no CPU arithmetic behind the shim. The GPU half is
 tests/test_gpu_immediate.py."""
 import os
@@ -8,15 +8,13 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "reftests_gpu")
+EXE = os.path.join(ROOT, "oracle", "_ref", "reftests_gpu")
 
 
 def test_reference_unit_tests_compile_unchanged_and_fail_loudly_without_a_device():
     import madronalib_amd as ml
-    if os.path.isdir("/root/reference/Tests"):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "include", "mlgpu"), "reftests"], stdout=subprocess.DEVNULL)
     if not os.path.exists(EXE):
-        pytest.skip("tests/cpp/reftests_gpu is built from the reference's Tests/ where that checkout exists")
+        pytest.skip("oracle/_ref/reftests_gpu is built from the reference's Tests/ where that checkout exists")
     if ml.device_count() > 0:
         pytest.skip("a GPU is visible here (tests/test_gpu_immediate.py runs the binary on it)")
     # (without the reference's two-thread DSPBuffer case: host-only, and a race by construction - see tests/test_gpu_immediate.py)

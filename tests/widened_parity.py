@@ -146,10 +146,10 @@ def synth_case(eng, orc):
 
 def reverb_case(eng_unused=None):
     """bench.py --workload reverb: the reference's examples/audio-and-midi/reverb.cpp compiled unchanged against the shim
-    (tests/cpp/libexamples_gpu.so) and against the reference (oracle/_ref/libexamples_ref.so); stereo noise in, both outputs."""
+    (oracle/_ref/libexamples_gpu.so) and against the reference (oracle/_ref/libexamples_ref.so); stereo noise in, both outputs."""
     from inputs import lcg_noise
     V, T = VOICES, 16
-    G = ctypes.CDLL(os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so"))
+    G = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so"))
     R = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libexamples_ref.so"))
     fp = ctypes.POINTER(ctypes.c_float)
     G.example_reverb_gpu_run.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, fp, fp, fp, fp, ctypes.c_char_p, ctypes.c_size_t]
@@ -171,6 +171,6 @@ def all_cases(eng, orc):
     cases = {"resample": lambda: resample_case(eng, orc), "strings": lambda: strings_case(eng, orc)}
     if _have_ref():
         cases.update({"events": lambda: events_case(eng), "synth": lambda: synth_case(eng, orc)})
-        if os.path.exists(os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so")):
+        if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so")):
             cases["reverb"] = lambda: reverb_case()
     return cases

@@ -1,11 +1,11 @@
 """Developer tool: throughput of the reference's own reverb example (examples/audio-and-midi/reverb.cpp, compiled unchanged
-against the shim: tests/cpp/libexamples_gpu.so) for V independent reverbs.   python tools/aaltoverb_bench.py [V] [T] [options]"""
+against the shim: oracle/_ref/libexamples_gpu.so) for V independent reverbs.   python tools/aaltoverb_bench.py [V] [T] [options]"""
 import ctypes
 import os
 import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-L = ctypes.CDLL(os.path.join(ROOT, "tests", "cpp", "libexamples_gpu.so"))
+L = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libexamples_gpu.so"))
 L.example_reverb_gpu_bench.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_char_p, ctypes.c_size_t]
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 16
