@@ -37,14 +37,11 @@ inline Rec makeRec(uint32_t vec, uint32_t type, int time, uint32_t flags, float 
   return Rec{vec, type | (t << 8) | (flags << 16), v1, v2};
 }
 
-#ifndef MLGPU_E2S_WAVES
-#define MLGPU_E2S_WAVES 4
-#endif
 // ROWS01: only the pitch and gate rows are wanted (what a Synth's voices usually read): an instance of the kernel without the controller
 // rows, the voice-index row and the elapsed-time row. Those are half of the general loop's code and registers; without them the
 // instance keeps its state in registers instead of scratch, and its loop has fewer memory round trips per DSPVector.
 template <bool ROWS01>
-__global__ __launch_bounds__(256, MLGPU_E2S_WAVES) void e2s_kernel(const E2SArgs aIn)
+__global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
 {
   E2SArgs a = aIn;
   if constexpr (ROWS01) a.rowMask &= 3u;
@@ -127,14 +124,11 @@ __global__ __launch_bounds__(256, MLGPU_E2S_WAVES) void e2s_kernel(const E2SArgs
   // be moving: it is stepped sample by sample as ever; what each vector does to the drift glide - hold / end / start / continue -
   // depends on the drift counter alone), rows are written as they come, the slots go back once. Same operations on the same
   // values as the general loop; the state variables are this kernel's own, so the two forms alternate freely.
-#ifndef MLGPU_E2S_BLOCK
-#define MLGPU_E2S_BLOCK 4
-#endif
-  constexpr int kBlock = MLGPU_E2S_BLOCK;
+  constexpr int kBlock = 4;
   typedef float f32x4b __attribute__((ext_vector_type(4)));
   for (size_t t = 0; t < a.T; ++t)
   {
-    if (a.blockPath && !a.s.mpe && t + kBlock <= a.T)
+    if (!a.s.mpe && t + kBlock <= a.T)
     {
       const bool onB = awake && active;
       bool ok = (cursor >= recEnd) || (a.recs[cursor].vec >= (uint32_t)(t + kBlock));
@@ -1813,8 +1807,6 @@ extern "C"
     a.T = nVectors;
     a.rowMask = ev->rowMask;
     a.flags = e->kflags;
-    static const bool noBlocks = getenv("MLGPU_E2S_NO_BLOCKS") != nullptr;
-    a.blockPath = noBlocks ? 0 : 1;
     a.group = ev->group;
     a.slotBase = ev->slotBase;
     a.polyphony = ev->polyphony;

@@ -32,7 +32,6 @@
 #include <mutex>
 #include <new>
 #include <set>
-#include <fstream>
 #include <sstream>
 
 #include "mlgpu_internal.hpp"
@@ -57,20 +56,10 @@ std::mutex g_cacheMutex;
 std::map<std::string, CompiledModule> g_cache;  // key: device id + source
 
 // The options every run-time kernel is compiled with (part of the disk cache's key): the ahead-of-time build's own
-// (csrc/Makefile) apart from its scheduling strategy. MLGPU_JIT_EXTRA_OPTS adds space-separated options for A/B
-// measurements, e.g. "-mllvm -amdgpu-sched-strategy=max-ilp" (profiles/archive/r03_jit_maxilp.txt: what it does to config 5).
+// (csrc/Makefile) apart from its scheduling strategy, max-ilp (profiles/archive/r03_jit_maxilp.txt: what it does to config 5).
 const std::vector<std::string>& jitOptions()
 {
-  static const std::vector<std::string> opts = [] {
-    std::vector<std::string> o = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"};
-    if (const char* extra = getenv("MLGPU_JIT_EXTRA_OPTS"))
-    {
-      std::istringstream in(extra);
-      std::string tok;
-      while (in >> tok) o.push_back(tok);
-    }
-    return o;
-  }();
+  static const std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"};
   return opts;
 }
 
@@ -579,7 +568,6 @@ struct mlgpu_graph
   std::vector<char> emitted;     // mlgpu_graph_emit: the gfx950 code object
   size_t memFloatsPerVoice{0};
   bool windowedRings{false};     // rings as [block][chunk][lane][8] behind LDS windows (mlgpu_graph_set_delay_layout)
-  bool fbAhead{true};            // kept DSPVectors (feedback nodes) are fetched two quads ahead; MLGPU_GRAPH_FB_AHEAD=0 for A / B
   bool transposedIfPossible{false};  // graph_set_delay_layout(3)
   bool rowAddr32{false};         // layout 0: ring rows behind 32-bit offsets from a wave-uniform base where a ring allows it (VoiceMem::ringPtr); set at compile
   bool earlyRows{false};         // layout 0: the ring reads of the outer graph's delay nodes issued ahead by LDS-DMA (RingCore::readEarly); set at compile
@@ -595,12 +583,6 @@ struct mlgpu_graph
   int compiledVoicesPerLane{1};
   int unrollQ{1};                // quads per trip of the sample loop
   int oscTripQ{2};               // quads per trip of the oscillators' sparse polyBLEP (0: per sample; mldsp_procs.hpp: trip_u)
-  std::string waveClockPath;     // MLGPU_GRAPH_WAVE_CLOCK=<file>: every wavefront of a launch stamps its start and end; the last launch's table is written there
-  unsigned long long* d_waveClock{nullptr};
-  bool lockOscillators{true};    // a SawGen and a PulseGen on one frequency node share their trip while their phase counters are equal; MLGPU_GRAPH_LOCK_OSC=0 for A / B
-  int takeTurns{2};              // the wavefronts of a SIMD rotate through the priority levels (mldsp_math.hpp): 0 off, 1 by their own progress, 2 by the shared clock; MLGPU_GRAPH_TURNS
-  int turnClockShift{13};        // a turn of the clock form lasts 2^shift ticks of 10 ns (82 us: the best of 2^7 .. 2^18, profiles/r04_take_turns.txt); MLGPU_GRAPH_TURN_CLOCK
-  int prefetchQ{1};              // streamed inputs are loaded one quad ahead of their use (0: where they are used)
   std::string lastError;         // mlgpu_graph_last_error
   mlgpu_events* events{nullptr}; // mlgpu_graph_bind_events: the object the NODE_EVENT_ROW nodes read
   bool hasEventRows{false};
@@ -618,6 +600,8 @@ struct mlgpu_graph
   bool aotDone{false};           // an engine-less graph whose ahead-of-time compile has been collected (mlgpu_graph_compile_poll keeps answering MLGPU_OK)
   int eventOffset{-1};           // frame offset of the block being processed (mlgpu_graph_process_events), -1: none pending
   int minWaves{0};               // wavefronts per SIMD the kernel's register budget must allow (0: the compiler's choice), generateBudgeted
+  int minWavesHook{-1};          // test hook MLGPU_GRAPH_MIN_WAVES (layoutAndGenerate): generateBudgeted's bound fixed; -1: not set
+  bool rowAddr64{false};         // test hook MLGPU_GRAPH_ROW_ADDR32=0 (layoutAndGenerate): state and ring rows by 64-bit addresses
   // Online tuning (mlgpu_graph_set_autotune): every variant (voices per lane x quads per trip) computes the same bits from
   // the same state arrays, so the first process calls simply take turns, are timed, and the fastest one stays.
   struct Variant
@@ -704,7 +688,7 @@ static bool isOscTrip(const mlgpu_graph* g, const Node& n)
 static int lockedPartner(const mlgpu_graph* g, size_t i)
 {
   const Node& n = g->nodes[i];
-  if (!g->lockOscillators || !isOscTrip(g, n) || n.kind != MLGPU_PROC_SAW_GEN) return -1;
+  if (!isOscTrip(g, n) || n.kind != MLGPU_PROC_SAW_GEN) return -1;
   for (size_t j = 0; j < g->nodes.size(); ++j)
   {
     const Node& m = g->nodes[j];
@@ -734,7 +718,7 @@ static int streamLockPulseOf(const mlgpu_graph* g, size_t i)
   auto streamedOsc = [&](const Node& m, int kind) {
     return m.type == NODE_PROC && m.kind == kind && m.region < 0 && m.rate == RATE_AUDIO && !m.in.empty() && g->nodes[m.in[0]].rate != RATE_VOICE;
   };
-  if (!g->lockOscillators || !streamedOsc(n, MLGPU_PROC_SAW_GEN)) return -1;
+  if (!streamedOsc(n, MLGPU_PROC_SAW_GEN)) return -1;
   for (size_t j = 0; j < g->nodes.size(); ++j)
   {
     const Node& m = g->nodes[j];
@@ -899,7 +883,7 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
       s << "};\n";
     }
   // windowed rings: the latency of a sector refill is hidden by other waves only, so keep at least two per SIMD
-  s << "extern \"C\" __global__ __launch_bounds__(256" << ((g->transposedRings && g->totalRings == 1) ? ", 4" : (g->sectorRings && g->totalRings) ? (getenv("MLGPU_SECTOR_WAVES") ? std::string(", ") + getenv("MLGPU_SECTOR_WAVES") : std::string(", 1")) : (g->windowedRings && g->totalRings) ? ", 2" : (g->minWaves ? ", " + std::to_string(g->minWaves) : std::string())) << ") void mlgpu_graph_kernel(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
+  s << "extern \"C\" __global__ __launch_bounds__(256" << ((g->transposedRings && g->totalRings == 1) ? ", 4" : (g->sectorRings && g->totalRings) ? ", 1" : (g->windowedRings && g->totalRings) ? ", 2" : (g->minWaves ? ", " + std::to_string(g->minWaves) : std::string())) << ") void mlgpu_graph_kernel(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
   if (g->hasImpulse)
   {
     s << "  __shared__ float ldsTable[32];\n  if (threadIdx.x < 17) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];\n  __syncthreads();\n";
@@ -927,9 +911,8 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
       << "  float* const ldsEarlyWave = ldsEarly + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * " << g->earlySlots * 64 << ";\n";
   // a group sum of 16 voices (one instrument's voices): four quads of the wavefront's 64 voices are parked in LDS and every lane
   // then adds up ONE (instrument, sample) pair in voice order - 2.3 instructions per voice-sample where the lane-shift chain
-  // (group_sum_in_order) takes 16 (MLGPU_GRAPH_GROUP_SUM=dpp: that form)
-  static const bool dppSum = getenv("MLGPU_GRAPH_GROUP_SUM") && !strcmp(getenv("MLGPU_GRAPH_GROUP_SUM"), "dpp");
-  auto ldsSum = [&](size_t o) { return VL == 1 && g->outputGroup[o] == 16 && !dppSum; };
+  // (group_sum_in_order) takes 16
+  auto ldsSum = [&](size_t o) { return VL == 1 && g->outputGroup[o] == 16; };
   for (size_t o = 0; o < g->outputs.size(); ++o)
     if (ldsSum(o))
       s << "  __shared__ float ldsSum" << o << "[4 * kGroup16Strip];\n  float* const strip" << o << " = ldsSum" << o << " + (threadIdx.x >> 6) * kGroup16Strip;\n";
@@ -955,12 +938,11 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
   const std::string ringLane = partialWaves ? "vr" : "v";
   // a row of the state memory at this lane: the row's address is wave-uniform (scalar arithmetic), the lane's place a 32-bit offset on
   // it - one memory instruction where `a.state[row * a.V + v]` with a 64-bit v is a 64-bit vector add in front of it
-  const bool stateAddr32 = g->V < ((size_t)1 << 30) && !(getenv("MLGPU_GRAPH_ROW_ADDR32") && !strcmp(getenv("MLGPU_GRAPH_ROW_ADDR32"), "0"));  // (developer knob, A / B)
+  const bool stateAddr32 = g->V < ((size_t)1 << 30) && !g->rowAddr64;
   if (stateAddr32) s << "  const uint32_t v4_0 = (uint32_t)v_0 * 4u;\n";
   auto stateRef = [&](const std::string& row, int l) {
     return stateAddr32 ? "*state_row(a, " + row + ", v4" + sfx(l) + ")" : "a.state[(size_t)(" + row + ") * a.V + v" + sfx(l) + "]";
   };
-  if (!g->waveClockPath.empty()) s << "  const unsigned long long waveClock0 = __builtin_amdgcn_s_memrealtime();\n";
   // a lane whose second voice does not exist recomputes its first one: same inputs, same state, same stores
   for (int l = 1; l < VL; ++l)
   {
@@ -1085,21 +1067,20 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
   // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
   // whole HBM round trip per quad, and with four wavefronts per SIMD there are long stretches with only one or two of them able to
   // issue (one wavefront alone issues at 40 % of the SIMD's rate). The very last quad of a launch loads itself again.
-  const int PF = (g->nInputs && g->prefetchQ) ? 1 : 0;
+  const bool PF = g->nInputs > 0;
   if (PF) s << "  if (a.T == 0) return;\n";
   for (int i = 0; PF && i < g->nInputs; ++i)
     for (int l = 0; l < VL; ++l)
       s << "  const f32x4* pf" << i << sfx(l) << " = in" << i << sfx(l) << ";\n  f32x4 nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
-  if (g->fbAhead)
-    for (size_t i = 0; i < g->nodes.size(); ++i)
-      if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].region < 0)
-        for (int l = 0; l < VL; ++l)
-        {
-          const std::string nm = std::to_string(i) + sfx(l);
-          s << "  float fbn" << nm << "[4], fbm" << nm << "[4];\n#pragma unroll\n  for (int kk = 0; kk < 4; ++kk)\n  {\n    fbn" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + kk", l)
-            << ");\n    fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + 4 + kk", l) << ");\n  }\n";
-        }
-  if (g->takeTurns) s << "  const uint32_t turn0 = wave_slot();\n";
+  for (size_t i = 0; i < g->nodes.size(); ++i)
+    if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].region < 0)
+      for (int l = 0; l < VL; ++l)
+      {
+        const std::string nm = std::to_string(i) + sfx(l);
+        s << "  float fbn" << nm << "[4], fbm" << nm << "[4];\n#pragma unroll\n  for (int kk = 0; kk < 4; ++kk)\n  {\n    fbn" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + kk", l)
+          << ");\n    fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + 4 + kk", l) << ");\n  }\n";
+      }
+  s << "  const uint32_t turn0 = wave_slot();\n";
   s << "  for (size_t t = 0; t < a.T; ++t)\n  {\n";
   // (Rounds 3-4 walked the event records inside this kernel - 134 spilled registers, 0.35 scalar / branch instructions per vector
   // one; round 5: the record walk is e2s_ctl_kernel's, this kernel expands its control records - mldsp_events.hpp.)
@@ -1130,8 +1111,7 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
     // the quads in trips of oscTripQ: the oscillators' samples of a trip first, then its quads (fully unrolled: qq is a constant)
     const int tq = ringTrips ? 2 : g->oscTripQ, unroll = (g->windowedRings && g->totalRings) ? 1 : std::max(1, g->unrollQ / tq);
     s << "#pragma unroll " << unroll << "\n    for (int q2 = 0; q2 < 16; q2 += " << tq << ")\n    {\n";
-    if (g->takeTurns == 2) s << "    take_turns_by_clock(turn0, " << g->turnClockShift << ");\n";
-    else if (g->takeTurns) s << "    take_turns(turn0 + (uint32_t)t * " << 16 / tq << "u + (uint32_t)(q2 / " << tq << "));\n";
+    s << "    take_turns_by_clock(turn0, " << kTurnClockShift << ");\n";
     std::vector<char> paired(g->nodes.size(), 0);
     for (size_t i = 0; i < g->nodes.size(); ++i)
       if (lockedPartner(g, i) >= 0) paired[i] = paired[(size_t)lockedPartner(g, i)] = 1;
@@ -1180,20 +1160,15 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
   else
   {
     s << "#pragma unroll " << ((g->windowedRings && g->totalRings) ? 1 : g->unrollQ) << "\n    for (int q = 0; q < 16; ++q)\n    {\n";
-    if (g->takeTurns == 2) s << "      if ((q & 1) == 0) take_turns_by_clock(turn0, " << g->turnClockShift << ");\n";
-    else if (g->takeTurns) s << "      if ((q & 1) == 0) take_turns(turn0 + (uint32_t)t * 8u + (uint32_t)(q >> 1));\n";
+    s << "      if ((q & 1) == 0) take_turns_by_clock(turn0, " << kTurnClockShift << ");\n";
   }
   // the next quad's address: one step on; from a vector's last quad to the next vector's first; the launch's last quad stays
   if (PF) s << "      const bool lastQ = (q == 15), lastT = (t + 1 == a.T);\n";
   for (int i = 0; i < g->nInputs; ++i)
     for (int l = 0; l < VL; ++l)
     {
-      if (PF == 0)
-        s << "      const f32x4 xin" << i << sfx(l) << " = __builtin_nontemporal_load(in" << i << sfx(l) << " + t * a.in[" << i << "].strideT + q * a.in["
-          << i << "].strideQ);\n";
-      else
-        s << "      const f32x4 xin" << i << sfx(l) << " = nx" << i << sfx(l) << ";\n      pf" << i << sfx(l) << " += lastQ ? (lastT ? (size_t)0 : a.in[" << i
-          << "].strideT - 15 * a.in[" << i << "].strideQ) : a.in[" << i << "].strideQ;\n      nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
+      s << "      const f32x4 xin" << i << sfx(l) << " = nx" << i << sfx(l) << ";\n      pf" << i << sfx(l) << " += lastQ ? (lastT ? (size_t)0 : a.in[" << i
+        << "].strideT - 15 * a.in[" << i << "].strideQ) : a.in[" << i << "].strideQ;\n      nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
     }
   for (size_t o = 0; o < g->outputs.size(); ++o)
     for (int l = 0; l < VL; ++l) s << "      f32x4 y" << o << sfx(l) << ";\n";
@@ -1204,17 +1179,13 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
   // AHEAD (round 5; they were written 14 quads ago). Fetched at the top of the quad that uses them, every quad of a feedback graph
   // stood still for a memory round trip, behind the stores of the quad before (memory operations of a wavefront complete in issue
   // order): 256 round trips per launch of 16 DSPVectors were the whole launch time of the plucked-string bank, whatever the ring
-  // layout. MLGPU_GRAPH_FB_AHEAD=0: the round-4 form (A / B).
+  // layout.
   for (size_t i = 0; i < g->nodes.size(); ++i)
     if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].region < 0)
       for (int l = 0; l < VL; ++l)
       {
         const std::string nm = std::to_string(i) + sfx(l);
-        if (!g->fbAhead)
-          s << "      float fbv" << nm << "[4];\n#pragma unroll\n      for (int kk = 0; kk < 4; ++kk) fbv" << nm << "[kk] = u2f("
-            << stateRef(std::to_string(g->nodes[i].sOff) + " + q * 4 + kk", l) << ");\n";
-        else
-          s << "      float fbv" << nm << "[4];\n#pragma unroll\n      for (int kk = 0; kk < 4; ++kk)\n      {\n        fbv" << nm << "[kk] = fbn" << nm << "[kk];\n        fbn" << nm
+        s << "      float fbv" << nm << "[4];\n#pragma unroll\n      for (int kk = 0; kk < 4; ++kk)\n      {\n        fbv" << nm << "[kk] = fbn" << nm << "[kk];\n        fbn" << nm
             << "[kk] = fbm" << nm << "[kk];\n        fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + ((q + 2) & 15) * 4 + kk", l) << ");\n      }\n";
       }
   for (size_t i = 0; i < g->nodes.size(); ++i)
@@ -1471,10 +1442,6 @@ std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
   for (size_t i = 0; i < g->nodes.size(); ++i)
     if (g->nodes[i].type == NODE_PROC)
       for (int l = 0; l < VL; ++l) s << "  p" << i << sfx(l) << ".store(m" << i << sfx(l) << ");\n";
-  if (!g->waveClockPath.empty())
-    s << "  if ((threadIdx.x & 63) == 0 && a.waveClock)\n  {\n    unsigned long long* w = a.waveClock + (blk * 4 + threadIdx.x / 64) * 4;\n"
-         "    w[0] = waveClock0;\n    w[1] = __builtin_amdgcn_s_memrealtime();\n    w[2] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));\n"
-         "    w[3] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));\n  }\n";
   s << "}\n";
   return s.str();
 }
@@ -1504,29 +1471,15 @@ static bool codeObjectNumber(const std::vector<char>& code, const char* key, lon
 // with a bound of four wavefronts per SIMD - then three, then two - and the first build that spills moderately (up to 640 bytes
 // of scratch per lane) is kept (the patch of SURVEY 8d: 170 VGPRs ->
 // 128 + 156 bytes of scratch per lane, 1.82 -> 1.46 ms; the voice with its EventsToSignals rows inside: 259 -> 128 + 528 bytes,
-// 3.13 -> 1.56 ms, where bounds of two and three wavefronts give 1.96 and 1.85). MLGPU_GRAPH_MIN_WAVES=0 / N overrides
-// (developer knob).
+// 3.13 -> 1.56 ms, where bounds of two and three wavefronts give 1.96 and 1.85). The test hook MLGPU_GRAPH_MIN_WAVES=0 / N
+// overrides (g->minWavesHook).
 static bool generateBudgeted(mlgpu_graph* g, int vl, std::string& source, std::vector<char>& code, std::string& log)
 {
-  const char* knob = getenv("MLGPU_GRAPH_MIN_WAVES");
-  g->minWaves = knob ? atoi(knob) : 0;
+  g->minWaves = std::max(0, g->minWavesHook);
   source = generateGraphSource(g, vl);
-  // developer aid for elimination experiments (what would the launch cost WITHOUT this branch / that test?): the kernel source comes
-  // from a file instead - an edited copy of mlgpu_graph_source()'s text. Its results are whatever the file computes.
-  if (const char* file = getenv("MLGPU_GRAPH_SOURCE_FILE"))
-  {
-    std::ifstream in(file);
-    std::stringstream text;
-    text << in.rdbuf();
-    if (!text.str().empty())
-    {
-      source = text.str();
-      return getCode(source, code, log);
-    }
-  }
   if (!getCode(source, code, log)) return false;
   long vgprs = 0;
-  if (knob || (g->windowedRings && g->totalRings) || g->V < 65536 || !codeObjectNumber(code, ".vgpr_count", vgprs) || vgprs <= 128) return true;
+  if (g->minWavesHook >= 0 || (g->windowedRings && g->totalRings) || g->V < 65536 || !codeObjectNumber(code, ".vgpr_count", vgprs) || vgprs <= 128) return true;
   // the tightest bound whose build spills moderately: four wavefronts per SIMD, else three, else two
   for (int waves = 4; waves >= 2; --waves)
   {
@@ -1908,18 +1861,6 @@ extern "C"
     {
       hipSetDevice(g->e->device);
       hipStreamSynchronize(g->e->stream);
-    }
-    if (g->d_waveClock)
-    {
-      const size_t words = (g->V + 255) / 256 * 4 * 4;
-      std::vector<unsigned long long> host(words);
-      if (hipMemcpy(host.data(), g->d_waveClock, words * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess)
-        if (FILE* f = fopen(g->waveClockPath.c_str(), "wb"))
-        {
-          fwrite(host.data(), sizeof(unsigned long long), words, f);
-          fclose(f);
-        }
-      hipFree(g->d_waveClock);
     }
     if (g->d_coeffs) hipFree(g->d_coeffs);
     if (g->d_state) hipFree(g->d_state);
@@ -2326,13 +2267,10 @@ extern "C"
     // mixdown: 4 wavefronts x kMixStrip floats = 21 KiB; a 16-voice group sum: 4 x kGroup16Strip = 20.3 KiB). A layout that does not fit
     // next to them falls back (layout 3) or is refused here with the sizes, not by hiprtc / the module loader.
     size_t ldsOther = g->hasImpulse ? 128 : 0;
+    for (size_t o = 0; o < g->outputs.size(); ++o)
     {
-      const bool dppSum = getenv("MLGPU_GRAPH_GROUP_SUM") && !strcmp(getenv("MLGPU_GRAPH_GROUP_SUM"), "dpp");
-      for (size_t o = 0; o < g->outputs.size(); ++o)
-      {
-        if (g->outputMix[o]) ldsOther += sizeof(float) * 4 * (size_t)kHostMixStripFloats;
-        else if (g->outputGroup[o] == 16 && !dppSum) ldsOther += sizeof(float) * 4 * (size_t)kHostGroup16StripFloats;
-      }
+      if (g->outputMix[o]) ldsOther += sizeof(float) * 4 * (size_t)kHostMixStripFloats;
+      else if (g->outputGroup[o] == 16) ldsOther += sizeof(float) * 4 * (size_t)kHostGroup16StripFloats;
     }
     constexpr size_t kLdsBytes = 160 * 1024;
     const size_t ldsLayout2 = (size_t)g->totalRings * 4 * 40 * 64 * sizeof(float), ldsLayout1 = (size_t)g->totalRings * 8 * 256 * sizeof(float);
@@ -2372,47 +2310,44 @@ extern "C"
                                                  " rings) next to " + kib(ldsOther) + " of output strips and tables; a workgroup has 160 KiB");
     if (ldsOther > kLdsBytes)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: " + kib(ldsOther) + " of LDS for the outputs summed inside the kernel (21 KiB per mixed-down output, 20.3 KiB per 16-voice group sum); a workgroup has 160 KiB");
+    // test hooks, not settings: the differential tests build a kernel's second form with these
+    const char* minWaves = getenv("MLGPU_GRAPH_MIN_WAVES");      // N: generateBudgeted's bound, N wavefronts per SIMD (0: none)
+    const char* rowAddr32 = getenv("MLGPU_GRAPH_ROW_ADDR32");    // "0": 64-bit state and ring row addresses
+    const char* earlyReads = getenv("MLGPU_GRAPH_EARLY_READS");  // "0": the plain ring loads
+    const char* oscTrip = getenv("MLGPU_GRAPH_OSC_TRIP");        // 0: polyBLEP per sample, else 1, 2 or 4 quads per trip
+    g->minWavesHook = minWaves ? atoi(minWaves) : -1;
+    g->rowAddr64 = rowAddr32 && !strcmp(rowAddr32, "0");
     // ring layout 0: rows behind 32-bit offsets where every delay node's memory stays below 4 GiB (VoiceMem::ringPtr)
     g->rowAddr32 = false;
-    if (!g->windowedRings && g->totalRings && g->V < ((size_t)1 << 22) && !(getenv("MLGPU_GRAPH_ROW_ADDR32") && !strcmp(getenv("MLGPU_GRAPH_ROW_ADDR32"), "0")))
+    if (!g->windowedRings && g->totalRings && g->V < ((size_t)1 << 22) && !g->rowAddr64)
       g->rowAddr32 = true;  // (node by node in the generator: a ring of the bank at most 4 GiB)
     // ring layout 0: the outer graph's ring reads by LDS-DMA ahead of the sample's arithmetic, a 256-byte landing slot per read and wavefront
     g->earlyRows = false;
     g->earlySlots = 0;
     for (Node& n : g->nodes) n.earlySlot = -1;
+    if (!g->windowedRings && g->totalRings && !(earlyReads && !strcmp(earlyReads, "0")))
     {
-      const char* er = getenv("MLGPU_GRAPH_EARLY_READS");  // developer knob (A / B): 0 = the plain loads
-      if (!g->windowedRings && g->totalRings && !(er && !strcmp(er, "0")))
-      {
-        int slots = 0;
-        for (Node& n : g->nodes)
-          if (n.type == NODE_PROC && n.region < 0 && n.role == ROLE_NONE && mlgpu_proc_rings(n.kind))
-          {
-            n.earlySlot = slots;
-            slots += n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? 2 : 1;
-          }
-        // (one ring - a plucked string - has nothing to issue together: 0.127 of the peak with the early read against 0.142 without)
-        if (slots >= 3 && (size_t)slots * 4 * 64 * sizeof(float) + ldsOther <= kLdsBytes)
+      int slots = 0;
+      for (Node& n : g->nodes)
+        if (n.type == NODE_PROC && n.region < 0 && n.role == ROLE_NONE && mlgpu_proc_rings(n.kind))
         {
-          g->earlyRows = true;
-          g->earlySlots = slots;
+          n.earlySlot = slots;
+          slots += n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? 2 : 1;
         }
-        else
-          for (Node& n : g->nodes) n.earlySlot = -1;
+      // (one ring - a plucked string - has nothing to issue together: 0.127 of the peak with the early read against 0.142 without)
+      if (slots >= 3 && (size_t)slots * 4 * 64 * sizeof(float) + ldsOther <= kLdsBytes)
+      {
+        g->earlyRows = true;
+        g->earlySlots = slots;
       }
+      else
+        for (Node& n : g->nodes) n.earlySlot = -1;
     }
-    const char* forced = getenv("MLGPU_GRAPH_UNROLL");  // developer knob: quads per trip of the sample loop
     // delay graphs wait on their ring reads: two quads per trip keep more of them in flight (allpass4: 5.4 vs 4.5 x 10^10)
-    g->unrollQ = forced ? std::max(1, atoi(forced)) : ((g->totalRings && !g->windowedRings) ? 2 : 1);
-    if (const char* wc = getenv("MLGPU_GRAPH_WAVE_CLOCK")) g->waveClockPath = wc;
-    if (const char* tt = getenv("MLGPU_GRAPH_TURNS")) g->takeTurns = std::min(2, std::max(0, atoi(tt)));
-    if (const char* tc = getenv("MLGPU_GRAPH_TURN_CLOCK")) g->turnClockShift = std::min(24, std::max(0, atoi(tc)));
-    if (const char* lk = getenv("MLGPU_GRAPH_LOCK_OSC")) g->lockOscillators = atoi(lk) != 0;
-    if (const char* pf = getenv("MLGPU_GRAPH_PREFETCH")) g->prefetchQ = atoi(pf) != 0;  // developer knob (A / B)
-    if (const char* fa = getenv("MLGPU_GRAPH_FB_AHEAD")) g->fbAhead = atoi(fa) != 0;
-    if (const char* trip = getenv("MLGPU_GRAPH_OSC_TRIP"))  // developer knob: 0 = polyBLEP per sample (A / B), else 1, 2 or 4 quads per trip
+    g->unrollQ = (g->totalRings && !g->windowedRings) ? 2 : 1;
+    if (oscTrip)
     {
-      const int t = atoi(trip);
+      const int t = atoi(oscTrip);
       g->oscTripQ = (t == 1 || t == 2 || t == 4) ? t : 0;
     }
     if (g->sectorRings && g->totalRings && g->oscTripQ > 0) g->oscTripQ = 2;  // (one trip structure: the rings' trips are two quads)
@@ -2874,12 +2809,6 @@ extern "C"
     a.t0 = g->vectorCount;
     a.flags = g->e->kflags;
     a.impulseTable = g->e->d_impulseTable;
-    if (!g->waveClockPath.empty())
-    {
-      const size_t waves = (g->V + 255) / 256 * 4;
-      if (!g->d_waveClock && hipMalloc((void**)&g->d_waveClock, waves * 4 * sizeof(unsigned long long)) != hipSuccess) g->d_waveClock = nullptr;
-      a.waveClock = g->d_waveClock;
-    }
     for (int i = 0; i < g->nInputs; ++i)
     {
       if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null / misaligned input");

@@ -56,7 +56,6 @@ struct E2SArgs
   int group, polyphony, slotBase;  // lane = instrument * group + (voice slot - slotBase)
   uint32_t rowMask;                // rows that are computed (mlgpu_events_set_wanted_rows); bit r = row r of `out`
   uint32_t flags;                  // MLGPU_KFLAG_*
-  int blockPath;                   // 0: every vector on its own (MLGPU_E2S_NO_BLOCKS in the environment, for A / B measurements)
   E2SSettings s;
 };
 

@@ -21,14 +21,7 @@ namespace mldev
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kChainBlock = 256;
-// the wavefronts of a SIMD take turns at the priority levels (mldsp_math.hpp: take_turns_by_clock) - 0 for A / B builds
-#ifndef MLGPU_CHAIN_TURNS
-#define MLGPU_CHAIN_TURNS 1
-#endif
-#ifndef MLGPU_CHAIN_TURN_SHIFT
-#define MLGPU_CHAIN_TURN_SHIFT 13
-#endif
-constexpr int kTurnClockShift = MLGPU_CHAIN_TURN_SHIFT;  // 82 us per turn (graph kernels: the best of 2^7 .. 2^18 ticks, profiles/r04_take_turns.txt)
+// the wavefronts of a SIMD take turns at the priority levels (mldsp_math.hpp: take_turns_by_clock; mlgpu_device_args.hpp: kTurnClockShift)
 
 // ---- the voices of a wavefront summed inside the voice kernel (chain_mix_kernel) ----
 // mlgpu_mixdown's first stage - the balanced tree over 64 consecutive voices, a[i] += a[i + d] for d = 1, 2 ... 32 - without the
@@ -95,9 +88,7 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
   const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + v * a.in.strideV : nullptr;
   f32x4* pout = MIX ? nullptr : (f32x4*)a.out.base + v * a.out.strideV;
   const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
-#if MLGPU_CHAIN_TURNS
   const uint32_t slot = wave_slot();
-#endif
   for (size_t t = 0; t < a.T; ++t)
   {
     const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
@@ -105,9 +96,7 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
 #pragma unroll 4
     for (int q = 0; q < 16; ++q)
     {
-#if MLGPU_CHAIN_TURNS
       if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
-#endif
       f32x4 x = {xc, xc, xc, xc};
       if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
       f32x4 y;
@@ -238,13 +227,7 @@ __global__ __launch_bounds__(kChainBlock) void chain_mix_kernel(const ChainArgs 
 // lane (each component rounded exactly like the scalar instruction: same bits) and issue at the scalar instructions' rate
 // (tools/valubench.hip). Stages are paired (p, p + N/2): the pair's inputs are then the previous pair's outputs, one
 // 64-bit register pair, except pair 0 = {x, r[N/2 - 1]}. A tick is 10 packed instructions per stage PAIR instead of 10
-// scalar ones per stage. MLGPU_CASCADE_PACKED=0 keeps the scalar form (A/B measurements, profiles/).
-#ifndef MLGPU_CASCADE_PACKED
-#define MLGPU_CASCADE_PACKED 1
-#endif
-#ifndef MLGPU_CASCADE_QUADS_PER_TRIP
-#define MLGPU_CASCADE_QUADS_PER_TRIP 4
-#endif
+// scalar ones per stage.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int KIND, int N>
@@ -292,7 +275,6 @@ struct SvfCascade
     }
   }
   // all stages active; returns stage N-1's output, i.e. the chain output for sample (tick - (N-1))
-#if MLGPU_CASCADE_PACKED
   MLD float tick(float x) { return tick_in0(f32x2{x, r[H - 1].x}); }
   // in0 = {input of stage 0, input of stage H = r of stage H - 1}
   MLD float tick_in0(f32x2 in0) { return tick_common<false>(in0, in0); }
@@ -356,57 +338,6 @@ struct SvfCascade
     for (int p = 0; p < H; ++p) ic2[p] = MLGPU_SVF_STRICT ? ic2[p] + two * t2[p] : __builtin_elementwise_fma(two, t2[p], ic2[p]);
     return r[H - 1].y;
   }
-#else
-  MLD float tick(float x)
-  {
-    float in[N], t0[N], a[N], b[N], c[N], d[N], t1[N], t2[N], v1[N], v2[N];
-    in[0] = x;
-#pragma unroll
-    for (int s = 1; s < N; ++s) in[s] = get(r, s - 1);
-#pragma unroll
-    for (int s = 0; s < N; ++s) t0[s] = in[s] - get(ic2, s);
-#pragma unroll
-    for (int s = 0; s < N; ++s) b[s] = get(g1, s) * get(ic1, s);
-#pragma unroll
-    for (int s = 0; s < N; ++s) d[s] = get(g0, s) * get(ic1, s);
-#pragma unroll
-    for (int s = 0; s < N; ++s) a[s] = get(g0, s) * t0[s];
-#pragma unroll
-    for (int s = 0; s < N; ++s) c[s] = get(g2, s) * t0[s];
-#pragma unroll
-    for (int s = 0; s < N; ++s) t1[s] = a[s] + b[s];
-#pragma unroll
-    for (int s = 0; s < N; ++s) t2[s] = c[s] + d[s];
-    if (KIND == MLGPU_PROC_LOPASS)
-    {
-#pragma unroll
-      for (int s = 0; s < N; ++s) put(r, s, t2[s] + get(ic2, s));
-    }
-    else if (KIND == MLGPU_PROC_BANDPASS)
-    {
-#pragma unroll
-      for (int s = 0; s < N; ++s) put(r, s, t1[s] + get(ic1, s));
-    }
-    else
-    {
-#pragma unroll
-      for (int s = 0; s < N; ++s) v1[s] = t1[s] + get(ic1, s);
-#pragma unroll
-      for (int s = 0; s < N; ++s) v2[s] = t2[s] + get(ic2, s);
-#pragma unroll
-      for (int s = 0; s < N; ++s) v1[s] = get(kk, s) * v1[s];
-#pragma unroll
-      for (int s = 0; s < N; ++s) v1[s] = in[s] - v1[s];
-#pragma unroll
-      for (int s = 0; s < N; ++s) put(r, s, v1[s] - v2[s]);
-    }
-#pragma unroll
-    for (int s = 0; s < N; ++s) put(ic1, s, svf_acc(get(ic1, s), t1[s]));
-#pragma unroll
-    for (int s = 0; s < N; ++s) put(ic2, s, svf_acc(get(ic2, s), t2[s]));
-    return get(r, N - 1);
-  }
-#endif
   // boundary tick: only stages sLo..sHi (wave-uniform) are active
   MLD float tick_masked(float x, int sLo, int sHi)
   {
@@ -481,7 +412,7 @@ __global__ __launch_bounds__(kChainBlock) void cascade_kernel(const ChainArgs a)
   // QT = 4 (4 KiB of loads in flight per wave) is the measured optimum on config 4: QT = 8 takes all 256 registers and runs
   // 0.570 ms against 0.477, QT = 16 0.491 (round 2, 131 072 channels x 32 DSPVectors) - the kernel is not waiting for its
   // loads (round 3's account, profiles/archive/r03_cfg4_account.md: it is bound by VALU issue, and the streams cost it clock).
-  constexpr int QT = MLGPU_CASCADE_QUADS_PER_TRIP;
+  constexpr int QT = 4;
   const size_t Q = (S - D) / 4;
   size_t q = 0;
   if constexpr (HAS_SIGNAL)
@@ -595,10 +526,6 @@ struct LaneGroup
   }
 };
 
-#ifndef MLGPU_CASCADE_LANES_DPP_SUB
-#define MLGPU_CASCADE_LANES_DPP_SUB 1
-#endif
-
 template <int KIND, int N, int LPC, int R, bool HAS_SIGNAL>
 __device__ __forceinline__ void cascade_lanes_body(const ChainArgs& a)
 {
@@ -641,7 +568,7 @@ __device__ __forceinline__ void cascade_lanes_body(const ChainArgs& a)
   // one tick with every stage active: the lane's first stage reads `x` (group's first lane) or the previous lane's output
   auto fastTick = [&](float x) {
     const f32x2 rr = c.r[H - 1];
-    if constexpr (KIND != MLGPU_PROC_HIPASS && MLGPU_CASCADE_LANES_DPP_SUB)
+    if constexpr (KIND != MLGPU_PROC_HIPASS)
     {
       // t0 of the lane's first stage = input - ic2: with the group's own sample everywhere, then again in the lanes that
       // take the previous lane's output, the DPP hand-over folded into the subtraction (v_sub_f32_dpp; masked lanes keep
@@ -720,14 +647,10 @@ __device__ __forceinline__ void cascade_lanes_body(const ChainArgs& a)
       if (last) __builtin_nontemporal_store(y, (f32x4*)ps);
       ps += s == 15 ? outNext : outStep;
     };
-#if MLGPU_CHAIN_TURNS
     const uint32_t slot = wave_slot();
-#endif
     for (size_t t = 0; t < a.T; ++t)
     {
-#if MLGPU_CHAIN_TURNS
       take_turns_by_clock(slot, kTurnClockShift);
-#endif
       const bool lastVector = (t + 1 == a.T);
       // where the fetch pointer goes when it leaves a vector: on to the next one, or - from the launch's last vector - back
       // to that vector's start

@@ -36,26 +36,17 @@ MLD void apply_fp_mode(uint32_t flags)
 // wavefront of a SIMD runs ahead of the others for the whole launch. A voice bank is launched as exactly as many wavefronts as the
 // chip holds (4 per SIMD at 262 144 voices), nothing is waiting to take a finished wavefront's place, and so the launch ends with a
 // long stretch of three, two and at last one wavefront per SIMD - and one wavefront alone issues at 40 % of a SIMD's rate (DESIGN
-// 3.11). Measured with per-wavefront clocks (tools/wave_clock.py): config 5's wavefronts ended at 52 %, 60 %, 80 % and 100 % of the
-// launch. The cure is to take turns: every `turn` (a trip of a few samples) a wavefront takes the next of the four priority levels,
+// 3.11). Measured with per-wavefront clocks (a developer tool since removed; it is in git history): config 5's wavefronts ended at
+// 52 %, 60 %, 80 % and 100 % of the launch. The cure is to take turns: every `turn` (a trip of a few samples) a wavefront takes the next of the four priority levels,
 // offset by its hardware slot, so the wavefronts of a SIMD hold four different levels that rotate - each gets the same share, they
 // arrive together, and the SIMD keeps its full issue rate to the end. (s_setprio takes an immediate: hence the switch.)
 MLD uint32_t wave_slot() { return (uint32_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3u; }  // HW_REG_HW_ID.wave_id
-// the same by the clock all wavefronts share (100 MHz): the four levels rotate every 2^shift ticks whatever the wavefront's own progress
+// the turns are told by the clock all wavefronts share (100 MHz): the four levels rotate every 2^shift ticks (kTurnClockShift)
+// whatever the wavefront's own progress
 MLD void take_turns_by_clock(uint32_t slot, int shift)
 {
   const uint32_t now = (uint32_t)(__builtin_amdgcn_s_memrealtime() >> shift);
   switch ((now + slot) & 3u)
-  {
-    case 0: __builtin_amdgcn_s_setprio(0); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    case 2: __builtin_amdgcn_s_setprio(2); break;
-    default: __builtin_amdgcn_s_setprio(3); break;
-  }
-}
-MLD void take_turns(uint32_t turn)
-{
-  switch (turn & 3u)
   {
     case 0: __builtin_amdgcn_s_setprio(0); break;
     case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -181,21 +172,11 @@ MLD void group16_sum_store(const float* strip, group16_f32x4* outQuad0, size_t s
 // is flushed in flush mode exactly as sse_max's canonicalization would.
 // Round 4: the pair is ONE instruction, v_med3_f32 - for lo <= hi the median of (x, lo, hi) is min(max(x, lo), hi), a NaN x gives
 // min3 = lo like the pair, and a denormal x is flushed in flush mode like any other operand of the float unit.
-#ifndef MLGPU_CLAMP_MED3
-#define MLGPU_CLAMP_MED3 1
-#endif
 MLD float clamp_const_bounds(float x, float lo, float hi)
 {
-#if MLGPU_CLAMP_MED3
   float r;
   asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "v"(hi));
   return r;
-#else
-  float m, r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(x), "v"(lo));
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(m), "v"(hi));
-  return r;
-#endif
 }
 
 // _mm_cvttps_epi32 / _mm_cvtps_epi32 (MLDSPMathSSE.h:124-125): NaN and out-of-range give

@@ -209,9 +209,6 @@ MLD float phasor_to_saw(float p, float cps)
   return saw - poly_blep<SKIP>(p, BlepFreq<FAST>::make(cps, ANY_PHASE && phase_is_odd(p)));
 }
 
-#ifndef MLGPU_PULSE_SINGLE_BLEP
-#define MLGPU_PULSE_SINGLE_BLEP 1
-#endif
 // phasorToPulse, MLDSPGens.h:342-358: +-1 by pulse width, plus the correction of the rising step at phase 0, minus the
 // correction of the falling step at phase = width (the phase shifted by 1 - width). Written out that is two polyBLEPs per
 // sample - but a lane is almost never inside both zones at once (only when the width is within one sample of 0 or 1), and
@@ -239,7 +236,7 @@ MLD float phasor_to_pulse(float p, float cps, float w)
   if (SKIP && __builtin_amdgcn_ballot_w64(nearUp || nearDown) == 0) return pulse;
   const bool full = f.anyLaneOdd();
   // (a `full` wavefront of the op forms may hold non-finite corrections, for which x + 0 == x does not hold: two evaluations)
-  if (MLGPU_PULSE_SINGLE_BLEP && !(ANY_PHASE && full) && __builtin_amdgcn_ballot_w64(nearUp && nearDown) == 0)
+  if (!(ANY_PHASE && full) && __builtin_amdgcn_ballot_w64(nearUp && nearDown) == 0)
   {
     const float c = f.correction(nearDown ? down : p, nearDown ? loDown : loUp, full);
     return nearDown ? (pulse - c) : (nearUp ? (pulse + c) : pulse);
@@ -1015,9 +1012,7 @@ struct Proc<MLGPU_PROC_ADSR>  // :657-797
     // ands - nine scalar instructions per sample where these are six, and scalar issue is not hidden on this chip)
     asm("" : "+s"(maybe));
     const uint64_t idle = mOff & xz;
-#ifndef MLGPU_X_ADSR_NO_SEGMENT_TEST  // (elimination experiment: wrong results, profiles/r06_synth_scalar_ceiling.txt)
     if (__builtin_expect(maybe != 0, 0)) change_segment(x);
-#endif
     const float yn = y + k * (target - y);
     x1 = lane_select(idle, x1, x);
     y1 = lane_select(idle, y1, y);
@@ -1479,9 +1474,6 @@ struct RingCore  // IntegerDelay's buffer, index and mask
   }
   MLD void flushT(const VoiceMem& m, int ringIdx, uint32_t halfStart)
   {
-#ifdef MLGPU_RING_X_NOFLUSH  // (elimination experiments: wrong results, used to find what a launch waits for - profiles/r05_ring_layouts.txt)
-    return;
-#endif
     f32x4r a[2];
     readHalf(m, ringIdx, a);
     if ((halfStart & (uint32_t)kTWrite) == 0)
@@ -1509,9 +1501,6 @@ struct RingCore  // IntegerDelay's buffer, index and mask
   MLD void unpark(const VoiceMem& m, int ringIdx)
   {
     if (!parked) return;
-#ifdef MLGPU_RING_X_NOUNPARK  // (shows that the tests reach this: tests/test_gpu_delays.py fails with it)
-    return;
-#endif
     storeHalf(m, ringIdx, w & ~(uint32_t)(kTChunk - 1), 0u, park);
     parked = false;
   }
@@ -1527,11 +1516,7 @@ struct RingCore  // IntegerDelay's buffer, index and mask
     {
       const uint32_t other = (uint32_t)mm * 16u + (lane >> 2);
       const uint32_t q = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(other * 4u), (int)want);
-#ifdef MLGPU_RING_X_NOLOAD
-      out[mm] = f32x4r{(float)q, 0.f, 0.f, 0.f};
-#else
       out[mm] = *((const f32x4r*)chunkOf(m, ringIdx, other, (q != kTNone ? q : spare) * (uint32_t)kTChunk) + j);
-#endif
     }
   }
   // ... and into the owners' read windows: chunk q goes to slot q & 1 (rows 16 + 16 (q & 1) ...)
@@ -1593,10 +1578,6 @@ struct RingCore  // IntegerDelay's buffer, index and mask
   // every 16 samples, all lanes together (w is the same in all of them and a multiple of 16, or this is the launch's first sample)
   MLD void boundaryT(const VoiceMem& m, int ringIdx, int32_t d)
   {
-#ifdef MLGPU_RING_X_NOBOUNDARY
-    primed = true;
-    return;
-#endif
     const uint32_t cmask = ((m.memMask + 1) >> 4) - 1u, wc = w >> 4;
     const uint32_t c = ((w - (uint32_t)d) & m.memMask) >> 4;
     const uint32_t age = (wc - c) & cmask;  // how many chunks behind the writer this lane reads (0: inside the write window)
@@ -1680,20 +1661,12 @@ struct RingCore  // IntegerDelay's buffer, index and mask
     const uint32_t r = (w - (uint32_t)d) & m.memMask;
     const bool inW = (r >> 3) == (w >> 3), inR = held(m, r);
     const uint32_t row = inW ? (r & (kTWrite - 1)) : (uint32_t)kTWrite + (r & (2 * kTChunk - 1));
-#ifdef MLGPU_RING_X_NOLDSREAD
-    float y = x + (float)row;
-#else
     float y = col[row * kTRowPad];
-#endif
-#ifndef MLGPU_RING_X_NOMISS
     if (__builtin_amdgcn_ballot_w64(!(inW || inR)) != 0)
     {
       // a sample no window holds (a delay of 8 to 47 samples: its chunk is too close behind the writer to be fetched a period
       // ahead; a delay time that jumped): from memory, complete there since the flush that ended its eight samples
       unpark(m, ringIdx);
-#ifdef MLGPU_RING_X_MISSPOISON
-      if (!(inW || inR)) y = 12345.f; else
-#endif
       if (!(inW || inR)) y = __hip_atomic_load(chunkOf(m, ringIdx, lane, r) + (r & (kTChunk - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       // The wait for that load belongs INSIDE this branch. Left to the join below, the compiler guards every later use of y with
       // s_waitcnt vmcnt(0) on the path that never loaded anything too - a memory round trip per sample behind the newest store,
@@ -1701,7 +1674,6 @@ struct RingCore  // IntegerDelay's buffer, index and mask
       // profiles/r05_ring_layouts.txt). A use of y here puts the wait here.
       asm volatile("" : "+v"(y));
     }
-#endif
     if ((w & (kTWrite - 1)) == kTWrite - 1)
     {
       flushT(m, ringIdx, w & ~(uint32_t)(kTWrite - 1));
@@ -2611,7 +2583,7 @@ MLD void step_locked_stream(Proc<MLGPU_PROC_SAW_GEN>& saw, Proc<MLGPU_PROC_PULSE
   outPulse = pulsev;
   if (__builtin_amdgcn_ballot_w64(nearUp || nearDown) == 0) return;
   const bool full = f.anyLaneOdd();
-  if (MLGPU_PULSE_SINGLE_BLEP && __builtin_amdgcn_ballot_w64(nearUp && nearDown) == 0)
+  if (__builtin_amdgcn_ballot_w64(nearUp && nearDown) == 0)
   {
     const float c = f.correction(nearDown ? down : p, nearDown ? loDown : loUp, full);
     outPulse = nearDown ? (pulsev - c) : (nearUp ? (pulsev + c) : pulsev);

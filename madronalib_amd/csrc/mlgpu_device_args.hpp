@@ -22,6 +22,10 @@ struct SignalView
 #define MLGPU_KFLAG_CASCADE_SHIFT 8
 #define MLGPU_KFLAG_CASCADE_MASK (7u << MLGPU_KFLAG_CASCADE_SHIFT)
 
+// a turn of the wavefronts of a SIMD at the priority levels (mldsp_math.hpp: take_turns_by_clock) lasts 2^13 ticks of 10 ns:
+// 82 us, the best of 2^7 .. 2^18 (profiles/r04_take_turns.txt). The chain kernels and the graph generator both use it.
+constexpr int kTurnClockShift = 13;
+
 struct ChainArgs
 {
   const float* coeffs;   // [NC][V]
@@ -82,7 +86,6 @@ struct GraphArgs
   size_t t0;  // DSPVectors processed since the last clear (a Downsample2xFunction region pairs vectors 2k, 2k + 1)
   uint32_t flags;  // MLGPU_KFLAG_*
   EventsDev events;
-  unsigned long long* waveClock;  // developer aid (MLGPU_GRAPH_WAVE_CLOCK): [wavefront][4] = start, end (100 MHz), HW_ID, XCC_ID; else nullptr
 };
 
 // row `row` of the state memory at the voice whose byte offset in a row is lane4: the row's address is wave-uniform (scalar

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (no GPU needed): generate a patch's fused graph kernel with hiprtc under the current MLGPU_GRAPH_* knobs and
+"""Developer tool (no GPU needed): generate a patch's fused graph kernel with hiprtc (the MLGPU_GRAPH_* test hooks apply) and
 print registers, scratch, code size and the instruction mix.   usage: tools/emit_stats.py cfg5|cfg5full|synth|synthfused [outprefix]"""
 import collections
 import os

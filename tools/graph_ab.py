@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Developer tool (GPU): A/B of generator knobs on BASELINE's graph workloads. Every variant starts from the same cleared state, runs
-the same launches and must produce the same bits (CRC of the last output and of every state word); prints ms per launch.
-    python tools/graph_ab.py "cfg5,cfg5full,synthpitch" "MLGPU_GRAPH_PREFETCH=0" "MLGPU_GRAPH_PREFETCH=1" ...
-A variant is a comma-separated list of NAME=VALUE pairs ("-" = no knob)."""
+"""Developer tool (GPU): A/B of the generator's test hooks on BASELINE's graph workloads. Every variant starts from the same cleared
+state, runs the same launches and must produce the same bits (CRC of the last output and of every state word); prints ms per launch.
+    python tools/graph_ab.py "cfg5,cfg5full,synthpitch" "MLGPU_GRAPH_OSC_TRIP=0" "MLGPU_GRAPH_OSC_TRIP=2" ...
+A variant is a comma-separated list of NAME=VALUE pairs ("-" = no hook). A kernel variant that no hook selects is measured by
+building it in a copy of the tree and running this tool once per library, with MLGPU_LIB pointing at each."""
 import os
 import sys
 import zlib

@@ -4,7 +4,7 @@
 // XCC_ID. Per launch the tool writes: the HIP-event duration, the device-side span, the gap to the previous launch and - per XCD - when
 // its first / last wavefront started and ended, its median wavefront life and the shader clock it held (d memtime / d realtime).
 // A host thread samples the board's power / sclk / mclk / temperature from sysfs beside it.
-//   build: see tools/spread_probe.sh        run: spread_probe --tag base [--V n] [--T n] [--nbuf n] [--launches n] [--per_step n]
+//   build: hipcc with csrc/Makefile's HIPFLAGS (no -fPIC), -lpthread        run: spread_probe --tag base [--V n] [--T n] [--nbuf n] [--launches n] [--per_step n]
 //          [--gap_us n] [--sync_each] [--out dir] [--dump 3]
 #include <hip/hip_runtime.h>
 #include <ctype.h>
