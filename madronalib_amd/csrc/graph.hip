@@ -8,27 +8,16 @@
 // Execution model: the graph is translated to HIP source that instantiates the hand-written device
 // building blocks (mldsp_procs.hpp / mldsp_ops.hpp) in topological order inside the voice-bank loop
 // (one lane per voice, state in registers, one 16-byte access per lane per quad) and compiled for
-// gfx950 with hiprtc. Every edge of the graph is a register; only graph inputs and outputs touch
-// HBM. Identical graphs share one compiled module per process. The same generator produces fused
-// kernels for processor chains that have no ahead-of-time instantiation (mlgpu_jit_chain).
-#include <hip/hiprtc.h>  // (types and enumerators only: the library is looked up at run time, see Hiprtc below)
-#include <dlfcn.h>
+// gfx950 with hiprtc (jit.hip). Every edge of the graph is a register; only graph inputs and outputs
+// touch HBM. Identical graphs share one compiled module per process.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <fcntl.h>
-#include <sys/file.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <chrono>
 
 #include <algorithm>
 #include <atomic>
 #include <thread>
-#include <functional>
-#include <map>
 #include <mutex>
 #include <new>
 #include <set>
@@ -36,437 +25,12 @@
 
 #include "mlgpu_internal.hpp"
 
-extern const char mlgpu_device_source_hash_str[];
 struct mlgpu_graph;
 static std::mutex g_boundMutex;
 static std::set<mlgpu_graph*> g_boundGraphs;  // graphs with an events object bound (mlgpu_graph_bind_events)
-extern const int mlgpu_embedded_count;
-extern const char* const mlgpu_embedded_names[];
-extern const char* const mlgpu_embedded_sources[];
 
 namespace
 {
-struct CompiledModule
-{
-  hipModule_t module{nullptr};
-  std::map<std::string, hipFunction_t> fns;
-};
-
-std::mutex g_cacheMutex;
-std::map<std::string, CompiledModule> g_cache;  // key: device id + source
-
-// The options every run-time kernel is compiled with (part of the disk cache's key): the ahead-of-time build's own
-// (csrc/Makefile) apart from its scheduling strategy, max-ilp (profiles/archive/r03_jit_maxilp.txt: what it does to config 5).
-const std::vector<std::string>& jitOptions()
-{
-  static const std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"};
-  return opts;
-}
-
-// hiprtc, looked up at RUN TIME (round 6): libmlgpu.so does not link it, so an installation without the compiler still loads and
-// runs every ahead-of-time kernel, and every generated one whose code it is given (the disk cache, mlgpu_jit_cache_import). A
-// graph or chain that needs a compile there fails with MLGPU_ERR_UNSUPPORTED and says why. MLGPU_HIPRTC=off: behave as if the
-// library were absent (what tests/test_abi.py uses); MLGPU_HIPRTC=<path>: that library.
-struct Hiprtc
-{
-  void* lib{nullptr};
-  decltype(&::hiprtcCreateProgram) createProgram{nullptr};
-  decltype(&::hiprtcCompileProgram) compileProgram{nullptr};
-  decltype(&::hiprtcGetProgramLogSize) getProgramLogSize{nullptr};
-  decltype(&::hiprtcGetProgramLog) getProgramLog{nullptr};
-  decltype(&::hiprtcGetCodeSize) getCodeSize{nullptr};
-  decltype(&::hiprtcGetCode) getCode{nullptr};
-  decltype(&::hiprtcDestroyProgram) destroyProgram{nullptr};
-  decltype(&::hiprtcGetErrorString) getErrorString{nullptr};
-  decltype(&::hiprtcVersion) version{nullptr};
-  std::string why;
-  Hiprtc()
-  {
-    const char* knob = getenv("MLGPU_HIPRTC");
-    for (const char* name : {knob && strcmp(knob, "off") ? knob : "libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so"})
-    {
-      lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (lib) break;
-    }
-    if (!lib)
-    {
-      why = std::string("libhiprtc.so cannot be loaded (") + (dlerror() ? dlerror() : "not found") + ")";
-      return;
-    }
-#define MLGPU_RTC_SYM(member, symbol) member = (decltype(member))dlsym(lib, #symbol)
-    MLGPU_RTC_SYM(createProgram, hiprtcCreateProgram);
-    MLGPU_RTC_SYM(compileProgram, hiprtcCompileProgram);
-    MLGPU_RTC_SYM(getProgramLogSize, hiprtcGetProgramLogSize);
-    MLGPU_RTC_SYM(getProgramLog, hiprtcGetProgramLog);
-    MLGPU_RTC_SYM(getCodeSize, hiprtcGetCodeSize);
-    MLGPU_RTC_SYM(getCode, hiprtcGetCode);
-    MLGPU_RTC_SYM(destroyProgram, hiprtcDestroyProgram);
-    MLGPU_RTC_SYM(getErrorString, hiprtcGetErrorString);
-    MLGPU_RTC_SYM(version, hiprtcVersion);
-#undef MLGPU_RTC_SYM
-    if (!createProgram || !compileProgram || !getProgramLogSize || !getProgramLog || !getCodeSize || !getCode || !destroyProgram || !getErrorString)
-    {
-      why = "libhiprtc.so lacks an entry point this library uses";
-      dlclose(lib);
-      lib = nullptr;
-    }
-  }
-};
-// nullptr (and `why`) where the compiler is not there - or a test says so
-const Hiprtc* hiprtc(std::string* why = nullptr)
-{
-  static const Hiprtc rtc;
-  const char* knob = getenv("MLGPU_HIPRTC");
-  if (knob && !strcmp(knob, "off"))
-  {
-    if (why) *why = "run-time compilation is switched off (MLGPU_HIPRTC=off)";
-    return nullptr;
-  }
-  if (!rtc.lib)
-  {
-    if (why) *why = rtc.why;
-    return nullptr;
-  }
-  return &rtc;
-}
-
-// compile `source` for gfx950 and load it on the current device; returns nullptr and fills `log` on failure
-bool compileToCode(const std::string& source, std::vector<char>& code, std::string& log)
-{
-  hiprtcProgram prog;
-  code.clear();
-  std::string why;
-  const Hiprtc* rtc = hiprtc(&why);
-  if (!rtc)
-  {
-    log = "this kernel is not in the memory or disk cache and " + why + ": compile it where hiprtc is installed and bring its code along (mlgpu_jit_cache_export / _import)";
-    return false;
-  }
-  if (rtc->createProgram(&prog, source.c_str(), "mlgpu_jit.hip", mlgpu_embedded_count, (const char**)mlgpu_embedded_sources,
-                          (const char**)mlgpu_embedded_names) != HIPRTC_SUCCESS)
-  {
-    log = "hiprtcCreateProgram failed";
-    return false;
-  }
-  std::vector<const char*> opts;
-  for (const std::string& o : jitOptions()) opts.push_back(o.c_str());
-  const hiprtcResult r = rtc->compileProgram(prog, (int)opts.size(), opts.data());
-  size_t logSize = 0;
-  rtc->getProgramLogSize(prog, &logSize);
-  if (logSize > 1)
-  {
-    log.resize(logSize);
-    rtc->getProgramLog(prog, &log[0]);
-  }
-  size_t codeSize = 0;
-  if (r == HIPRTC_SUCCESS) rtc->getCodeSize(prog, &codeSize);
-  if (codeSize)
-  {
-    code.resize(codeSize);
-    rtc->getCode(prog, code.data());
-  }
-  rtc->destroyProgram(&prog);
-  if (r != HIPRTC_SUCCESS && log.empty()) log = rtc->getErrorString(r);
-  return r == HIPRTC_SUCCESS && codeSize > 0;
-}
-
-// hiprtc results by source. Two levels: in memory (identical graphs and the size probe of graph_compile compile once per
-// process) and on disk (a process that starts again - a plug-in host reloading, the next benchmark run - finds the code
-// object of every graph it has built before and skips hiprtc, which takes 0.3-2 s per kernel). The disk key is a hash of
-// everything that decides the code object: the generated source, the compile options, every embedded device header and
-// the hiprtc version. Files are written to a temporary name and renamed, so concurrent processes (one rank per GPU) can
-// share the directory. MLGPU_CACHE_DIR names it (default $XDG_CACHE_HOME/mlgpu or ~/.cache/mlgpu); MLGPU_CACHE_DIR=off
-// disables the disk level.
-std::mutex g_codeMutex;
-std::map<std::string, std::vector<char>> g_codeCache;
-struct JitStats
-{
-  uint64_t compiles{0}, diskHits{0}, memoryHits{0}, diskWrites{0};
-  double compileSeconds{0}, diskLoadSeconds{0};
-} g_jitStats;
-
-
-uint64_t fnv1a(uint64_t h, const void* data, size_t n)
-{
-  const unsigned char* p = (const unsigned char*)data;
-  for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
-  return h;
-}
-
-// The cache directory, or "" when the disk level is off or the directory cannot be trusted: code objects are loaded into
-// the GPU as they are, so the directory must belong to this user and be writable by nobody else (a directory another user
-// can write to would let them choose the code this process runs).
-std::string cacheDir()
-{
-  const char* d = getenv("MLGPU_CACHE_DIR");
-  if (d && !strcmp(d, "off")) return "";
-  std::string dir;
-  if (d && *d)
-    dir = d;
-  else if (const char* x = getenv("XDG_CACHE_HOME"))
-    dir = std::string(x) + "/mlgpu";
-  else if (const char* h = getenv("HOME"))
-    dir = std::string(h) + "/.cache/mlgpu";
-  else
-    return "";
-  // mkdir -p; what we create is ours alone
-  for (size_t i = 1; i <= dir.size(); ++i)
-    if (i == dir.size() || dir[i] == '/') mkdir(dir.substr(0, i).c_str(), 0700);
-  struct stat st;
-  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return "";
-  if (st.st_uid != geteuid() || (st.st_mode & (S_IWGRP | S_IWOTH)))
-  {
-    fprintf(stderr, "mlgpu: kernel cache directory %s is not owned by this user or is writable by others: disk cache off\n", dir.c_str());
-    return "";
-  }
-  return dir;
-}
-
-// Everything that decides a code object besides the generated source: compile options, the fingerprint of the device
-// headers of this build (embed.py: the headers hiprtc is given are part of it), the HIP runtime / hiprtc versions with
-// their patch level, and the library's ABI version.
-const std::string& cacheContext()
-{
-  static const std::string ctx = [] {
-    std::string c = "mlgpu-kernel-cache 2\n";
-    for (const std::string& o : jitOptions()) c += o + " ";
-    c += "\ndevice-sources " + std::string(mlgpu_device_source_hash_str);
-    int major = 0, minor = 0, runtime = 0, driver = 0;
-    if (const Hiprtc* rtc = hiprtc())
-      if (rtc->version) rtc->version(&major, &minor);  // (0.0 without the compiler: such a process only ever READS code it is given)
-    if (hipRuntimeGetVersion(&runtime) != hipSuccess) runtime = -1;
-    if (hipDriverGetVersion(&driver) != hipSuccess) driver = -1;
-    c += "\nhiprtc " + std::to_string(major) + "." + std::to_string(minor) + " runtime " + std::to_string(runtime) + " driver " + std::to_string(driver);
-#ifdef HIP_VERSION_GITHASH
-    c += std::string(" built-with ") + HIP_VERSION_GITHASH;
-#endif
-    c += "\nabi " + std::to_string(MLGPU_ABI_VERSION) + "\n";
-    return c;
-  }();
-  return ctx;
-}
-
-std::string cacheFile(const std::string& source)
-{
-  // (looked up again whenever MLGPU_CACHE_DIR changes: a host - or a test - may switch the disk level off after the first kernel)
-  static std::mutex m;
-  static std::string dirFor, dirValue;
-  static bool dirKnown = false;
-  std::string dir;
-  {
-    std::lock_guard<std::mutex> lock(m);
-    const char* envNow = getenv("MLGPU_CACHE_DIR");
-    const std::string key = envNow ? envNow : "";
-    if (!dirKnown || key != dirFor)
-    {
-      dirValue = cacheDir();
-      dirFor = key;
-      dirKnown = true;
-    }
-    dir = dirValue;
-  }
-  if (dir.empty()) return "";
-  const std::string& ctx = cacheContext();
-  uint64_t h = 0xcbf29ce484222325ull;
-  h = fnv1a(h, ctx.data(), ctx.size());
-  h = fnv1a(h, source.data(), source.size());
-  char name[64];
-  snprintf(name, sizeof(name), "/%016llx-%zu.co", (unsigned long long)h, source.size());
-  return dir + name;
-}
-
-// A cache file = header line "MLGPUCO2 <context bytes> <source bytes> <code bytes>\n", the context, the generated source,
-// the code object. The file name is only a 64-bit hash: a file is used when its context and its source are byte for byte
-// the ones asked for, so neither a hash collision nor another compiler / library build can hand back a different kernel.
-bool readCacheFile(const std::string& path, const std::string& source, std::vector<char>& code)
-{
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  bool ok = false;
-  char magic[16] = {0};
-  unsigned long long nCtx = 0, nSrc = 0, nCode = 0;
-  const std::string& ctx = cacheContext();
-  if (fscanf(f, "%15s %llu %llu %llu", magic, &nCtx, &nSrc, &nCode) == 4 && fgetc(f) == '\n' && !strcmp(magic, "MLGPUCO2") &&
-      nCtx == ctx.size() && nSrc == source.size() && nCode > 64 && nCode < (1ull << 30))
-  {
-    std::string gotCtx(nCtx, '\0'), gotSrc(nSrc, '\0');
-    code.resize((size_t)nCode);
-    ok = fread(&gotCtx[0], 1, nCtx, f) == nCtx && fread(&gotSrc[0], 1, nSrc, f) == nSrc && fread(code.data(), 1, (size_t)nCode, f) == (size_t)nCode &&
-         fgetc(f) == EOF && gotCtx == ctx && gotSrc == source && !memcmp(code.data(), "\177ELF", 4);
-  }
-  fclose(f);
-  if (!ok) code.clear();
-  return ok;
-}
-
-bool writeCacheFile(const std::string& path, const std::string& source, const std::vector<char>& code)
-{
-  // a temporary file of our own in the same directory (mkstemp: unique whatever shares the directory - other processes,
-  // containers with the same pids, hosts on a network file system), then an atomic rename
-  std::string tmp = path + ".XXXXXX";
-  const int fd = mkstemp(&tmp[0]);
-  if (fd < 0) return false;
-  FILE* f = fdopen(fd, "wb");
-  if (!f)
-  {
-    close(fd);
-    remove(tmp.c_str());
-    return false;
-  }
-  const std::string& ctx = cacheContext();
-  bool ok = fprintf(f, "MLGPUCO2 %zu %zu %zu\n", ctx.size(), source.size(), code.size()) > 0;
-  ok = ok && fwrite(ctx.data(), 1, ctx.size(), f) == ctx.size() && fwrite(source.data(), 1, source.size(), f) == source.size() &&
-       fwrite(code.data(), 1, code.size(), f) == code.size();
-  ok = (fclose(f) == 0) && ok;
-  if (ok && rename(tmp.c_str(), path.c_str()) == 0) return true;
-  remove(tmp.c_str());
-  return false;
-}
-
-bool compileToCode(const std::string& source, std::vector<char>& code, std::string& log);
-
-bool getCode(const std::string& source, std::vector<char>& code, std::string& log)
-{
-  {
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    auto it = g_codeCache.find(source);
-    if (it != g_codeCache.end())
-    {
-      code = it->second;
-      ++g_jitStats.memoryHits;
-      return true;
-    }
-  }
-  // One build at a time: the host threads of a DeviceGroup ask for the same kernels at the same moment, and the second one
-  // should find the first one's result instead of running hiprtc again beside it.
-  static std::mutex buildMutex;
-  std::lock_guard<std::mutex> building(buildMutex);
-  {
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    auto it = g_codeCache.find(source);
-    if (it != g_codeCache.end())
-    {
-      code = it->second;
-      ++g_jitStats.memoryHits;
-      return true;
-    }
-  }
-  const std::string path = cacheFile(source);
-  bool fromDisk = false;
-  // One build per MACHINE too: the ranks of a multi-GPU job start together and all ask for the same kernel. Whoever gets
-  // the advisory lock on <entry>.lock first compiles and writes the entry; the others block in flock(), then find it. The
-  // kernel drops the lock when its holder dies, so a killed rank cannot strand the rest.
-  struct FileLock
-  {
-    int fd{-1};
-    explicit FileLock(const std::string& p)
-    {
-      if (p.empty()) return;
-      fd = open((p + ".lock").c_str(), O_CREAT | O_RDWR | O_CLOEXEC, 0600);
-      if (fd >= 0 && flock(fd, LOCK_EX) != 0)
-      {
-        close(fd);
-        fd = -1;
-      }
-    }
-    ~FileLock()
-    {
-      if (fd >= 0)
-      {
-        flock(fd, LOCK_UN);
-        close(fd);
-      }
-    }
-  } entryLock(path);
-  if (!path.empty())
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    fromDisk = readCacheFile(path, source, code);  // anything else under that name (a truncated write, another build's file) is ignored and rebuilt
-    if (fromDisk)
-    {
-      std::lock_guard<std::mutex> lock(g_codeMutex);
-      ++g_jitStats.diskHits;
-      g_jitStats.diskLoadSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-  }
-  if (!fromDisk)
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!compileToCode(source, code, log)) return false;
-    {
-      std::lock_guard<std::mutex> lock(g_codeMutex);
-      ++g_jitStats.compiles;
-      g_jitStats.compileSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if (!path.empty() && writeCacheFile(path, source, code))
-    {
-      std::lock_guard<std::mutex> lock(g_codeMutex);
-      ++g_jitStats.diskWrites;
-    }
-  }
-  std::lock_guard<std::mutex> lock(g_codeMutex);
-  g_codeCache[source] = code;
-  return true;
-}
-
-CompiledModule* compileAndLoad(int device, const std::string& source, std::string& log)
-{
-  const std::string key = std::to_string(device) + "\n" + source;
-  {
-    std::lock_guard<std::mutex> lock(g_cacheMutex);
-    auto it = g_cache.find(key);
-    if (it != g_cache.end()) return &it->second;
-  }
-  // hiprtc (seconds, on a compile job's worker thread) runs OUTSIDE the module cache's lock: a thread that only looks a loaded module
-  // up - an autotune trial inside graph_process, a bank's chain, another graph - never waits for someone else's compile
-  std::vector<char> code;
-  if (!getCode(source, code, log)) return nullptr;
-
-  std::lock_guard<std::mutex> lock(g_cacheMutex);
-  auto it = g_cache.find(key);  // (another thread may have loaded the same source meanwhile)
-  if (it != g_cache.end()) return &it->second;
-  CompiledModule cm;
-  const hipError_t e = hipModuleLoadData(&cm.module, code.data());
-  if (e != hipSuccess)
-  {
-    log = std::string("hipModuleLoadData: ") + hipGetErrorString(e);
-    return nullptr;
-  }
-  return &(g_cache[key] = cm);
-}
-
-// compile only (no device needed): used by mlgpu_jit_selftest
-bool compileOnly(const std::string& source, std::string& log)
-{
-  std::vector<char> code;
-  return compileToCode(source, code, log);
-}
-
-hipFunction_t getFunction(CompiledModule* cm, const char* name, std::string& log)
-{
-  auto it = cm->fns.find(name);
-  if (it != cm->fns.end()) return it->second;
-  hipFunction_t f = nullptr;
-  const hipError_t e = hipModuleGetFunction(&f, cm->module, name);
-  if (e != hipSuccess)
-  {
-    log = std::string("hipModuleGetFunction(") + name + "): " + hipGetErrorString(e);
-    return nullptr;
-  }
-  cm->fns[name] = f;
-  return f;
-}
-
-template <class ARGS>
-hipError_t launchJit(hipFunction_t fn, const ARGS& args, size_t V, hipStream_t stream)
-{
-  ARGS copy = args;
-  size_t size = sizeof(ARGS);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  const unsigned blocks = (unsigned)((V + 255) / 256);
-  return hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, stream, nullptr, config);
-}
-
 enum NodeType
 {
   NODE_INPUT = 0,
@@ -496,13 +60,16 @@ struct Node
   int kind;  // proc kind or op
   std::vector<int> in;
   std::string name;
+  Node(int type_ = 0, int kind_ = 0, const char* name_ = nullptr) : type(type_), kind(kind_), name(name_ ? name_ : "") {}
   float value{0.f};
   int slot{0};            // input index / param index / control index; demultiplex: output index
   int nOut{0};            // demultiplex: number of outputs
   size_t ringLen{0};      // delay nodes: floats per ring (power of two), 0 = not set
   int ringSlot{0};        // delay nodes: index of this node's first ring among all rings of the graph (LDS windows)
-  int earlySlot{-1};      // ring layout 0 with early reads: this node's first 256-byte landing slot in the wavefront's LDS
-  int earlyPending{0};    //   and the loads the kernel issues right after this node's (RingCore::earlyWait), set by the generator
+  int earlySlot{-1};      // ring layout 0 with early reads: this node's first 256-byte landing slot in the wavefront's LDS,
+  bool earlyTop{false};   //   its read issued at the top of the sample with the batch of such reads (RingCore::readEarly),
+  int earlyPending{0};    //   and the loads the kernel issues there right after this node's (RingCore::earlyWait)
+  bool earlyHoisted{false};  // a node such a read's delay time is made of: made at the top of the sample, before the reads
   size_t memOff{0};       // delay nodes: first ring at d_mem + memOff * V
   int fbSource{-1};       // feedback nodes: the node whose value is stored for the next vector
   int rate{RATE_AUDIO};
@@ -514,6 +81,22 @@ struct Node
 };
 
 enum { ROLE_NONE = 0, ROLE_REGION_IN = 1, ROLE_REGION_OUT = 2 };
+
+// Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them at compile)
+enum class RingLayout
+{
+  ROWS,        // layout 0: ring rows of the bank's voices
+  WINDOWS,     // layout 1: rings as [block][chunk][lane][8] behind LDS windows
+  TRANSPOSED,  // layout 2: [block][chunk][lane][16], every global access a 64-byte piece made by four lanes, on a wave-uniform clock
+  SECTORS      // layout 4: layout 1's memory, no LDS, trips of 8 samples with every ring's loads in the trip's prologue
+};
+
+// A graph kernel's form besides the graph: voices per lane, quads per trip of the sample loop, and the wavefronts per SIMD its
+// register budget must allow (0: the compiler's choice; generateBudgeted)
+struct KernelForm
+{
+  int voicesPerLane{1}, quadsPerTrip{1}, minWaves{0};
+};
 
 // Upsample2xFunction / Downsample2xFunction (MLDSPFunctional.h:114-213) with fn written out as nodes
 struct Region
@@ -567,15 +150,13 @@ struct mlgpu_graph
   float* d_mem{nullptr};
   std::vector<char> emitted;     // mlgpu_graph_emit: the gfx950 code object
   size_t memFloatsPerVoice{0};
-  bool windowedRings{false};     // rings as [block][chunk][lane][8] behind LDS windows (mlgpu_graph_set_delay_layout)
-  bool transposedIfPossible{false};  // graph_set_delay_layout(3)
+  int delayLayout{0};            // as mlgpu_graph_set_delay_layout took it (3: the best of 2 / 4 / 1 for the graph)
+  RingLayout rings{RingLayout::ROWS};  // the layout the kernel uses: layout 3 laid out as 1 until layoutAndGenerate resolves it
   bool rowAddr32{false};         // layout 0: ring rows behind 32-bit offsets from a wave-uniform base where a ring allows it (VoiceMem::ringPtr); set at compile
   bool earlyRows{false};         // layout 0: the ring reads of the outer graph's delay nodes issued ahead by LDS-DMA (RingCore::readEarly); set at compile
   int earlySlots{0};             // their landing slots per wavefront
-  bool sectorRings{false};       // layout 4: layout 1's memory, no LDS, trips of 8 samples with every ring's loads in the trip's prologue (implies windowedRings)
-  bool transposedRings{false};   // layout 2: [block][chunk][lane][16], every global access a 64-byte piece made by four lanes, on a wave-uniform clock (implies windowedRings)
   int totalRings{0};
-  size_t memVoices() const { return windowedRings ? ((V + 255) & ~(size_t)255) : V; }  // voices the ring memory is laid out for
+  size_t memVoices() const { return rings != RingLayout::ROWS ? ((V + 255) & ~(size_t)255) : V; }  // voices the ring memory is laid out for
   std::vector<Region> regions;
   int openRegion{-1};            // between graph_begin_region and graph_end_region
   size_t vectorCount{0};         // DSPVectors processed since the last clear (GraphArgs::t0)
@@ -599,7 +180,6 @@ struct mlgpu_graph
   CompileJob* job{nullptr};
   bool aotDone{false};           // an engine-less graph whose ahead-of-time compile has been collected (mlgpu_graph_compile_poll keeps answering MLGPU_OK)
   int eventOffset{-1};           // frame offset of the block being processed (mlgpu_graph_process_events), -1: none pending
-  int minWaves{0};               // wavefronts per SIMD the kernel's register budget must allow (0: the compiler's choice), generateBudgeted
   int minWavesHook{-1};          // test hook MLGPU_GRAPH_MIN_WAVES (layoutAndGenerate): generateBudgeted's bound fixed; -1: not set
   bool rowAddr64{false};         // test hook MLGPU_GRAPH_ROW_ADDR32=0 (layoutAndGenerate): state and ring rows by 64-bit addresses
   // Online tuning (mlgpu_graph_set_autotune): every variant (voices per lane x quads per trip) computes the same bits from
@@ -744,6 +324,57 @@ static int streamLockSawOf(const mlgpu_graph* g, size_t i)  // the saw of the pa
 // ring layout 0, a delay node of the outer graph: its ring read is issued ahead of its place in the graph (RingCore::readEarly)
 static bool earlyRingReads(const mlgpu_graph* g, const Node& n) { return g->earlyRows && n.earlySlot >= 0; }
 
+// The early reads' plan, made with the landing slots (layoutAndGenerate): the delay nodes whose reads are issued at the top of the
+// sample (earlyTop), the nodes their delay times are made of (earlyHoisted) and what each read leaves in flight (earlyPending).
+// The nodes a delay time is computed from go to the top of the sample with the reads behind them, where nothing of this sample
+// has been stored yet: plain nodes only (operators, inputs, one-vector feedback values, processors without rings - each keeps its
+// own state, so their order among independent nodes is free), and only those whose inputs are such nodes themselves.
+static void planEarlyReads(mlgpu_graph* g)
+{
+  std::vector<char> movable(g->nodes.size(), 0), wanted(g->nodes.size(), 0);
+  for (Node& n : g->nodes) n.earlyTop = n.earlyHoisted = false, n.earlyPending = 0;
+  if (!g->earlyRows) return;
+  for (size_t j = 0; j < g->nodes.size(); ++j)
+  {
+    const Node& m = g->nodes[j];
+    if (m.rate != RATE_AUDIO)
+    {
+      movable[j] = 1;  // (a value per voice or per DSPVector: there before the sample loop)
+      continue;
+    }
+    bool ok = m.region < 0 && m.role == ROLE_NONE && (m.type == NODE_OP || m.type == NODE_INPUT || m.type == NODE_FEEDBACK || m.type == NODE_VOP || (m.type == NODE_PROC && !mlgpu_proc_rings(m.kind) && streamLockSawOf(g, j) < 0));
+    if (m.type != NODE_FEEDBACK)
+      for (int in : m.in) ok = ok && movable[(size_t)in];
+    movable[j] = ok;
+  }
+  for (Node& m : g->nodes)
+  {
+    if (!earlyRingReads(g, m)) continue;
+    bool all = true;
+    for (size_t a = 1; a < m.in.size(); ++a) all = all && movable[(size_t)m.in[a]];
+    if (!all) continue;
+    for (size_t a = 1; a < m.in.size(); ++a) wanted[(size_t)m.in[a]] = 1;
+    m.earlyTop = true;
+  }
+  // the audio-rate nodes the batch's delay times need, and theirs in turn (a node's inputs come before it)
+  for (size_t j = g->nodes.size(); j-- > 0;)
+  {
+    Node& m = g->nodes[j];
+    if (!wanted[j] || m.rate != RATE_AUDIO) continue;
+    m.earlyHoisted = true;
+    if (m.type != NODE_FEEDBACK)
+      for (int in : m.in) wanted[(size_t)in] = 1;
+  }
+  // what is still in flight behind a node's loads when they have landed: at least the loads of the batch issued after them
+  int after = 0;
+  for (size_t b = g->nodes.size(); b-- > 0;)
+    if (g->nodes[b].earlyTop)
+    {
+      g->nodes[b].earlyPending = after;
+      after += g->nodes[b].kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? 2 : 1;
+    }
+}
+
 std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& ph = "", const std::string& idx = "q * 4 + k")
 {
   const Node& n = g->nodes[i];
@@ -751,6 +382,11 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
   const std::string L = "_" + std::to_string(l);
   // an input that lives in an enclosing region (or outside) carries only the phase letters of ITS regions
   auto arg = [&](size_t j) { return "n" + std::to_string(n.in[j]) + ph.substr(0, (size_t)upDepth(g, g->nodes[n.in[j]].region)) + L; };
+  auto argsFrom = [&](size_t j0) {  // ", " before each of the inputs from j0 on
+    std::string t;
+    for (size_t j = j0; j < n.in.size(); ++j) t += ", " + arg(j);
+    return t;
+  };
   switch (n.type)
   {
     case NODE_INPUT: s << "xin" << n.slot << L << "[k]"; break;
@@ -772,14 +408,9 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
         s << "p" << i << L << (n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? ".post_i<" : ".post<") << n.earlyPending << ">("
           << (n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? idx + ", " : std::string()) << arg(0) << ")";
       else if (n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY)
-        s << "p" << i << L << ".next_i(" << idx << ", " << arg(0) << ", " << arg(1) << ((g->sectorRings && n.region < 0) ? ", qq * 4 + k" : "") << ")";
-      else if (g->sectorRings && n.region < 0 && mlgpu_proc_rings(n.kind))
-      {
-        // ring layout 4: the sample's place in its trip of 8 (a constant once qq and k are unrolled)
-        s << "p" << i << L << ".next_k(qq * 4 + k, " << arg(0);
-        for (size_t j = 1; j < n.in.size(); ++j) s << ", " << arg(j);
-        s << ")";
-      }
+        s << "p" << i << L << ".next_i(" << idx << ", " << arg(0) << ", " << arg(1) << ((g->rings == RingLayout::SECTORS && n.region < 0) ? ", qq * 4 + k" : "") << ")";
+      else if (g->rings == RingLayout::SECTORS && n.region < 0 && mlgpu_proc_rings(n.kind))  // ring layout 4: the sample's place in its trip of 8
+        s << "p" << i << L << ".next_k(qq * 4 + k, " << arg(0) << argsFrom(1) << ")";     // (a constant once qq and k are unrolled)
       else if (isOscTrip(g, n))
         s << "osc" << i << L << "[qq * 4 + k]";  // made for the whole trip before the sample loop
       else if ((n.kind == MLGPU_PROC_SAW_GEN || n.kind == MLGPU_PROC_PULSE_GEN) && g->nodes[n.in[0]].rate == RATE_VOICE)
@@ -800,11 +431,7 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
       else if (n.kind == MLGPU_PROC_PULSE_GEN && n.in.size() == 2)
         s << "p" << i << L << ".next2(" << arg(0) << ", " << arg(1) << ")";
       else
-      {
-        s << "p" << i << L << ".next(" << (n.in.empty() ? std::string("0.f") : arg(0));
-        for (size_t j = 1; j < n.in.size(); ++j) s << ", " << arg(j);
-        s << ")";
-      }
+        s << "p" << i << L << ".next(" << (n.in.empty() ? std::string("0.f") : arg(0)) << argsFrom(1) << ")";
       break;
     case NODE_OP:
       if (n.kind == MLGPU_OP_CLAMP && clampHasConstBounds(g, n))
@@ -812,9 +439,7 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
         s << "clamp_const_bounds(" << arg(0) << ", " << arg(1) << ", " << arg(2) << ")";  // two instructions (mldsp_math.hpp)
         break;
       }
-      s << "apply_f<" << n.kind << ">(" << arg(0);
-      for (size_t j = 1; j < n.in.size(); ++j) s << ", " << arg(j);
-      s << ")";
+      s << "apply_f<" << n.kind << ">(" << arg(0) << argsFrom(1) << ")";
       break;
     case NODE_FEEDBACK:
       if (n.region < 0)
@@ -824,11 +449,7 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
       break;
     case NODE_ROUTE:
       if (n.kind == MLGPU_ROUTE_MULTIPLEX || n.kind == MLGPU_ROUTE_MULTIPLEX_LINEAR)
-      {
-        s << (n.kind == MLGPU_ROUTE_MULTIPLEX ? "route_multiplex_v(" : "route_multiplex_linear_v(") << arg(0);
-        for (size_t j = 1; j < n.in.size(); ++j) s << ", " << arg(j);
-        s << ")";
-      }
+        s << (n.kind == MLGPU_ROUTE_MULTIPLEX ? "route_multiplex_v(" : "route_multiplex_linear_v(") << arg(0) << argsFrom(1) << ")";
       else
         s << (n.kind == MLGPU_ROUTE_DEMULTIPLEX ? "route_demultiplex(" : "route_demultiplex_linear(") << arg(0) << ", " << arg(1) << ", "
           << n.slot << ", " << n.nOut << ")";
@@ -839,9 +460,7 @@ std::string nodeExpr(const mlgpu_graph* g, size_t i, int l, const std::string& p
         s << "u2f(cv" << i << "[" << idx << "])";  // same index for every lane: a scalar load from constant memory
         break;
       }
-      s << "vop<" << n.kind << ">(" << idx;
-      for (size_t j = 0; j < n.in.size(); ++j) s << ", " << arg(j);
-      s << ")";
+      s << "vop<" << n.kind << ">(" << idx << argsFrom(0) << ")";
       break;
   }
   return s.str();
@@ -867,604 +486,568 @@ int graphVoicesPerLane(const mlgpu_graph* g)
   return 1;
 }
 
-std::string generateGraphSource(mlgpu_graph* g, int forceVl = 0)
+// The source of a graph's kernel, a pure function of the graph and the form: the facts every section needs are worked out once,
+// and each section of the kernel is written by a member, in the order the kernel has them.
+struct GraphEmitter
 {
-  const int VL = forceVl > 0 ? forceVl : graphVoicesPerLane(g);
-  g->compiledVoicesPerLane = VL;
+  const mlgpu_graph& g;
+  const KernelForm& form;
+  const int VL;
   std::ostringstream s;
-  auto sfx = [](int l) { return "_" + std::to_string(l); };
-  s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane)\n"
-    << (g->transposedRings ? "#define MLGPU_RING_WINDOWS 2\n" : (g->sectorRings ? "#define MLGPU_RING_WINDOWS 3\n" : (g->windowedRings ? "#define MLGPU_RING_WINDOWS 1\n" : ""))) << (g->strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\n#include \"mldsp_ops.hpp\"\n" << (g->hasEventRows ? "#include \"mldsp_events.hpp\"\n" : "") << "using namespace mldev;\n";
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_VOP && g->nodes[i].kind == MLGPU_VOP_TABLE)
-    {
-      s << "__constant__ unsigned cv" << i << "[64] = {";
-      for (int j = 0; j < 64; ++j) s << (j ? ", " : "") << "0x" << std::hex << g->nodes[i].table[j] << std::dec << "u";
-      s << "};\n";
-    }
-  // windowed rings: the latency of a sector refill is hidden by other waves only, so keep at least two per SIMD
-  s << "extern \"C\" __global__ __launch_bounds__(256" << ((g->transposedRings && g->totalRings == 1) ? ", 4" : (g->sectorRings && g->totalRings) ? ", 1" : (g->windowedRings && g->totalRings) ? ", 2" : (g->minWaves ? ", " + std::to_string(g->minWaves) : std::string())) << ") void mlgpu_graph_kernel(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
-  if (g->hasImpulse)
-  {
-    s << "  __shared__ float ldsTable[32];\n  if (threadIdx.x < 17) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];\n  __syncthreads();\n";
-    s << "  const KernelTables tables{ldsTable};\n";
-  }
-  else
-  {
-    s << "  const KernelTables tables{nullptr};\n";
-  }
-  if (g->transposedRings && g->totalRings) s << "  __shared__ float ldsRings[" << (size_t)g->totalRings * 4 << " * kTStrip];  // [ring][wavefront][40 rows][64]: write window + two read chunks\n";
+  bool windowed, partialWaves, stateAddr32, PF, oscTrips, ringTrips;
+  std::string ringLane;
   // ring layout 4, per wavefront: every delay node's held sectors (512 floats per ring) and history rows (1024 floats per node)
-  std::vector<size_t> sectorLdsOff(g->nodes.size(), 0);
-  size_t sectorLdsPerWave = 0;
-  if (g->sectorRings)
-    for (size_t i = 0; i < g->nodes.size(); ++i)
-      if (g->nodes[i].type == NODE_PROC && g->nodes[i].ringLen)
-      {
-        sectorLdsOff[i] = sectorLdsPerWave;
-        sectorLdsPerWave += (size_t)mlgpu_proc_rings(g->nodes[i].kind) * 512 + 1024;
-      }
-  if (g->sectorRings && g->totalRings) s << "  __shared__ __attribute__((aligned(16))) float ldsRings[" << 4 * sectorLdsPerWave << "];  // [wavefront][node: held sectors, history rows]\n";
-  else if (!g->transposedRings && g->windowedRings && g->totalRings) s << "  __shared__ float ldsRings[" << (size_t)g->totalRings * 8 * 256 << "];  // write windows, [ring][8][256 lanes]\n";
-  if (g->earlyRows)
-    s << "  __shared__ float ldsEarly[" << 4 * g->earlySlots * 64 << "];  // [wavefront][ring read][64 lanes]: where the early ring reads land\n"
-      << "  float* const ldsEarlyWave = ldsEarly + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * " << g->earlySlots * 64 << ";\n";
+  std::vector<size_t> sectorLdsOff;
+  size_t sectorLdsPerWave{0};
+  GraphEmitter(const mlgpu_graph& graph, const KernelForm& f) : g(graph), form(f), VL(f.voicesPerLane), sectorLdsOff(graph.nodes.size(), 0)
+  {
+    windowed = g.rings != RingLayout::ROWS && g.totalRings;
+    if (g.rings == RingLayout::SECTORS)
+      for (size_t i = 0; i < g.nodes.size(); ++i)
+        if (g.nodes[i].type == NODE_PROC && g.nodes[i].ringLen)
+        {
+          sectorLdsOff[i] = sectorLdsPerWave;
+          sectorLdsPerWave += (size_t)mlgpu_proc_rings(g.nodes[i].kind) * 512 + 1024;
+        }
+    // Ring layout 2 moves a voice's pieces with its NEIGHBOURS' lanes: a bank whose last wavefront is not full keeps that wavefront's
+    // spare lanes running. They run the bank's last voice again - same inputs, same state, same stores - on ring memory and LDS
+    // columns of their own (vr: the lane's place; the rings are laid out for whole 256-voice blocks and cleared together, so a spare
+    // lane's ring always holds what the last voice's holds).
+    // (... and so does an output that is the mixdown of all voices: the tree over a wavefront's 64 lanes, a spare lane adds +0)
+    bool anyMix = false;
+    for (size_t o = 0; o < g.outputs.size(); ++o) anyMix = anyMix || g.outputMix[o];
+    partialWaves = ((g.rings == RingLayout::TRANSPOSED && g.totalRings) || anyMix) && (g.V % 64);
+    ringLane = partialWaves ? "vr" : "v";
+    // a row of the state memory at this lane: the row's address is wave-uniform (scalar arithmetic), the lane's place a 32-bit offset on
+    // it - one memory instruction where `a.state[row * a.V + v]` with a 64-bit v is a 64-bit vector add in front of it
+    stateAddr32 = g.V < ((size_t)1 << 30) && !g.rowAddr64;
+    PF = g.nInputs > 0;
+    oscTrips = hasOscTrips(&g);
+    ringTrips = g.rings == RingLayout::SECTORS && g.totalRings;  // ring layout 4: trips of two quads, every ring's loads in the trip's prologue
+  }
+  static std::string sfx(int l) { return "_" + std::to_string(l); }
+  static std::string name(int j, const std::string& ph, int l) { return "n" + std::to_string(j) + ph + sfx(l); }
   // a group sum of 16 voices (one instrument's voices): four quads of the wavefront's 64 voices are parked in LDS and every lane
   // then adds up ONE (instrument, sample) pair in voice order - 2.3 instructions per voice-sample where the lane-shift chain
   // (group_sum_in_order) takes 16
-  auto ldsSum = [&](size_t o) { return VL == 1 && g->outputGroup[o] == 16; };
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    if (ldsSum(o))
-      s << "  __shared__ float ldsSum" << o << "[4 * kGroup16Strip];\n  float* const strip" << o << " = ldsSum" << o << " + (threadIdx.x >> 6) * kGroup16Strip;\n";
-  // Ring layout 2 moves a voice's pieces with its NEIGHBOURS' lanes: a bank whose last wavefront is not full keeps that wavefront's
-  // spare lanes running. They run the bank's last voice again - same inputs, same state, same stores - on ring memory and LDS
-  // columns of their own (vr: the lane's place; the rings are laid out for whole 256-voice blocks and cleared together, so a spare
-  // lane's ring always holds what the last voice's holds).
-  bool anyMix = false;
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    if (g->outputMix[o])
-    {
-      anyMix = true;
-      s << "  __shared__ __attribute__((aligned(16))) float ldsMix" << o << "[4 * kMixStrip];\n  float* const mstrip" << o << " = ldsMix" << o << " + (threadIdx.x >> 6) * kMixStrip;\n";
-    }
-  // (... and so does an output that is the mixdown of all voices: the tree over a wavefront's 64 lanes, a spare lane adds +0)
-  const bool partialWaves = ((g->transposedRings && g->totalRings) || anyMix) && (g->V % 64);
-  s << "  size_t blk = blockIdx.x;\n  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;\n"
-       "  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);\n";
-  if (partialWaves)
-    s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n  if ((vr_0 & ~(size_t)63) >= a.V) return;\n  const size_t v_0 = vr_0 < a.V ? vr_0 : a.V - 1;\n";
-  else
-    s << "  const size_t v_0 = blk * " << 256 * VL << " + threadIdx.x;\n  if (v_0 >= a.V) return;\n";
-  const std::string ringLane = partialWaves ? "vr" : "v";
-  // a row of the state memory at this lane: the row's address is wave-uniform (scalar arithmetic), the lane's place a 32-bit offset on
-  // it - one memory instruction where `a.state[row * a.V + v]` with a 64-bit v is a 64-bit vector add in front of it
-  const bool stateAddr32 = g->V < ((size_t)1 << 30) && !g->rowAddr64;
-  if (stateAddr32) s << "  const uint32_t v4_0 = (uint32_t)v_0 * 4u;\n";
-  auto stateRef = [&](const std::string& row, int l) {
+  bool ldsSum(size_t o) const { return VL == 1 && g.outputGroup[o] == 16; }
+  std::string stateRef(const std::string& row, int l) const
+  {
     return stateAddr32 ? "*state_row(a, " + row + ", v4" + sfx(l) + ")" : "a.state[(size_t)(" + row + ") * a.V + v" + sfx(l) + "]";
-  };
-  // a lane whose second voice does not exist recomputes its first one: same inputs, same state, same stores
-  for (int l = 1; l < VL; ++l)
-  {
-    s << "  const size_t v" << sfx(l) << " = (v_0 + " << 256 * l << " < a.V) ? v_0 + " << 256 * l << " : v_0;\n";
-    if (stateAddr32) s << "  const uint32_t v4" << sfx(l) << " = (uint32_t)v" << sfx(l) << " * 4u;\n";
   }
-  auto emit = [&](size_t i, const char* indent) {
-    for (int l = 0; l < VL; ++l)
-    {
-      s << indent << "const float n" << i << sfx(l) << " = " << nodeExpr(g, i, l) << ";";
-      if (l == 0 && !g->nodes[i].name.empty()) s << "  // " << g->nodes[i].name;
-      s << "\n";
-    }
-  };
-  // once per voice: processor state, signal bases, voice-rate nodes
-  for (size_t i = 0; i < g->nodes.size(); ++i)
+  // a PulseGen's width: its input, or its own coefficient
+  std::string width(size_t j, int l) const
   {
-    const Node& n = g->nodes[i];
-    for (int l = 0; l < VL; ++l)
-    {
-      const std::string L = sfx(l);
-      if (n.type == NODE_PROC)
-      {
-        s << "  Proc<" << n.kind << "> p" << i << L << ";\n  const VoiceMem m" << i << L << "{a.coeffs + (size_t)" << n.cOff << " * a.V + v" << L
-          << ", a.state + (size_t)" << n.sOff << " * a.V + v" << L << ", a.V";
-        // (a ring of at most 4 GiB over the bank: 32-bit row offsets from the wave-uniform start of the ring)
-        const bool a32 = n.ringLen && g->rowAddr32 && (size_t)n.ringLen * g->V * sizeof(float) <= ((size_t)1 << 32) && n.ringLen < ((size_t)1 << 24);
-        if (n.ringLen && !g->windowedRings) s << ", a.mem + (size_t)" << n.memOff << " * a.V" << (a32 ? std::string() : " + v" + std::string(L)) << ", " << (n.ringLen - 1) << "u";
-        if (n.ringLen && !g->windowedRings && (earlyRingReads(g, n) || a32)) s << ", " << (earlyRingReads(g, n) ? "ldsEarlyWave + " + std::to_string(n.earlySlot * 64) : std::string("nullptr"));
-        if (a32) s << ", 0u, (uint32_t)v" << L << " * 4u, (uint32_t)a.V * 4u, true";
-        if (n.ringLen && g->transposedRings)
-          s << ", a.mem + (size_t)" << n.memOff << " * ((a.V + 255) & ~(size_t)255) + (" << ringLane << L << " >> 8) * (size_t)" << n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * 256
-            << " + (" << ringLane << L << " & 255) * 16, " << (n.ringLen - 1)
-            << "u, ldsRings + (" << (size_t)n.ringSlot * 4 << " + (threadIdx.x >> 6)) * kTStrip + (threadIdx.x & 63)";
-        else if (n.ringLen && g->windowedRings)
-          s << ", a.mem + (size_t)" << n.memOff << " * ((a.V + 255) & ~(size_t)255) + (v" << L << " >> 8) * (size_t)" << n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * 256
-            << " + (v" << L << " & 255) * 8, " << (n.ringLen - 1)
-            << "u, ldsRings + " << (g->sectorRings ? "(threadIdx.x >> 6) * " + std::to_string(sectorLdsPerWave) + " + " + std::to_string(sectorLdsOff[i]) + ", " + std::to_string((size_t)mlgpu_proc_rings(n.kind) * 512) + "u"
-                                                   : std::to_string((size_t)n.ringSlot * 8 * 256) + " + threadIdx.x");
-        s << "};\n  p" << i << L << ".load(m" << i << L << ", tables);\n";
-      }
-      else if (n.type == NODE_INPUT)
-      {
-        const std::string row = g->inputGroup[n.slot] > 1 ? "(v" + std::string(L) + " / " + std::to_string(g->inputGroup[n.slot]) + ")" : "v" + std::string(L);
-        s << "  const f32x4* in" << n.slot << L << " = (const f32x4*)a.in[" << n.slot << "].base + " << row << " * a.in[" << n.slot << "].strideV;\n";
-      }
-      else if (n.type == NODE_CONTROL)
-      {
-        s << "  const float* ctl" << n.slot << L << " = a.ctl[" << n.slot << "] + v" << L << ";\n";
-      }
-    }
-    if (n.rate == RATE_VOICE && n.type != NODE_PROC) emit(i, "  ");
+    const Node& m = g.nodes[j];
+    return m.in.size() == 2 ? "n" + std::to_string(m.in[1]) + sfx(l) : "p" + std::to_string(j) + sfx(l) + ".width";
   }
-  for (size_t i = 0; i < g->nodes.size(); ++i)
+  // expr(l) of every voice of the lane, or-ed; and the wave-uniform ballot of such a test
+  template <class F>
+  std::string anyVoice(F expr) const
   {
-    const Node& n = g->nodes[i];
-    if (n.type == NODE_PROC && (n.kind == MLGPU_PROC_SAW_GEN || n.kind == MLGPU_PROC_PULSE_GEN) && g->nodes[n.in[0]].rate == RATE_VOICE)
+    std::string t;
+    for (int l = 0; l < VL; ++l) t += (l ? " || " : "") + expr(l);
+    return t;
+  }
+  static std::string ballot(const std::string& test) { return "__builtin_amdgcn_ballot_w64(" + test + ")"; }
+  // node j's value for every voice of the lane, in a region's phase `ph` at sample index `idx`
+  void value(size_t j, const std::string& indent, const std::string& ph = "", const std::string& idx = "q * 4 + k")
+  {
+    for (int l = 0; l < VL; ++l)
+      s << indent << "const float " << name((int)j, ph, l) << " = " << nodeExpr(&g, j, l, ph, idx) << ";"
+        << (l == 0 && !g.nodes[j].name.empty() ? "  // " + g.nodes[j].name : std::string()) << "\n";
+  }
+  void header()
+  {
+    static const char* const kRingWindows[] = {"", "#define MLGPU_RING_WINDOWS 1\n", "#define MLGPU_RING_WINDOWS 2\n", "#define MLGPU_RING_WINDOWS 3\n"};
+    s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane)\n" << kRingWindows[(int)g.rings]
+      << (g.strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\n#include \"mldsp_ops.hpp\"\n"
+      << (g.hasEventRows ? "#include \"mldsp_events.hpp\"\n" : "") << "using namespace mldev;\n";
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_VOP && g.nodes[i].kind == MLGPU_VOP_TABLE)
+      {
+        s << "__constant__ unsigned cv" << i << "[64] = {";
+        for (int j = 0; j < 64; ++j) s << (j ? ", " : "") << "0x" << std::hex << g.nodes[i].table[j] << std::dec << "u";
+        s << "};\n";
+      }
+    // windowed rings: the latency of a sector refill is hidden by other waves only, so keep at least two per SIMD
+    const std::string bound = (g.rings == RingLayout::TRANSPOSED && g.totalRings == 1) ? ", 4" : ringTrips ? ", 1" : windowed ? ", 2"
+                              : form.minWaves ? ", " + std::to_string(form.minWaves) : std::string();
+    s << "extern \"C\" __global__ __launch_bounds__(256" << bound << ") void mlgpu_graph_kernel(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
+  }
+  void sharedMemory()
+  {
+    if (g.hasImpulse) s << "  __shared__ float ldsTable[32];\n  if (threadIdx.x < 17) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];\n  __syncthreads();\n";
+    s << "  const KernelTables tables{" << (g.hasImpulse ? "ldsTable" : "nullptr") << "};\n";
+    if (g.rings == RingLayout::TRANSPOSED && g.totalRings)
+      s << "  __shared__ float ldsRings[" << (size_t)g.totalRings * 4 << " * kTStrip];  // [ring][wavefront][40 rows][64]: write window + two read chunks\n";
+    if (ringTrips) s << "  __shared__ __attribute__((aligned(16))) float ldsRings[" << 4 * sectorLdsPerWave << "];  // [wavefront][node: held sectors, history rows]\n";
+    else if (g.rings == RingLayout::WINDOWS && g.totalRings) s << "  __shared__ float ldsRings[" << (size_t)g.totalRings * 8 * 256 << "];  // write windows, [ring][8][256 lanes]\n";
+    if (g.earlyRows)
+      s << "  __shared__ float ldsEarly[" << 4 * g.earlySlots * 64 << "];  // [wavefront][ring read][64 lanes]: where the early ring reads land\n"
+        << "  float* const ldsEarlyWave = ldsEarly + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * " << g.earlySlots * 64 << ";\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (ldsSum(o))
+        s << "  __shared__ float ldsSum" << o << "[4 * kGroup16Strip];\n  float* const strip" << o << " = ldsSum" << o << " + (threadIdx.x >> 6) * kGroup16Strip;\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (g.outputMix[o])
+        s << "  __shared__ __attribute__((aligned(16))) float ldsMix" << o << "[4 * kMixStrip];\n  float* const mstrip" << o << " = ldsMix" << o << " + (threadIdx.x >> 6) * kMixStrip;\n";
+  }
+  // the lane's voices, then once per voice: processor state, signal bases, voice-rate nodes
+  void voiceSetup()
+  {
+    s << "  size_t blk = blockIdx.x;\n  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;\n"
+         "  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);\n";
+    if (partialWaves)
+      s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n  if ((vr_0 & ~(size_t)63) >= a.V) return;\n  const size_t v_0 = vr_0 < a.V ? vr_0 : a.V - 1;\n";
+    else
+      s << "  const size_t v_0 = blk * " << 256 * VL << " + threadIdx.x;\n  if (v_0 >= a.V) return;\n";
+    if (stateAddr32) s << "  const uint32_t v4_0 = (uint32_t)v_0 * 4u;\n";
+    // a lane whose second voice does not exist recomputes its first one: same inputs, same state, same stores
+    for (int l = 1; l < VL; ++l)
     {
-      s << "  const bool odd" << i << " = __builtin_amdgcn_ballot_w64(blep_freq_is_odd(n" << n.in[0] << "_0)";
-      for (int l = 1; l < VL; ++l) s << " || blep_freq_is_odd(n" << n.in[0] << sfx(l) << ")";
-      // a PulseGen whose width is per voice too (its own coefficient, or a voice-rate node): the width's range joins the test
-      if (n.kind == MLGPU_PROC_PULSE_GEN && (n.in.size() == 1 || g->nodes[n.in[1]].rate == RATE_VOICE))
+      s << "  const size_t v" << sfx(l) << " = (v_0 + " << 256 * l << " < a.V) ? v_0 + " << 256 * l << " : v_0;\n";
+      if (stateAddr32) s << "  const uint32_t v4" << sfx(l) << " = (uint32_t)v" << sfx(l) << " * 4u;\n";
+    }
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+    {
+      const Node& n = g.nodes[i];
+      for (int l = 0; l < VL; ++l)
+      {
+        const std::string L = sfx(l);
+        if (n.type == NODE_PROC)
+          procSetup(i, L);
+        else if (n.type == NODE_INPUT)
+        {
+          const std::string row = g.inputGroup[n.slot] > 1 ? "(v" + L + " / " + std::to_string(g.inputGroup[n.slot]) + ")" : "v" + L;
+          s << "  const f32x4* in" << n.slot << L << " = (const f32x4*)a.in[" << n.slot << "].base + " << row << " * a.in[" << n.slot << "].strideV;\n";
+        }
+        else if (n.type == NODE_CONTROL)
+          s << "  const float* ctl" << n.slot << L << " = a.ctl[" << n.slot << "] + v" << L << ";\n";
+      }
+      if (n.rate == RATE_VOICE && n.type != NODE_PROC) value(i, "  ");
+    }
+  }
+  // processor i of voice L: its object, its memory (VoiceMem: coefficients, state, rings), its state loaded
+  void procSetup(size_t i, const std::string& L)
+  {
+    const Node& n = g.nodes[i];
+    s << "  Proc<" << n.kind << "> p" << i << L << ";\n  const VoiceMem m" << i << L << "{a.coeffs + (size_t)" << n.cOff << " * a.V + v" << L
+      << ", a.state + (size_t)" << n.sOff << " * a.V + v" << L << ", a.V";
+    // (a ring of at most 4 GiB over the bank: 32-bit row offsets from the wave-uniform start of the ring)
+    const bool a32 = n.ringLen && g.rowAddr32 && (size_t)n.ringLen * g.V * sizeof(float) <= ((size_t)1 << 32) && n.ringLen < ((size_t)1 << 24);
+    const bool rows = g.rings == RingLayout::ROWS;
+    if (n.ringLen && rows) s << ", a.mem + (size_t)" << n.memOff << " * a.V" << (a32 ? std::string() : " + v" + L) << ", " << (n.ringLen - 1) << "u";
+    if (n.ringLen && rows && (earlyRingReads(&g, n) || a32)) s << ", " << (earlyRingReads(&g, n) ? "ldsEarlyWave + " + std::to_string(n.earlySlot * 64) : std::string("nullptr"));
+    if (a32) s << ", 0u, (uint32_t)v" << L << " * 4u, (uint32_t)a.V * 4u, true";
+    if (n.ringLen && g.rings == RingLayout::TRANSPOSED)
+      s << ", a.mem + (size_t)" << n.memOff << " * ((a.V + 255) & ~(size_t)255) + (" << ringLane << L << " >> 8) * (size_t)" << n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * 256
+        << " + (" << ringLane << L << " & 255) * 16, " << (n.ringLen - 1)
+        << "u, ldsRings + (" << (size_t)n.ringSlot * 4 << " + (threadIdx.x >> 6)) * kTStrip + (threadIdx.x & 63)";
+    else if (n.ringLen && !rows)
+      s << ", a.mem + (size_t)" << n.memOff << " * ((a.V + 255) & ~(size_t)255) + (v" << L << " >> 8) * (size_t)" << n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * 256
+        << " + (v" << L << " & 255) * 8, " << (n.ringLen - 1)
+        << "u, ldsRings + " << (g.rings == RingLayout::SECTORS ? "(threadIdx.x >> 6) * " + std::to_string(sectorLdsPerWave) + " + " + std::to_string(sectorLdsOff[i]) + ", " + std::to_string((size_t)mlgpu_proc_rings(n.kind) * 512) + "u"
+                                                           : std::to_string((size_t)n.ringSlot * 8 * 256) + " + threadIdx.x");
+    s << "};\n  p" << i << L << ".load(m" << i << L << ", tables);\n";
+  }
+  // the oscillators' wave-uniform tests, asked once per launch
+  void oscillatorTests()
+  {
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+    {
+      const Node& n = g.nodes[i];
+      const bool pulseVoiceWidth = n.type == NODE_PROC && n.kind == MLGPU_PROC_PULSE_GEN && (n.in.size() == 1 || g.nodes[n.in[1]].rate == RATE_VOICE);
+      auto widthOdd = [&](int l) { return "pulse_width_is_odd(" + width(i, l) + ")"; };
+      if (n.type == NODE_PROC && (n.kind == MLGPU_PROC_SAW_GEN || n.kind == MLGPU_PROC_PULSE_GEN) && g.nodes[n.in[0]].rate == RATE_VOICE)
+      {
+        // a PulseGen whose width is per voice too (its own coefficient, or a voice-rate node): the width's range joins the test
+        const std::string odd = anyVoice([&](int l) { return "blep_freq_is_odd(" + name(n.in[0], "", l) + ")"; });
+        s << "  const bool odd" << i << " = " << ballot(pulseVoiceWidth ? odd + " || " + anyVoice(widthOdd) : odd) << " != 0;\n";
+        if (isOscTrip(&g, n))
+          s << "  const bool dense" << i << " = odd" << i << " || "
+            << ballot(anyVoice([&](int l) { return "trip_freq_is_dense(" + name(n.in[0], "", l) + ", " + std::to_string(g.oscTripQ * 4) + ")"; })) << " != 0;\n";
+      }
+      else if (pulseVoiceWidth)
+        s << "  const bool oddw" << i << " = " << ballot(anyVoice(widthOdd)) << " != 0;\n";
+    }
+    // a Saw / Pulse pair whose phase counters are equal in every lane of the wavefront
+    auto counters = [&](size_t i, int j) {
+      return ballot(anyVoice([&](int l) { return "p" + std::to_string(i) + sfx(l) + ".omega32 != p" + std::to_string(j) + sfx(l) + ".omega32"; })) + " == 0;\n";
+    };
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (lockedPartner(&g, i) >= 0)
+        s << "  const bool locked" << i << " = !dense" << i << " && !dense" << lockedPartner(&g, i) << " && " << counters(i, lockedPartner(&g, i));
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (streamLockPulseOf(&g, i) >= 0) s << "  const bool slocked" << i << " = " << counters(i, streamLockPulseOf(&g, i));
+  }
+  void outputsAndPrefetch()
+  {
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      for (int l = 0; l < VL; ++l)
+      {
+        if (g.outputMix[o])  // the rows of 64-voice group sums (mlgpu_mixdown's first stage): [(group * T + t) * 64 + sample]
+          s << "  float* const out" << o << sfx(l) << " = (float*)a.out[" << o << "].base + ((" << ringLane << sfx(l) << " >> 6) * a.T) * 64;\n";
+        else if (g.outputGroup[o])
+          s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + (v" << sfx(l) << " / " << g.outputGroup[o] << ") * a.out[" << o << "].strideV;\n";
+        else
+          s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + v" << sfx(l) << " * a.out[" << o << "].strideV;\n";
+      }
+    // a Downsample2x region's filter pairs its parent's samples (m - 1, m): the previous sample of each of its sources
+    for (const Region& R : g.regions)
+      if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X)
+        for (int in : R.ins)
+          for (int l = 0; l < VL; ++l) s << "  float prev" << in << sfx(l) << " = 0.f;\n";
+    // EventsToSignals rows made here from the control records of e2s_ctl_kernel: one CtlVoice per voice (lane == voice index: MIDI protocol)
+    if (g.hasEventRows)
+      for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
+    // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
+    // whole HBM round trip per quad, and with four wavefronts per SIMD there are long stretches with only one or two of them able to
+    // issue (one wavefront alone issues at 40 % of the SIMD's rate). The very last quad of a launch loads itself again.
+    if (PF) s << "  if (a.T == 0) return;\n";
+    for (int i = 0; PF && i < g.nInputs; ++i)
+      for (int l = 0; l < VL; ++l)
+        s << "  const f32x4* pf" << i << sfx(l) << " = in" << i << sfx(l) << ";\n  f32x4 nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_FEEDBACK && g.nodes[i].region < 0)
         for (int l = 0; l < VL; ++l)
         {
-          if (n.in.size() == 1) s << " || pulse_width_is_odd(p" << i << sfx(l) << ".width)";
-          else s << " || pulse_width_is_odd(n" << n.in[1] << sfx(l) << ")";
+          const std::string nm = std::to_string(i) + sfx(l);
+          s << "  float fbn" << nm << "[4], fbm" << nm << "[4];\n#pragma unroll\n  for (int kk = 0; kk < 4; ++kk)\n  {\n    fbn" << nm << "[kk] = u2f(" << stateRef(std::to_string(g.nodes[i].sOff) + " + kk", l)
+            << ");\n    fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g.nodes[i].sOff) + " + 4 + kk", l) << ");\n  }\n";
         }
-      s << ") != 0;\n";
-      if (isOscTrip(g, n))
+    s << "  const uint32_t turn0 = wave_slot();\n";
+  }
+  // the DSPVector loop's head: vector-rate nodes, the vector-rate processors' begin_vector, the trips' and quads' loops
+  void vectorHead()
+  {
+    s << "  for (size_t t = 0; t < a.T; ++t)\n  {\n";
+    // (Rounds 3-4 walked the event records inside this kernel - 134 spilled registers, 0.35 scalar / branch instructions per vector
+    // one; round 5: the record walk is e2s_ctl_kernel's, this kernel expands its control records - mldsp_events.hpp.)
+    if (g.hasEventRows)
+      for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".begin_vector(t);\n";
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+    {
+      const Node& n = g.nodes[i];
+      if (n.rate == RATE_VECTOR) value(i, "    ");
+      if (n.type != NODE_PROC || (n.kind == MLGPU_PROC_TEMPO_LOCK && g.nodes[n.in[0]].type != NODE_INPUT)) continue;
+      if (n.kind == MLGPU_PROC_TEMPO_LOCK)
       {
-        s << "  const bool dense" << i << " = odd" << i << " || __builtin_amdgcn_ballot_w64(";
-        for (int l = 0; l < VL; ++l) s << (l ? " || " : "") << "trip_freq_is_dense(n" << n.in[0] << sfx(l) << ", " << g->oscTripQ * 4 << ")";
-        s << ") != 0;\n";
+        const int slot = g.nodes[n.in[0]].slot;  // the streamed input: first two samples of this vector
+        for (int l = 0; l < VL; ++l)
+          s << "    { const f32x4 x01 = in" << slot << sfx(l) << "[t * a.in[" << slot << "].strideT]; p" << i << sfx(l) << ".begin_vector(x01[0], x01[1], n"
+            << n.in[1] << sfx(l) << ", n" << n.in[2] << sfx(l) << "); }\n";
       }
+      else if (mlgpu_proc_is_vector_rate(n.kind))
+        for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".begin_vector(n" << n.in[0] << sfx(l) << ");\n";
     }
-    else if (n.type == NODE_PROC && n.kind == MLGPU_PROC_PULSE_GEN && (n.in.size() == 1 || g->nodes[n.in[1]].rate == RATE_VOICE))
+    if (oscTrips || ringTrips)
+      tripHead();
+    else
     {
-      s << "  const bool oddw" << i << " = __builtin_amdgcn_ballot_w64(";
-      for (int l = 0; l < VL; ++l)
-      {
-        if (l) s << " || ";
-        if (n.in.size() == 1) s << "pulse_width_is_odd(p" << i << sfx(l) << ".width)";
-        else s << "pulse_width_is_odd(n" << n.in[1] << sfx(l) << ")";
-      }
-      s << ") != 0;\n";
+      s << "#pragma unroll " << (windowed ? 1 : form.quadsPerTrip) << "\n    for (int q = 0; q < 16; ++q)\n    {\n";
+      s << "      if ((q & 1) == 0) take_turns_by_clock(turn0, " << kTurnClockShift << ");\n";
     }
+    quadHead();
   }
-  for (size_t i = 0; i < g->nodes.size(); ++i)
+  // the quads in trips of oscTripQ: the oscillators' samples of a trip first, then its quads (fully unrolled: qq is a constant)
+  void tripHead()
   {
-    const int j = lockedPartner(g, i);
-    if (j < 0) continue;
-    s << "  const bool locked" << i << " = !dense" << i << " && !dense" << j << " && __builtin_amdgcn_ballot_w64(";
-    for (int l = 0; l < VL; ++l) s << (l ? " || " : "") << "p" << i << sfx(l) << ".omega32 != p" << j << sfx(l) << ".omega32";
-    s << ") == 0;\n";
-  }
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-  {
-    const int j = streamLockPulseOf(g, i);
-    if (j < 0) continue;
-    s << "  const bool slocked" << i << " = __builtin_amdgcn_ballot_w64(";
-    for (int l = 0; l < VL; ++l) s << (l ? " || " : "") << "p" << i << sfx(l) << ".omega32 != p" << j << sfx(l) << ".omega32";
-    s << ") == 0;\n";
-  }
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    for (int l = 0; l < VL; ++l)
-    {
-      if (g->outputMix[o])  // the rows of 64-voice group sums (mlgpu_mixdown's first stage): [(group * T + t) * 64 + sample]
-        s << "  float* const out" << o << sfx(l) << " = (float*)a.out[" << o << "].base + ((" << (partialWaves ? "vr" : "v") << sfx(l) << " >> 6) * a.T) * 64;\n";
-      else if (g->outputGroup[o])
-        s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + (v" << sfx(l) << " / " << g->outputGroup[o] << ") * a.out[" << o << "].strideV;\n";
-      else
-        s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + v" << sfx(l) << " * a.out[" << o << "].strideV;\n";
-    }
-  // a Downsample2x region's filter pairs its parent's samples (m - 1, m): the previous sample of each of its sources
-  for (const Region& R : g->regions)
-    if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X)
-      for (int in : R.ins)
-        for (int l = 0; l < VL; ++l) s << "  float prev" << in << sfx(l) << " = 0.f;\n";
-  // EventsToSignals rows made here from the control records of e2s_ctl_kernel: one CtlVoice per voice (lane == voice index: MIDI protocol)
-  if (g->hasEventRows)
-    for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
-  // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
-  // whole HBM round trip per quad, and with four wavefronts per SIMD there are long stretches with only one or two of them able to
-  // issue (one wavefront alone issues at 40 % of the SIMD's rate). The very last quad of a launch loads itself again.
-  const bool PF = g->nInputs > 0;
-  if (PF) s << "  if (a.T == 0) return;\n";
-  for (int i = 0; PF && i < g->nInputs; ++i)
-    for (int l = 0; l < VL; ++l)
-      s << "  const f32x4* pf" << i << sfx(l) << " = in" << i << sfx(l) << ";\n  f32x4 nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].region < 0)
-      for (int l = 0; l < VL; ++l)
-      {
-        const std::string nm = std::to_string(i) + sfx(l);
-        s << "  float fbn" << nm << "[4], fbm" << nm << "[4];\n#pragma unroll\n  for (int kk = 0; kk < 4; ++kk)\n  {\n    fbn" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + kk", l)
-          << ");\n    fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + 4 + kk", l) << ");\n  }\n";
-      }
-  s << "  const uint32_t turn0 = wave_slot();\n";
-  s << "  for (size_t t = 0; t < a.T; ++t)\n  {\n";
-  // (Rounds 3-4 walked the event records inside this kernel - 134 spilled registers, 0.35 scalar / branch instructions per vector
-  // one; round 5: the record walk is e2s_ctl_kernel's, this kernel expands its control records - mldsp_events.hpp.)
-  if (g->hasEventRows)
-    for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".begin_vector(t);\n";
-  // once per DSPVector: vector-rate nodes, then the vector-rate processors' begin_vector
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-  {
-    const Node& n = g->nodes[i];
-    if (n.rate == RATE_VECTOR) emit(i, "    ");
-    if (n.type == NODE_PROC && n.kind == MLGPU_PROC_TEMPO_LOCK && g->nodes[n.in[0]].type != NODE_INPUT)
-    {
-    }
-    else if (n.type == NODE_PROC && n.kind == MLGPU_PROC_TEMPO_LOCK)
-    {
-      const int slot = g->nodes[n.in[0]].slot;  // the streamed input: first two samples of this vector
-      for (int l = 0; l < VL; ++l)
-        s << "    { const f32x4 x01 = in" << slot << sfx(l) << "[t * a.in[" << slot << "].strideT]; p" << i << sfx(l) << ".begin_vector(x01[0], x01[1], n"
-          << n.in[1] << sfx(l) << ", n" << n.in[2] << sfx(l) << "); }\n";
-    }
-    else if (n.type == NODE_PROC && mlgpu_proc_is_vector_rate(n.kind))
-      for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".begin_vector(n" << n.in[0] << sfx(l) << ");\n";
-  }
-  const bool oscTrips = hasOscTrips(g);
-  const bool ringTrips = g->sectorRings && g->totalRings;  // ring layout 4: trips of two quads, every ring's loads in the trip's prologue
-  if (oscTrips || ringTrips)
-  {
-    // the quads in trips of oscTripQ: the oscillators' samples of a trip first, then its quads (fully unrolled: qq is a constant)
-    const int tq = ringTrips ? 2 : g->oscTripQ, unroll = (g->windowedRings && g->totalRings) ? 1 : std::max(1, g->unrollQ / tq);
+    const int tq = ringTrips ? 2 : g.oscTripQ, unroll = windowed ? 1 : std::max(1, form.quadsPerTrip / tq);
     s << "#pragma unroll " << unroll << "\n    for (int q2 = 0; q2 < 16; q2 += " << tq << ")\n    {\n";
     s << "    take_turns_by_clock(turn0, " << kTurnClockShift << ");\n";
-    std::vector<char> paired(g->nodes.size(), 0);
-    for (size_t i = 0; i < g->nodes.size(); ++i)
-      if (lockedPartner(g, i) >= 0) paired[i] = paired[(size_t)lockedPartner(g, i)] = 1;
-    for (size_t i = 0; i < g->nodes.size(); ++i)
+    std::vector<char> paired(g.nodes.size(), 0);
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (lockedPartner(&g, i) >= 0) paired[i] = paired[(size_t)lockedPartner(&g, i)] = 1;
+    auto tripU = [&](size_t i, int l, const char* indent, bool withWidth) {
+      const Node& n = g.nodes[i];
+      s << indent << "p" << i << sfx(l) << ".trip_u<" << tq * 4 << ">(n" << n.in[0] << sfx(l);
+      if (withWidth && n.in.size() == 2) s << ", n" << n.in[1] << sfx(l);
+      s << ", odd" << i << ", dense" << i << ", osc" << i << sfx(l) << ");\n";
+    };
+    for (size_t i = 0; i < g.nodes.size(); ++i)
     {
-      const Node& n = g->nodes[i];
-      if (!isOscTrip(g, n)) continue;
+      if (!isOscTrip(&g, g.nodes[i])) continue;
       for (int l = 0; l < VL; ++l) s << "    float osc" << i << sfx(l) << "[" << tq * 4 << "];\n";
       if (paired[i]) continue;  // made with its partner below
-      for (int l = 0; l < VL; ++l)
-      {
-        s << "    p" << i << sfx(l) << ".trip_u<" << tq * 4 << ">(n" << n.in[0] << sfx(l);
-        if (n.in.size() == 2) s << ", n" << n.in[1] << sfx(l);
-        s << ", odd" << i << ", dense" << i << ", osc" << i << sfx(l) << ");\n";
-      }
+      for (int l = 0; l < VL; ++l) tripU(i, l, "    ", true);
     }
-    for (size_t i = 0; i < g->nodes.size(); ++i)
+    for (size_t i = 0; i < g.nodes.size(); ++i)
     {
-      const int j = lockedPartner(g, i);
+      const int j = lockedPartner(&g, i);
       if (j < 0) continue;
-      const Node &n = g->nodes[i], &m = g->nodes[(size_t)j];
-      auto width = [&](int l) { return m.in.size() == 2 ? "n" + std::to_string(m.in[1]) + sfx(l) : "p" + std::to_string(j) + sfx(l) + ".width"; };
       for (int l = 0; l < VL; ++l) s << "    const uint32_t keep" << i << sfx(l) << " = p" << i << sfx(l) << ".omega32, keep" << j << sfx(l) << " = p" << j << sfx(l) << ".omega32;\n";
       s << "    bool made" << i << " = locked" << i << ";\n";
       for (int l = 0; l < VL; ++l)
-        s << "    if (made" << i << ") made" << i << " = trip_locked<" << tq * 4 << ">(p" << i << sfx(l) << ", p" << j << sfx(l) << ", n" << n.in[0] << sfx(l) << ", " << width(l)
+        s << "    if (made" << i << ") made" << i << " = trip_locked<" << tq * 4 << ">(p" << i << sfx(l) << ", p" << j << sfx(l) << ", n" << g.nodes[i].in[0] << sfx(l) << ", " << width((size_t)j, l)
           << ", osc" << i << sfx(l) << ", osc" << j << sfx(l) << ");\n";
       // (two voices per lane: a suspect trip of the second voice sends both back - the first one's counters are restored below)
       s << "    if (!made" << i << ")\n    {\n";
       for (int l = 0; l < VL; ++l)
       {
         s << "      p" << i << sfx(l) << ".omega32 = keep" << i << sfx(l) << ";\n      p" << j << sfx(l) << ".omega32 = keep" << j << sfx(l) << ";\n";
-        s << "      p" << i << sfx(l) << ".trip_u<" << tq * 4 << ">(n" << n.in[0] << sfx(l) << ", odd" << i << ", dense" << i << ", osc" << i << sfx(l) << ");\n";
-        s << "      p" << j << sfx(l) << ".trip_u<" << tq * 4 << ">(n" << m.in[0] << sfx(l);
-        if (m.in.size() == 2) s << ", n" << m.in[1] << sfx(l);
-        s << ", odd" << j << ", dense" << j << ", osc" << j << sfx(l) << ");\n";
+        tripU(i, l, "      ", false);
+        tripU((size_t)j, l, "      ", true);
       }
       s << "    }\n";
     }
     if (ringTrips)
-      for (size_t i = 0; i < g->nodes.size(); ++i)
-        if (g->nodes[i].type == NODE_PROC && g->nodes[i].region < 0 && mlgpu_proc_rings(g->nodes[i].kind))
+      for (size_t i = 0; i < g.nodes.size(); ++i)
+        if (g.nodes[i].type == NODE_PROC && g.nodes[i].region < 0 && mlgpu_proc_rings(g.nodes[i].kind))
           for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".trip_begin();\n";
     s << "#pragma unroll\n    for (int qq = 0; qq < " << tq << "; ++qq)\n    {\n      const int q = q2 + qq;\n";
   }
-  else
+  // the quad's head: the next quad's inputs, the quad's feedback values, then the sample loop
+  void quadHead()
   {
-    s << "#pragma unroll " << ((g->windowedRings && g->totalRings) ? 1 : g->unrollQ) << "\n    for (int q = 0; q < 16; ++q)\n    {\n";
-    s << "      if ((q & 1) == 0) take_turns_by_clock(turn0, " << kTurnClockShift << ");\n";
-  }
-  // the next quad's address: one step on; from a vector's last quad to the next vector's first; the launch's last quad stays
-  if (PF) s << "      const bool lastQ = (q == 15), lastT = (t + 1 == a.T);\n";
-  for (int i = 0; i < g->nInputs; ++i)
-    for (int l = 0; l < VL; ++l)
-    {
-      s << "      const f32x4 xin" << i << sfx(l) << " = nx" << i << sfx(l) << ";\n      pf" << i << sfx(l) << " += lastQ ? (lastT ? (size_t)0 : a.in[" << i
-        << "].strideT - 15 * a.in[" << i << "].strideQ) : a.in[" << i << "].strideQ;\n      nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
-    }
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    for (int l = 0; l < VL; ++l) s << "      f32x4 y" << o << sfx(l) << ";\n";
-  if (g->hasEventRows)
-    for (int l = 0; l < VL; ++l)
-      s << "      mlev::CtlVoice::f32x4e evP" << sfx(l) << ", evG" << sfx(l) << ";\n      ev" << sfx(l) << ".quad(t, q, evP" << sfx(l) << ", evG" << sfx(l) << ");\n";
-  // A kept DSPVector's slot n is read and rewritten at sample n only: the quad's four slots are fetched together - and TWO QUADS
-  // AHEAD (round 5; they were written 14 quads ago). Fetched at the top of the quad that uses them, every quad of a feedback graph
-  // stood still for a memory round trip, behind the stores of the quad before (memory operations of a wavefront complete in issue
-  // order): 256 round trips per launch of 16 DSPVectors were the whole launch time of the plucked-string bank, whatever the ring
-  // layout.
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].region < 0)
+    // the next quad's address: one step on; from a vector's last quad to the next vector's first; the launch's last quad stays
+    if (PF) s << "      const bool lastQ = (q == 15), lastT = (t + 1 == a.T);\n";
+    for (int i = 0; i < g.nInputs; ++i)
       for (int l = 0; l < VL; ++l)
       {
-        const std::string nm = std::to_string(i) + sfx(l);
-        s << "      float fbv" << nm << "[4];\n#pragma unroll\n      for (int kk = 0; kk < 4; ++kk)\n      {\n        fbv" << nm << "[kk] = fbn" << nm << "[kk];\n        fbn" << nm
-            << "[kk] = fbm" << nm << "[kk];\n        fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g->nodes[i].sOff) + " + ((q + 2) & 15) * 4 + kk", l) << ");\n      }\n";
+        s << "      const f32x4 xin" << i << sfx(l) << " = nx" << i << sfx(l) << ";\n      pf" << i << sfx(l) << " += lastQ ? (lastT ? (size_t)0 : a.in[" << i
+          << "].strideT - 15 * a.in[" << i << "].strideQ) : a.in[" << i << "].strideQ;\n      nx" << i << sfx(l) << " = __builtin_nontemporal_load(pf" << i << sfx(l) << ");\n";
       }
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_PROC && (g->nodes[i].kind == MLGPU_PROC_LINEAR_GLIDE || g->nodes[i].kind == MLGPU_PROC_HALF_BAND_BUFFERED))
-      for (int l = 0; l < VL; ++l) s << "      p" << i << sfx(l) << ".begin_quad(q);\n";
-  s << "#pragma unroll\n      for (int k = 0; k < 4; ++k)\n      {\n";
-  {
-    // Rate regions are emitted in place, recursively. A context = where we are in the tree of regions: the phase letters
-    // that name its values, the sample index inside the current function's own DSPVector, and that function's vector count.
-    struct Ctx
-    {
-      std::string sfx, idx, vec, indent;
-    };
-    auto name = [&](int j, const std::string& ph, int l) { return "n" + std::to_string(j) + ph + sfx(l); };
-    auto isInside = [&](int r, int ancestor) {  // r == ancestor or nested somewhere inside it
-      for (; r >= 0; r = g->regions[(size_t)r].parent)
-        if (r == ancestor) return true;
-      return false;
-    };
-    auto childUnder = [&](int r, int ancestor) {  // the region directly under `ancestor` that contains r
-      while (g->regions[(size_t)r].parent != ancestor) r = g->regions[(size_t)r].parent;
-      return r;
-    };
-    std::function<void(int, const Ctx&)> emitNodes;   // the nodes of region r (-1: the outer graph) in context c
-    std::function<void(int, const Ctx&)> emitRegion;  // region r, entered from context c of its parent
-    // ring layout 0: where a delay node's read goes - right after the last audio-rate node its delay time needs (-1: at the sample's top)
-    auto emitPre = [&](size_t dn, const Ctx& c) {
-      const Node& m = g->nodes[dn];
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      for (int l = 0; l < VL; ++l) s << "      f32x4 y" << o << sfx(l) << ";\n";
+    if (g.hasEventRows)
       for (int l = 0; l < VL; ++l)
-      {
-        s << c.indent << "p" << dn << sfx(l) << (m.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? ".pre_i(" + c.idx : ".pre(");
-        for (size_t a = 1; a < m.in.size(); ++a) s << ((a > 1 || m.kind == MLGPU_PROC_PITCHBENDABLE_DELAY) ? ", " : "") << name(m.in[a], "", l);
-        s << ");\n";
-      }
-    };
-    // The nodes a delay time is computed from go to the top of the sample with the reads behind them, where nothing of this sample
-    // has been stored yet: plain nodes only (operators, inputs, one-vector feedback values, processors without rings - each keeps its
-    // own state, so their order among independent nodes is free), and only those whose inputs are such nodes themselves.
-    std::vector<char> movable(g->nodes.size(), 0), hoisted(g->nodes.size(), 0);
-    std::vector<size_t> batch;  // the delay nodes whose reads are issued at the top, in issue order
-    if (g->earlyRows)
-    {
-      for (size_t j = 0; j < g->nodes.size(); ++j)
-      {
-        const Node& m = g->nodes[j];
-        if (m.rate != RATE_AUDIO)
-        {
-          movable[j] = 1;  // (a value per voice or per DSPVector: there before the sample loop)
-          continue;
-        }
-        bool ok = m.region < 0 && m.role == ROLE_NONE && (m.type == NODE_OP || m.type == NODE_INPUT || m.type == NODE_FEEDBACK || m.type == NODE_VOP || (m.type == NODE_PROC && !mlgpu_proc_rings(m.kind) && streamLockSawOf(g, j) < 0));
-        if (m.type != NODE_FEEDBACK)
-          for (int in : m.in) ok = ok && movable[(size_t)in];
-        movable[j] = ok;
-      }
-      std::function<void(int)> want = [&](int j) {
-        if (hoisted[(size_t)j] || g->nodes[(size_t)j].rate != RATE_AUDIO) return;
-        hoisted[(size_t)j] = 1;
-        if (g->nodes[(size_t)j].type != NODE_FEEDBACK)
-          for (int in : g->nodes[(size_t)j].in) want(in);
-      };
-      for (size_t dn = 0; dn < g->nodes.size(); ++dn)
-      {
-        const Node& m = g->nodes[dn];
-        if (!earlyRingReads(g, m)) continue;
-        bool all = true;
-        for (size_t a = 1; a < m.in.size(); ++a) all = all && movable[(size_t)m.in[a]];
-        if (!all) continue;
-        for (size_t a = 1; a < m.in.size(); ++a) want(m.in[a]);
-        batch.push_back(dn);
-      }
-      // what is still in flight behind a node's loads when they have landed: at least the loads of the batch issued after them
-      int after = 0;
-      for (size_t b = batch.size(); b-- > 0;)
-      {
-        g->nodes[batch[b]].earlyPending = after;
-        after += g->nodes[batch[b]].kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? 2 : 1;
-      }
-    }
-    auto inBatch = [&](size_t dn) { return std::find(batch.begin(), batch.end(), dn) != batch.end(); };
-    auto emitPlain = [&](size_t j, const Ctx& c) {
-      const Node& m = g->nodes[j];
-      for (int l = 0; l < VL; ++l)
-        s << c.indent << "const float " << name((int)j, c.sfx, l) << " = " << nodeExpr(g, j, l, c.sfx, c.idx) << ";"
-          << (l == 0 && !m.name.empty() ? "  // " + m.name : std::string()) << "\n";
-    };
-    emitNodes = [&](int r, const Ctx& c) {
-      std::vector<char> entered(g->regions.size(), 0);
-      if (r < 0 && g->earlyRows)
-      {
-        for (size_t j = 0; j < g->nodes.size(); ++j)
-          if (hoisted[j]) emitPlain(j, c);
-        for (size_t dn : batch) emitPre(dn, c);
-      }
-      for (size_t j = 0; j < g->nodes.size(); ++j)
-      {
-        const Node& m = g->nodes[j];
-        if (m.rate != RATE_AUDIO) continue;
-        if (r < 0 && hoisted[j]) continue;  // at the top of the sample
-        if (m.region != r)
-        {
-          // the first node of a region nested directly here: the whole region goes in at this point
-          if (m.region >= 0 && (r < 0 || isInside(m.region, r)) && m.region != r)
-          {
-            const int child = childUnder(m.region, r);
-            if (!entered[(size_t)child])
-            {
-              entered[(size_t)child] = 1;
-              emitRegion(child, c);
-            }
-          }
-          continue;
-        }
-        if (m.role == ROLE_REGION_IN) continue;  // made by emitRegion
-        if (m.role == ROLE_REGION_OUT)
-        {
-          const Region& R = g->regions[(size_t)m.slot];
-          if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X) continue;  // read before the region's block, see emitRegion
-          for (int l = 0; l < VL; ++l)
-            s << c.indent << "const float " << name((int)j, c.sfx, l) << " = p" << j << sfx(l) << ".down(" << name(m.in[0], c.sfx + "a", l) << ", "
-              << name(m.in[0], c.sfx + "b", l) << ");" << (l == 0 && !m.name.empty() ? "  // " + m.name : std::string()) << "\n";
-          continue;
-        }
-        if (r < 0 && streamLockSawOf(g, j) >= 0)
-        {
-          // a SawGen / PulseGen pair on one streamed frequency: both values are made where the first of the two stands
-          const int si = streamLockSawOf(g, j), pj = streamLockPulseOf(g, (size_t)si);
-          if ((int)j == std::min(si, pj))
-          {
-            const Node &sn = g->nodes[(size_t)si], &pn = g->nodes[(size_t)pj];
-            for (int l = 0; l < VL; ++l)
-            {
-              const std::string freq = "n" + std::to_string(sn.in[0]) + sfx(l);
-              const std::string width = pn.in.size() == 2 ? "n" + std::to_string(pn.in[1]) + sfx(l) : "p" + std::to_string(pj) + sfx(l) + ".width";
-              s << c.indent << "float sl" << si << "s" << sfx(l) << ", sl" << si << "p" << sfx(l) << ";\n";
-              // (the usual case - counters equal, widths regular - behind ONE wave-uniform test per sample)
-              s << c.indent << "if (slocked" << si << " && !oddw" << pj << ") step_locked_stream<true>(p" << si << sfx(l) << ", p" << pj << sfx(l) << ", " << freq << ", " << width << ", sl" << si
-                << "s" << sfx(l) << ", sl" << si << "p" << sfx(l) << ");\n";
-              s << c.indent << "else if (slocked" << si << ") step_locked_stream<false>(p" << si << sfx(l) << ", p" << pj << sfx(l) << ", " << freq << ", " << width << ", sl" << si << "s" << sfx(l)
-                << ", sl" << si << "p" << sfx(l) << ");\n";
-              s << c.indent << "else\n" << c.indent << "{\n";
-              s << c.indent << "  sl" << si << "s" << sfx(l) << " = p" << si << sfx(l) << ".next(" << freq << ");\n";
-              s << c.indent << "  sl" << si << "p" << sfx(l) << " = p" << pj << sfx(l) << ".next_sw(" << freq << (pn.in.size() == 2 ? ", " + width : std::string()) << ", oddw" << pj << ");\n";
-              s << c.indent << "}\n";
-            }
-          }
-        }
-        if (r < 0 && earlyRingReads(g, m) && !inBatch(j)) emitPre(j, c);  // (a delay time made of this sample's own signal: read and value together)
-        emitPlain(j, c);
-      }
-      if (r < 0) return;
-      // fn's own one-vector feedback (slot = the sample index inside fn's DSPVector), then the end of fn's DSPVector
-      for (size_t j = 0; j < g->nodes.size(); ++j)
-        if (g->nodes[j].region == r && g->nodes[j].type == NODE_FEEDBACK && g->nodes[j].fbSource >= 0)
-          for (int l = 0; l < VL; ++l)
-            s << c.indent << stateRef(std::to_string(g->nodes[j].sOff) + " + " + c.idx, l) << " = f2u(" << name(g->nodes[j].fbSource, c.sfx, l)
-              << ");\n";
-      bool any = false;
-      for (size_t j = 0; j < g->nodes.size(); ++j)
-      {
-        const Node& m = g->nodes[j];
-        if (m.type != NODE_PROC || m.region != r || m.role != ROLE_NONE) continue;
-        if (!any) s << c.indent << "if (" << c.idx << " == 63)\n" << c.indent << "{\n";
-        any = true;
-        for (int l = 0; l < VL; ++l) s << c.indent << "  p" << j << sfx(l) << ".end_vector();\n";
-      }
-      if (any) s << c.indent << "}\n";
-    };
-    emitRegion = [&](int r, const Ctx& c) {
-      const Region& R = g->regions[(size_t)r];
-      if (R.kind == MLGPU_REGION_UPSAMPLE_2X)
-      {
-        // fn on the two samples the HalfBandFilters make of this sample (upsampleFirstHalf / SecondHalf in stream order)
-        for (int phase = 0; phase < 2; ++phase)
-        {
-          const std::string ph = phase ? "b" : "a";
-          Ctx cc;
-          cc.sfx = c.sfx + ph;
-          cc.idx = "((2 * (" + c.idx + ") + " + std::to_string(phase) + ") & 63)";
-          cc.vec = "(2 * (" + c.vec + ") + ((2 * (" + c.idx + ") + " + std::to_string(phase) + ") >> 6))";
-          cc.indent = c.indent;
-          for (int in : R.ins)
-            for (int l = 0; l < VL; ++l)
-              s << c.indent << "const float " << name(in, cc.sfx, l) << " = p" << in << sfx(l) << ".up_" << ph << "("
-                << name(g->nodes[(size_t)in].in[0], c.sfx.substr(0, (size_t)upDepth(g, g->nodes[(size_t)g->nodes[(size_t)in].in[0]].region)), l) << ");\n";
-          emitNodes(r, cc);
-        }
-      }
-      else
-      {
-        // the region's output is what its upsampler made one DSPVector (of the parent's) ago; fn runs on the parent's odd samples
-        const bool top = (R.parent < 0);
+        s << "      mlev::CtlVoice::f32x4e evP" << sfx(l) << ", evG" << sfx(l) << ";\n      ev" << sfx(l) << ".quad(t, q, evP" << sfx(l) << ", evG" << sfx(l) << ");\n";
+    // A kept DSPVector's slot n is read and rewritten at sample n only: the quad's four slots are fetched together - and TWO QUADS
+    // AHEAD (round 5; they were written 14 quads ago). Fetched at the top of the quad that uses them, every quad of a feedback graph
+    // stood still for a memory round trip, behind the stores of the quad before (memory operations of a wavefront complete in issue
+    // order): 256 round trips per launch of 16 DSPVectors were the whole launch time of the plucked-string bank, whatever the ring
+    // layout.
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_FEEDBACK && g.nodes[i].region < 0)
         for (int l = 0; l < VL; ++l)
-          s << c.indent << "const float " << name(R.out, c.sfx, l) << " = p" << R.out << sfx(l) << (top ? ".delayed(" : ".delayedAt(") << c.idx << ");\n";
-        s << c.indent << "if ((" << c.idx << ") & 1)\n" << c.indent << "{\n";
-        Ctx cc;
-        cc.sfx = c.sfx;
-        cc.idx = "((((" + c.idx + ") - 1) >> 1) + 32 * (int)((" + c.vec + ") & 1))";
-        cc.vec = "((" + c.vec + ") >> 1)";
-        cc.indent = c.indent + "  ";
-        for (int in : R.ins)
-          for (int l = 0; l < VL; ++l)
-            s << cc.indent << "const float " << name(in, cc.sfx, l) << " = p" << in << sfx(l) << ".down(prev" << in << sfx(l) << ", "
-              << name(g->nodes[(size_t)in].in[0], c.sfx.substr(0, (size_t)upDepth(g, g->nodes[(size_t)g->nodes[(size_t)in].in[0]].region)), l) << ");\n";
-        emitNodes(r, cc);
-        for (int l = 0; l < VL; ++l) s << cc.indent << "p" << R.out << sfx(l) << ".push(" << c.idx << ", " << name(R.result, cc.sfx, l) << ");\n";
-        s << c.indent << "}\n";
-        for (int in : R.ins)
-          for (int l = 0; l < VL; ++l)
-            s << c.indent << "prev" << in << sfx(l) << " = "
-              << name(g->nodes[(size_t)in].in[0], c.sfx.substr(0, (size_t)upDepth(g, g->nodes[(size_t)g->nodes[(size_t)in].in[0]].region)), l) << ";\n";
-      }
-    };
-    Ctx outer;
-    outer.idx = "(q * 4 + k)";
-    outer.vec = "(a.t0 + t)";
-    outer.indent = "        ";
-    emitNodes(-1, outer);
+        {
+          const std::string nm = std::to_string(i) + sfx(l);
+          s << "      float fbv" << nm << "[4];\n#pragma unroll\n      for (int kk = 0; kk < 4; ++kk)\n      {\n        fbv" << nm << "[kk] = fbn" << nm << "[kk];\n        fbn" << nm
+            << "[kk] = fbm" << nm << "[kk];\n        fbm" << nm << "[kk] = u2f(" << stateRef(std::to_string(g.nodes[i].sOff) + " + ((q + 2) & 15) * 4 + kk", l) << ");\n      }\n";
+        }
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_PROC && (g.nodes[i].kind == MLGPU_PROC_LINEAR_GLIDE || g.nodes[i].kind == MLGPU_PROC_HALF_BAND_BUFFERED))
+        for (int l = 0; l < VL; ++l) s << "      p" << i << sfx(l) << ".begin_quad(q);\n";
+    s << "#pragma unroll\n      for (int k = 0; k < 4; ++k)\n      {\n";
   }
-  for (size_t o = 0; o < g->outputs.size(); ++o)
+  // Rate regions are emitted in place, recursively. A context = where we are in the tree of regions: the phase letters
+  // that name its values, the sample index inside the current function's own DSPVector, and that function's vector count.
+  struct Ctx { std::string sfx, idx, vec, indent; };
+  bool isInside(int r, int ancestor) const  // r == ancestor or nested somewhere inside it
+  {
+    for (; r >= 0; r = g.regions[(size_t)r].parent)
+      if (r == ancestor) return true;
+    return false;
+  }
+  int childUnder(int r, int ancestor) const  // the region directly under `ancestor` that contains r
+  {
+    while (g.regions[(size_t)r].parent != ancestor) r = g.regions[(size_t)r].parent;
+    return r;
+  }
+  // the outer value a region input carries, in the phase of ITS region
+  std::string regionSource(int in, const Ctx& c, int l) const
+  {
+    const int src = g.nodes[(size_t)in].in[0];
+    return name(src, c.sfx.substr(0, (size_t)upDepth(&g, g.nodes[(size_t)src].region)), l);
+  }
+  // ring layout 0: where a delay node's read goes - right after the last audio-rate node its delay time needs (-1: at the sample's top)
+  void emitPre(size_t dn, const Ctx& c)
+  {
+    const Node& m = g.nodes[dn];
     for (int l = 0; l < VL; ++l)
     {
-      if (g->outputGroup[o] && !ldsSum(o)) s << "        y" << o << sfx(l) << "[k] = group_sum_in_order<" << g->outputGroup[o] << ">(n" << g->outputs[o] << sfx(l) << ");\n";
-      else s << "        y" << o << sfx(l) << "[k] = n" << g->outputs[o] << sfx(l) << ";\n";
+      s << c.indent << "p" << dn << sfx(l) << (m.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? ".pre_i(" + c.idx : ".pre(");
+      for (size_t a = 1; a < m.in.size(); ++a) s << ((a > 1 || m.kind == MLGPU_PROC_PITCHBENDABLE_DELAY) ? ", " : "") << name(m.in[a], "", l);
+      s << ");\n";
     }
-  // feedback: keep this sample's value for the same sample of the next DSPVector (its old value was read above)
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_FEEDBACK && g->nodes[i].fbSource >= 0 && g->nodes[i].region < 0)
-      for (int l = 0; l < VL; ++l)
-        s << "        " << stateRef(std::to_string(g->nodes[i].sOff) + " + q * 4 + k", l) << " = f2u(n" << g->nodes[i].fbSource << sfx(l) << ");\n";
-  s << "      }\n";
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    if (ldsSum(o))
-      s << "      group16_park(strip" << o << ", q & 3, y" << o << "_0);\n      if ((q & 3) == 3) group16_sum_store(strip" << o << ", out" << o << "_0 + t * a.out[" << o
-        << "].strideT + (q - 3) * a.out[" << o << "].strideQ, a.out[" << o << "].strideQ);\n";
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    if (g->outputMix[o])
-      s << "      mix64_park(mstrip" << o << ", q & 3, " << (partialWaves ? "(vr_0 < a.V) ? y" + std::to_string(o) + "_0 : f32x4{0.f, 0.f, 0.f, 0.f}" : "y" + std::to_string(o) + "_0")
-        << ");\n      if ((q & 3) == 3) mix64_sum_store(mstrip" << o << ", out" << o << "_0 + t * 64 + (q - 3) * 4);\n";
-  for (size_t o = 0; o < g->outputs.size(); ++o)
-    for (int l = 0; l < VL && !ldsSum(o) && !g->outputMix[o]; ++l)
-      s << "      " << (g->outputGroup[o] ? "if ((threadIdx.x & " + std::to_string(g->outputGroup[o] - 1) + ") == " + std::to_string(g->outputGroup[o] - 1) + ") " : std::string())
-        << "__builtin_nontemporal_store(y" << o << sfx(l) << ", out" << o << sfx(l) << " + t * a.out[" << o << "].strideT + q * a.out[" << o << "].strideQ);\n";
-  s << "    }\n";
-  if (oscTrips || ringTrips) s << "    }\n";
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_PROC && (g->nodes[i].region < 0 || g->nodes[i].role != ROLE_NONE))
-      for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".end_vector();\n";
-  if (g->hasEventRows)
-    for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".end_vector();\n";
-  s << "  }\n";
-  if (g->hasEventRows)
-    for (int l = 0; l < VL; ++l) s << "  ev" << sfx(l) << ".store();\n";
-  for (size_t i = 0; i < g->nodes.size(); ++i)
-    if (g->nodes[i].type == NODE_PROC)
-      for (int l = 0; l < VL; ++l) s << "  p" << i << sfx(l) << ".store(m" << i << sfx(l) << ");\n";
-  s << "}\n";
-  return s.str();
-}
-
-// Registers and scratch bytes per lane of the (only) kernel of a code object, read from its metadata note (msgpack: the key
-// string, then an unsigned integer).
-static bool codeObjectNumber(const std::vector<char>& code, const char* key, long& value)
-{
-  const size_t klen = strlen(key);
-  for (size_t i = 0; i + klen + 1 < code.size(); ++i)
-  {
-    if (memcmp(code.data() + i, key, klen) != 0) continue;
-    const unsigned char* p = (const unsigned char*)code.data() + i + klen;
-    const size_t left = code.size() - (i + klen);
-    if (p[0] <= 0x7f) { value = p[0]; return true; }
-    if (p[0] == 0xcc && left >= 2) { value = p[1]; return true; }
-    if (p[0] == 0xcd && left >= 3) { value = (p[1] << 8) | p[2]; return true; }
-    if (p[0] == 0xce && left >= 5) { value = ((long)p[1] << 24) | (p[2] << 16) | (p[3] << 8) | p[4]; return true; }
   }
-  return false;
+  // a SawGen / PulseGen pair on one streamed frequency: both values are made where the first of the two stands
+  void streamLockPair(int si, const Ctx& c)
+  {
+    const int pj = streamLockPulseOf(&g, (size_t)si);
+    const Node &sn = g.nodes[(size_t)si], &pn = g.nodes[(size_t)pj];
+    for (int l = 0; l < VL; ++l)
+    {
+      const std::string freq = name(sn.in[0], "", l), w = width((size_t)pj, l);
+      s << c.indent << "float sl" << si << "s" << sfx(l) << ", sl" << si << "p" << sfx(l) << ";\n";
+      // (the usual case - counters equal, widths regular - behind ONE wave-uniform test per sample)
+      s << c.indent << "if (slocked" << si << " && !oddw" << pj << ") step_locked_stream<true>(p" << si << sfx(l) << ", p" << pj << sfx(l) << ", " << freq << ", " << w << ", sl" << si
+        << "s" << sfx(l) << ", sl" << si << "p" << sfx(l) << ");\n";
+      s << c.indent << "else if (slocked" << si << ") step_locked_stream<false>(p" << si << sfx(l) << ", p" << pj << sfx(l) << ", " << freq << ", " << w << ", sl" << si << "s" << sfx(l)
+        << ", sl" << si << "p" << sfx(l) << ");\n";
+      s << c.indent << "else\n" << c.indent << "{\n";
+      s << c.indent << "  sl" << si << "s" << sfx(l) << " = p" << si << sfx(l) << ".next(" << freq << ");\n";
+      s << c.indent << "  sl" << si << "p" << sfx(l) << " = p" << pj << sfx(l) << ".next_sw(" << freq << (pn.in.size() == 2 ? ", " + w : std::string()) << ", oddw" << pj << ");\n";
+      s << c.indent << "}\n";
+    }
+  }
+  // the nodes of region r (-1: the outer graph) in context c
+  void emitNodes(int r, const Ctx& c)
+  {
+    std::vector<char> entered(g.regions.size(), 0);
+    if (r < 0 && g.earlyRows)
+    {
+      for (size_t j = 0; j < g.nodes.size(); ++j)
+        if (g.nodes[j].earlyHoisted) value(j, c.indent, c.sfx, c.idx);
+      for (size_t dn = 0; dn < g.nodes.size(); ++dn)
+        if (g.nodes[dn].earlyTop) emitPre(dn, c);
+    }
+    for (size_t j = 0; j < g.nodes.size(); ++j)
+    {
+      const Node& m = g.nodes[j];
+      if (m.rate != RATE_AUDIO) continue;
+      if (r < 0 && g.earlyRows && m.earlyHoisted) continue;  // at the top of the sample
+      if (m.region != r)
+      {
+        // the first node of a region nested directly here: the whole region goes in at this point
+        if (m.region >= 0 && (r < 0 || isInside(m.region, r)))
+        {
+          const int child = childUnder(m.region, r);
+          if (!entered[(size_t)child])
+          {
+            entered[(size_t)child] = 1;
+            emitRegion(child, c);
+          }
+        }
+        continue;
+      }
+      if (m.role == ROLE_REGION_IN) continue;  // made by emitRegion
+      if (m.role == ROLE_REGION_OUT)
+      {
+        const Region& R = g.regions[(size_t)m.slot];
+        if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X) continue;  // read before the region's block, see emitRegion
+        for (int l = 0; l < VL; ++l)
+          s << c.indent << "const float " << name((int)j, c.sfx, l) << " = p" << j << sfx(l) << ".down(" << name(m.in[0], c.sfx + "a", l) << ", "
+            << name(m.in[0], c.sfx + "b", l) << ");" << (l == 0 && !m.name.empty() ? "  // " + m.name : std::string()) << "\n";
+        continue;
+      }
+      if (r < 0 && streamLockSawOf(&g, j) >= 0)
+      {
+        const int si = streamLockSawOf(&g, j);
+        if ((int)j == std::min(si, streamLockPulseOf(&g, (size_t)si))) streamLockPair(si, c);
+      }
+      if (r < 0 && earlyRingReads(&g, m) && !m.earlyTop) emitPre(j, c);  // (a delay time made of this sample's own signal: read and value together)
+      value(j, c.indent, c.sfx, c.idx);
+    }
+    if (r < 0) return;
+    // fn's own one-vector feedback (slot = the sample index inside fn's DSPVector), then the end of fn's DSPVector
+    for (size_t j = 0; j < g.nodes.size(); ++j)
+      if (g.nodes[j].region == r && g.nodes[j].type == NODE_FEEDBACK && g.nodes[j].fbSource >= 0)
+        for (int l = 0; l < VL; ++l)
+          s << c.indent << stateRef(std::to_string(g.nodes[j].sOff) + " + " + c.idx, l) << " = f2u(" << name(g.nodes[j].fbSource, c.sfx, l) << ");\n";
+    bool any = false;
+    for (size_t j = 0; j < g.nodes.size(); ++j)
+    {
+      const Node& m = g.nodes[j];
+      if (m.type != NODE_PROC || m.region != r || m.role != ROLE_NONE) continue;
+      if (!any) s << c.indent << "if (" << c.idx << " == 63)\n" << c.indent << "{\n";
+      any = true;
+      for (int l = 0; l < VL; ++l) s << c.indent << "  p" << j << sfx(l) << ".end_vector();\n";
+    }
+    if (any) s << c.indent << "}\n";
+  }
+  // region r, entered from context c of its parent
+  void emitRegion(int r, const Ctx& c)
+  {
+    const Region& R = g.regions[(size_t)r];
+    if (R.kind == MLGPU_REGION_UPSAMPLE_2X)
+    {
+      // fn on the two samples the HalfBandFilters make of this sample (upsampleFirstHalf / SecondHalf in stream order)
+      for (int phase = 0; phase < 2; ++phase)
+      {
+        const std::string ph = phase ? "b" : "a";
+        const Ctx cc{c.sfx + ph, "((2 * (" + c.idx + ") + " + std::to_string(phase) + ") & 63)",
+                     "(2 * (" + c.vec + ") + ((2 * (" + c.idx + ") + " + std::to_string(phase) + ") >> 6))", c.indent};
+        for (int in : R.ins)
+          for (int l = 0; l < VL; ++l) s << c.indent << "const float " << name(in, cc.sfx, l) << " = p" << in << sfx(l) << ".up_" << ph << "(" << regionSource(in, c, l) << ");\n";
+        emitNodes(r, cc);
+      }
+      return;
+    }
+    // the region's output is what its upsampler made one DSPVector (of the parent's) ago; fn runs on the parent's odd samples
+    const bool top = (R.parent < 0);
+    for (int l = 0; l < VL; ++l)
+      s << c.indent << "const float " << name(R.out, c.sfx, l) << " = p" << R.out << sfx(l) << (top ? ".delayed(" : ".delayedAt(") << c.idx << ");\n";
+    s << c.indent << "if ((" << c.idx << ") & 1)\n" << c.indent << "{\n";
+    const Ctx cc{c.sfx, "((((" + c.idx + ") - 1) >> 1) + 32 * (int)((" + c.vec + ") & 1))", "((" + c.vec + ") >> 1)", c.indent + "  "};
+    for (int in : R.ins)
+      for (int l = 0; l < VL; ++l) s << cc.indent << "const float " << name(in, cc.sfx, l) << " = p" << in << sfx(l) << ".down(prev" << in << sfx(l) << ", " << regionSource(in, c, l) << ");\n";
+    emitNodes(r, cc);
+    for (int l = 0; l < VL; ++l) s << cc.indent << "p" << R.out << sfx(l) << ".push(" << c.idx << ", " << name(R.result, cc.sfx, l) << ");\n";
+    s << c.indent << "}\n";
+    for (int in : R.ins)
+      for (int l = 0; l < VL; ++l) s << c.indent << "prev" << in << sfx(l) << " = " << regionSource(in, c, l) << ";\n";
+  }
+  // one sample of every voice of the lane: the graph, the outputs' values, the feedback values kept for the next DSPVector
+  void sampleBody()
+  {
+    emitNodes(-1, Ctx{"", "(q * 4 + k)", "(a.t0 + t)", "        "});
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      for (int l = 0; l < VL; ++l)
+      {
+        if (g.outputGroup[o] && !ldsSum(o)) s << "        y" << o << sfx(l) << "[k] = group_sum_in_order<" << g.outputGroup[o] << ">(n" << g.outputs[o] << sfx(l) << ");\n";
+        else s << "        y" << o << sfx(l) << "[k] = n" << g.outputs[o] << sfx(l) << ";\n";
+      }
+    // feedback: keep this sample's value for the same sample of the next DSPVector (its old value was read above)
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_FEEDBACK && g.nodes[i].fbSource >= 0 && g.nodes[i].region < 0)
+        for (int l = 0; l < VL; ++l)
+          s << "        " << stateRef(std::to_string(g.nodes[i].sOff) + " + q * 4 + k", l) << " = f2u(n" << g.nodes[i].fbSource << sfx(l) << ");\n";
+    s << "      }\n";
+  }
+  // the quad's outputs: group sums and mixdowns through LDS, every other output straight to memory
+  void outputStores()
+  {
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (ldsSum(o))
+        s << "      group16_park(strip" << o << ", q & 3, y" << o << "_0);\n      if ((q & 3) == 3) group16_sum_store(strip" << o << ", out" << o << "_0 + t * a.out[" << o
+          << "].strideT + (q - 3) * a.out[" << o << "].strideQ, a.out[" << o << "].strideQ);\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (g.outputMix[o])
+        s << "      mix64_park(mstrip" << o << ", q & 3, " << (partialWaves ? "(vr_0 < a.V) ? y" + std::to_string(o) + "_0 : f32x4{0.f, 0.f, 0.f, 0.f}" : "y" + std::to_string(o) + "_0")
+          << ");\n      if ((q & 3) == 3) mix64_sum_store(mstrip" << o << ", out" << o << "_0 + t * 64 + (q - 3) * 4);\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+      for (int l = 0; l < VL && !ldsSum(o) && !g.outputMix[o]; ++l)
+        s << "      " << (g.outputGroup[o] ? "if ((threadIdx.x & " + std::to_string(g.outputGroup[o] - 1) + ") == " + std::to_string(g.outputGroup[o] - 1) + ") " : std::string())
+          << "__builtin_nontemporal_store(y" << o << sfx(l) << ", out" << o << sfx(l) << " + t * a.out[" << o << "].strideT + q * a.out[" << o << "].strideQ);\n";
+    s << "    }\n";
+    if (oscTrips || ringTrips) s << "    }\n";
+  }
+  // the end of every DSPVector, then the state stored back
+  void epilogue()
+  {
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_PROC && (g.nodes[i].region < 0 || g.nodes[i].role != ROLE_NONE))
+        for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".end_vector();\n";
+    if (g.hasEventRows)
+      for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".end_vector();\n";
+    s << "  }\n";
+    if (g.hasEventRows)
+      for (int l = 0; l < VL; ++l) s << "  ev" << sfx(l) << ".store();\n";
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+      if (g.nodes[i].type == NODE_PROC)
+        for (int l = 0; l < VL; ++l) s << "  p" << i << sfx(l) << ".store(m" << i << sfx(l) << ");\n";
+    s << "}\n";
+  }
+};
+
+std::string generateGraphSource(const mlgpu_graph& g, const KernelForm& form)
+{
+  GraphEmitter e(g, form);
+  e.header();
+  e.sharedMemory();
+  e.voiceSetup();
+  e.oscillatorTests();
+  e.outputsAndPrefetch();
+  e.vectorHead();
+  e.sampleBody();
+  e.outputStores();
+  e.epilogue();
+  return e.s.str();
 }
 
-// Source + code object of the graph kernel for `vl` voices per lane, with the register budget chosen: a voice bank is launched
+// Source + code object of the graph kernel of `form`, with the register budget chosen: a voice bank is launched
 // as whole blocks of four wavefronts, one per SIMD, and a big bank is a few blocks per CU - so a kernel that needs more than
 // 128 VGPRs (three, two or one wavefront per SIMD) runs its blocks in rounds where one that fits 128 runs them all at once. If
 // the bank is big enough for that to matter (65 536 voices: a block per CU) and the kernel is above 128, it is generated again
@@ -1473,24 +1056,23 @@ static bool codeObjectNumber(const std::vector<char>& code, const char* key, lon
 // 128 + 156 bytes of scratch per lane, 1.82 -> 1.46 ms; the voice with its EventsToSignals rows inside: 259 -> 128 + 528 bytes,
 // 3.13 -> 1.56 ms, where bounds of two and three wavefronts give 1.96 and 1.85). The test hook MLGPU_GRAPH_MIN_WAVES=0 / N
 // overrides (g->minWavesHook).
-static bool generateBudgeted(mlgpu_graph* g, int vl, std::string& source, std::vector<char>& code, std::string& log)
+static bool generateBudgeted(const mlgpu_graph* g, KernelForm form, std::string& source, std::vector<char>& code, std::string& log)
 {
-  g->minWaves = std::max(0, g->minWavesHook);
-  source = generateGraphSource(g, vl);
-  if (!getCode(source, code, log)) return false;
+  form.minWaves = std::max(0, g->minWavesHook);
+  source = generateGraphSource(*g, form);
+  if (!mlgpu_jit_code(source, code, log)) return false;
   long vgprs = 0;
-  if (g->minWavesHook >= 0 || (g->windowedRings && g->totalRings) || g->V < 65536 || !codeObjectNumber(code, ".vgpr_count", vgprs) || vgprs <= 128) return true;
+  if (g->minWavesHook >= 0 || (g->rings != RingLayout::ROWS && g->totalRings) || g->V < 65536 || !mlgpu_jit_code_number(code, ".vgpr_count", vgprs) || vgprs <= 128) return true;
   // the tightest bound whose build spills moderately: four wavefronts per SIMD, else three, else two
   for (int waves = 4; waves >= 2; --waves)
   {
     if (((vgprs + 7) & ~7L) * waves <= 512) break;  // the unbounded kernel already allows that many (registers come in blocks of 8 of a SIMD's 512)
-    g->minWaves = waves;
-    const std::string bounded = generateGraphSource(g, vl);
-    g->minWaves = 0;
+    form.minWaves = waves;
+    const std::string bounded = generateGraphSource(*g, form);
     std::vector<char> boundedCode;
     std::string boundedLog;
     long scratch = 0;
-    if (getCode(bounded, boundedCode, boundedLog) && codeObjectNumber(boundedCode, ".private_segment_fixed_size", scratch) && scratch <= 640)
+    if (mlgpu_jit_code(bounded, boundedCode, boundedLog) && mlgpu_jit_code_number(boundedCode, ".private_segment_fixed_size", scratch) && scratch <= 640)
     {
       source = bounded;
       code.swap(boundedCode);
@@ -1542,11 +1124,8 @@ int addNode(mlgpu_graph* g, Node&& n)
 // a processor node with its coefficient and state slots (the checks of mlgpu_graph_add_proc are the caller's)
 int addProcNode(mlgpu_graph* g, int kind, const int* inputs, int nIn, const char* name, int role = ROLE_NONE, int region = -1, int slot = 0)
 {
-  Node n;
-  n.type = NODE_PROC;
-  n.kind = kind;
+  Node n(NODE_PROC, kind, name);
   if (nIn) n.in.assign(inputs, inputs + nIn);
-  n.name = name ? name : "";
   n.nc = mlgpu_proc_nc(kind);
   n.ns = mlgpu_proc_ns(kind);
   n.cOff = g->NC;
@@ -1573,6 +1152,14 @@ int checkNode(mlgpu_graph* g, int node, int type)
   if (g->nodes[node].type != type) return gfail(g, MLGPU_ERR_INVALID, "node has the wrong type for this call");
   return MLGPU_OK;
 }
+// a call that changes the graph's description: only before mlgpu_graph_compile
+int checkEditable(mlgpu_graph* g)
+{
+  if (!g) return MLGPU_ERR_INVALID;
+  if (g->job) return MLGPU_ERR_BUSY;
+  if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+  return MLGPU_OK;
+}
 // nodes that own state words: processors and feedback nodes (their stored DSPVector, 64 words)
 int checkStateNode(mlgpu_graph* g, int node)
 {
@@ -1584,164 +1171,22 @@ int checkStateNode(mlgpu_graph* g, int node)
 }
 }  // namespace
 
-// ---- fused kernels for processor chains without an ahead-of-time instantiation -------------------
-// Generates `chain_kernel_body<Chain<kinds...>, HAS_SIGNAL>` wrappers; used by mlgpu_bank_create.
-static std::string chainSource(const int32_t* kinds, int n, bool strictSvf = false)
-{
-  std::ostringstream s;
-  s << "// generated by libmlgpu graph.hip (chain)\n" << (strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\nusing namespace mldev;\n";
-  // a plain cascade of 2, 4 or 8 equal SVF sections keeps its stage-skewed form (one lane per channel; chains.hip picks wider
-  // forms by bank size for the ahead-of-time kernels): strict mode must not cost config 4 its kernel
-  bool cascade = (n == 2 || n == 4 || n == 8) && (kinds[0] == MLGPU_PROC_LOPASS || kinds[0] == MLGPU_PROC_HIPASS || kinds[0] == MLGPU_PROC_BANDPASS);
-  for (int i = 1; i < n; ++i) cascade = cascade && kinds[i] == kinds[0];
-  if (cascade)
-  {
-    for (int sig = 1; sig >= 0; --sig)
-      s << "extern \"C\" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mlgpu_chain_" << (sig ? "signal" : "const")
-        << "(const ChainArgs a) { cascade_lanes_body<" << kinds[0] << ", " << n << ", 1, 8, " << (sig ? "true" : "false") << ">(a); }\n";
-    return s.str();
-  }
-  s << "using CH = Chain<";
-  for (int i = 0; i < n; ++i) s << (i ? ", " : "") << kinds[i];
-  s << ">;\n"
-       "extern \"C\" __global__ __launch_bounds__(256) void mlgpu_chain_signal(const ChainArgs a) { chain_kernel_body<CH, true>(a); }\n"
-       "extern \"C\" __global__ __launch_bounds__(256) void mlgpu_chain_const(const ChainArgs a) { chain_kernel_body<CH, false>(a); }\n";
-  return s.str();
-}
-
-bool mlgpu_jit_chain(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log)
-{
-  const std::string src = chainSource(kinds, n, e->strictSvf);
-  CompiledModule* cm = compileAndLoad(e->device, src, log);
-  if (!cm) return false;
-  *fnSignal = (void*)getFunction(cm, "mlgpu_chain_signal", log);
-  *fnConst = (void*)getFunction(cm, "mlgpu_chain_const", log);
-  return *fnSignal && *fnConst;
-}
-
-hipError_t mlgpu_jit_chain_launch(void* fn, const ChainArgs& a, hipStream_t stream) { return launchJit((hipFunction_t)fn, a, a.V, stream); }
-
-// ... and the form of a chain that sums its voices inside the kernel (chain_kernel_body<CH, HAS_SIGNAL, true>, mlgpu_bank_prepare_mixdown):
-// generated on request for the chains chains.hip has no ahead-of-time instantiation of
-bool mlgpu_jit_chain_mix(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log)
-{
-  std::ostringstream s;
-  s << "// generated by libmlgpu graph.hip (chain, voices summed in the kernel)\n" << (e->strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "")
-    << "#include \"mldsp_kernels.hpp\"\nusing namespace mldev;\nusing CH = Chain<";
-  for (int i = 0; i < n; ++i) s << (i ? ", " : "") << kinds[i];
-  s << ">;\n"
-       "extern \"C\" __global__ __launch_bounds__(256) void mlgpu_chain_mix_signal(const ChainArgs a) { chain_kernel_body<CH, true, true>(a); }\n"
-       "extern \"C\" __global__ __launch_bounds__(256) void mlgpu_chain_mix_const(const ChainArgs a) { chain_kernel_body<CH, false, true>(a); }\n";
-  CompiledModule* cm = compileAndLoad(e->device, s.str(), log);
-  if (!cm) return false;
-  *fnSignal = (void*)getFunction(cm, "mlgpu_chain_mix_signal", log);
-  *fnConst = (void*)getFunction(cm, "mlgpu_chain_mix_const", log);
-  return *fnSignal && *fnConst;
-}
-
 extern "C"
 {
-  // Every generated kernel this process holds (compiled here or read from the disk cache), as one relocatable blob: what an
-  // installation WITHOUT hiprtc is given so that its graphs and chains find their code. Header: magic, the fingerprint of the device
-  // headers the kernels were generated from (a bundle of another build is refused: its kernels would be looked up by other sources
-  // anyway), count; then per kernel the generated source (the key) and the code object.
-  static const char kBundleMagic[8] = {'M', 'L', 'G', 'P', 'U', 'K', 'B', '1'};
-  int mlgpu_jit_cache_export(void* buffer, size_t capacity, size_t* needed)
-  {
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    const std::string fp = mlgpu_device_source_hash_str;
-    size_t total = sizeof(kBundleMagic) + 8 + fp.size() + 8;
-    for (const auto& kv : g_codeCache) total += 16 + kv.first.size() + kv.second.size();
-    if (needed) *needed = total;
-    if (!buffer) return MLGPU_OK;
-    if (capacity < total) return MLGPU_ERR_RANGE;
-    char* p = (char*)buffer;
-    auto put = [&p](const void* src, size_t n) {
-      memcpy(p, src, n);
-      p += n;
-    };
-    auto put64 = [&put](uint64_t v) { put(&v, 8); };
-    put(kBundleMagic, sizeof(kBundleMagic));
-    put64(fp.size());
-    put(fp.data(), fp.size());
-    put64(g_codeCache.size());
-    for (const auto& kv : g_codeCache)
-    {
-      put64(kv.first.size());
-      put64(kv.second.size());
-      put(kv.first.data(), kv.first.size());
-      put(kv.second.data(), kv.second.size());
-    }
-    return MLGPU_OK;
-  }
-  int mlgpu_jit_cache_import(const void* buffer, size_t size, size_t* kernels)
-  {
-    if (kernels) *kernels = 0;
-    if (!buffer) return MLGPU_ERR_INVALID;
-    const char *p = (const char*)buffer, *end = p + size;
-    auto get64 = [&p, end](uint64_t& v) {
-      if ((size_t)(end - p) < 8) return false;
-      memcpy(&v, p, 8);
-      p += 8;
-      return true;
-    };
-    if (size < sizeof(kBundleMagic) || memcmp(p, kBundleMagic, sizeof(kBundleMagic)) != 0) return MLGPU_ERR_INVALID;
-    p += sizeof(kBundleMagic);
-    uint64_t n = 0;
-    if (!get64(n) || (size_t)(end - p) < n) return MLGPU_ERR_INVALID;
-    if (std::string(p, (size_t)n) != mlgpu_device_source_hash_str) return MLGPU_ERR_UNSUPPORTED;  // kernels of another build of the device code
-    p += n;
-    uint64_t count = 0;
-    if (!get64(count)) return MLGPU_ERR_INVALID;
-    std::vector<std::pair<std::string, std::vector<char>>> items;
-    for (uint64_t i = 0; i < count; ++i)
-    {
-      uint64_t ns = 0, nc = 0;
-      if (!get64(ns) || !get64(nc) || (size_t)(end - p) < ns || (size_t)(end - p) - ns < nc) return MLGPU_ERR_INVALID;
-      if (nc < 4 || memcmp(p + ns, "\x7f" "ELF", 4) != 0) return MLGPU_ERR_INVALID;  // (what goes to the module loader is at least an ELF file)
-      items.emplace_back(std::string(p, (size_t)ns), std::vector<char>(p + ns, p + ns + nc));
-      p += ns + nc;
-    }
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    for (auto& it : items) g_codeCache[it.first] = std::move(it.second);
-    if (kernels) *kernels = items.size();
-    return MLGPU_OK;
-  }
-  // (tests) forget the kernels held in memory: the next request goes to the disk cache or the compiler again
-  int mlgpu_jit_cache_clear_memory(void)
-  {
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    g_codeCache.clear();
-    return MLGPU_OK;
-  }
-  // 1 where run-time compilation is there (libhiprtc.so can be loaded and MLGPU_HIPRTC is not "off"), else 0
-  int mlgpu_jit_compiler_available(void) { return hiprtc() ? 1 : 0; }
-
-  int mlgpu_jit_stats(uint64_t* compiles, uint64_t* diskHits, uint64_t* memoryHits, double* compileSeconds, double* diskLoadSeconds)
-  {
-    std::lock_guard<std::mutex> lock(g_codeMutex);
-    if (compiles) *compiles = g_jitStats.compiles;
-    if (diskHits) *diskHits = g_jitStats.diskHits;
-    if (memoryHits) *memoryHits = g_jitStats.memoryHits;
-    if (compileSeconds) *compileSeconds = g_jitStats.compileSeconds;
-    if (diskLoadSeconds) *diskLoadSeconds = g_jitStats.diskLoadSeconds;
-    return MLGPU_OK;
-  }
-
   int mlgpu_jit_selftest(char* logOut, size_t logLen)
   {
     std::string log, all;
     bool ok = true;
     // (1) a chain that has no ahead-of-time instantiation, including the LDS-table ImpulseGen
     const int32_t chain[] = {MLGPU_PROC_IMPULSE_GEN, MLGPU_PROC_LO_SHELF, MLGPU_PROC_ADSR, MLGPU_PROC_PEAK, MLGPU_PROC_GAIN};
-    ok = compileOnly(chainSource(chain, 5), log) && ok;
+    ok = mlgpu_jit_compile_only(mlgpu_jit_chain_source(chain, 5, false, false), log) && ok;
     all += log;
     // (1b) the strict-SVF forms: a generic chain and a plain cascade (which keeps its stage-skewed kernel)
     const int32_t svfChain[] = {MLGPU_PROC_SAW_GEN, MLGPU_PROC_BANDPASS, MLGPU_PROC_HI_SHELF, MLGPU_PROC_GAIN};
-    ok = compileOnly(chainSource(svfChain, 4, true), log) && ok;
+    ok = mlgpu_jit_compile_only(mlgpu_jit_chain_source(svfChain, 4, true, false), log) && ok;
     all += log;
     const int32_t casc[] = {MLGPU_PROC_HIPASS, MLGPU_PROC_HIPASS, MLGPU_PROC_HIPASS, MLGPU_PROC_HIPASS};
-    ok = compileOnly(chainSource(casc, 4, true), log) && ok;
+    ok = mlgpu_jit_compile_only(mlgpu_jit_chain_source(casc, 4, true, false), log) && ok;
     all += log;
     // (2) a graph touching every node type
     mlgpu_graph g;
@@ -1810,19 +1255,16 @@ extern "C"
     ok = (vca > 0) && (hs > 0) && (dm > 0) && (dml > 0) && (mlgpu_graph_add_output(&g, hs) == MLGPU_OK) && (mlgpu_graph_add_output(&g, dm) == MLGPU_OK) &&
          (mlgpu_graph_add_output(&g, dml) == MLGPU_OK) && ok;
     log.clear();
-    ok = compileOnly(generateGraphSource(&g), log) && ok;
+    ok = mlgpu_jit_compile_only(generateGraphSource(g, KernelForm{graphVoicesPerLane(&g), g.unrollQ, 0}), log) && ok;
     all += log;
     // (3) the same graph with per-voice rings behind LDS windows
-    g.windowedRings = true;
+    g.rings = RingLayout::WINDOWS;
     g.voicesPerLane = 1;
     g.totalRings = 20;  // the largest LDS footprint graph_compile accepts (160 KiB)
     log.clear();
-    ok = compileOnly(generateGraphSource(&g), log) && ok;
+    ok = mlgpu_jit_compile_only(generateGraphSource(g, KernelForm{graphVoicesPerLane(&g), g.unrollQ, 0}), log) && ok;
     all += log;
-    if (logOut && logLen)
-    {
-      snprintf(logOut, logLen, "%s", all.c_str());
-    }
+    if (logOut && logLen) snprintf(logOut, logLen, "%s", all.c_str());
     return ok ? MLGPU_OK : MLGPU_ERR_UNSUPPORTED;
   }
 
@@ -1877,10 +1319,7 @@ extern "C"
   {
     if (!g) return -MLGPU_ERR_INVALID;
     if (g->nInputs >= MLGPU_GRAPH_MAX_INPUTS) return -gfail(g, MLGPU_ERR_UNSUPPORTED, "too many graph inputs");
-    Node n;
-    n.type = NODE_INPUT;
-    n.kind = 0;
-    n.name = name ? name : "";
+    Node n(NODE_INPUT, 0, name);
     n.slot = g->nInputs;
     const int id = addNode(g, std::move(n));
     if (id >= 0) g->nInputs++;
@@ -1889,10 +1328,7 @@ extern "C"
   int mlgpu_graph_add_param(mlgpu_graph* g, const char* name)
   {
     if (!g) return -MLGPU_ERR_INVALID;
-    Node n;
-    n.type = NODE_PARAM;
-    n.kind = 0;
-    n.name = name ? name : "";
+    Node n(NODE_PARAM, 0, name);
     n.slot = g->nParams;
     const int id = addNode(g, std::move(n));
     if (id >= 0) g->nParams++;
@@ -1902,10 +1338,7 @@ extern "C"
   {
     if (!g) return -MLGPU_ERR_INVALID;
     if (g->nControls >= MLGPU_GRAPH_MAX_CONTROLS) return -gfail(g, MLGPU_ERR_UNSUPPORTED, "too many graph control inputs");
-    Node n;
-    n.type = NODE_CONTROL;
-    n.kind = 0;
-    n.name = name ? name : "";
+    Node n(NODE_CONTROL, 0, name);
     n.slot = g->nControls;
     const int id = addNode(g, std::move(n));
     if (id >= 0) g->nControls++;
@@ -1918,10 +1351,7 @@ extern "C"
     if (row != 0 && row != 1) return -gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_add_event_row: rows 0 (pitch) and 1 (gate) can be source nodes");
     for (const Node& m : g->nodes)
       if (m.type == NODE_EVENT_ROW && m.slot == row) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_event_row: this row is a node already");
-    Node n;
-    n.type = NODE_EVENT_ROW;
-    n.kind = 0;
-    n.name = name ? name : "";
+    Node n(NODE_EVENT_ROW, 0, name);
     n.slot = row;
     const int id = addNode(g, std::move(n));
     if (id >= 0) g->hasEventRows = true;
@@ -1952,32 +1382,23 @@ extern "C"
     for (int j = 0; j < nIn; ++j)
       if (inputs[j] < 0 || inputs[j] >= (int)g->nodes.size() || g->nodes[inputs[j]].rate > RATE_VECTOR)
         return -gfail(g, MLGPU_ERR_INVALID, "graph_add_vop: start / end are floats (a control, param or const node)");
-    Node n;
-    n.type = NODE_VOP;
-    n.kind = vop;
+    Node n(NODE_VOP, vop, name);
     if (nIn) n.in.assign(inputs, inputs + nIn);
-    n.name = name ? name : "";
     return addNode(g, std::move(n));
   }
   int mlgpu_graph_add_const_vector(mlgpu_graph* g, const float* values, const char* name)
   {
     if (!g) return -MLGPU_ERR_INVALID;
     if (!values) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_const_vector: 64 floats");
-    Node n;
-    n.type = NODE_VOP;
-    n.kind = MLGPU_VOP_TABLE;
+    Node n(NODE_VOP, MLGPU_VOP_TABLE, name);
     n.table.resize(MLGPU_FLOATS_PER_DSPVECTOR);
     memcpy(n.table.data(), values, sizeof(float) * MLGPU_FLOATS_PER_DSPVECTOR);
-    n.name = name ? name : "";
     return addNode(g, std::move(n));
   }
   int mlgpu_graph_add_feedback(mlgpu_graph* g, const char* name)
   {
     if (!g) return -MLGPU_ERR_INVALID;
-    Node n;
-    n.type = NODE_FEEDBACK;
-    n.kind = 0;
-    n.name = name ? name : "";
+    Node n(NODE_FEEDBACK, 0, name);
     n.ns = MLGPU_FLOATS_PER_DSPVECTOR;
     n.sOff = g->NS;
     const int id = addNode(g, std::move(n));
@@ -1988,7 +1409,6 @@ extern "C"
   {
     int st = checkNode(g, fbNode, NODE_FEEDBACK);
     if (st) return st;
-    if (g->job) return MLGPU_ERR_BUSY;
     if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
     if (valueNode < 0 || valueNode >= (int)g->nodes.size()) return gfail(g, MLGPU_ERR_RANGE, "graph_set_feedback: unknown value node");
     g->nodes[fbNode].fbSource = valueNode;
@@ -1998,7 +1418,6 @@ extern "C"
   {
     int st = checkNode(g, node, NODE_PROC);
     if (st) return st;
-    if (g->job) return MLGPU_ERR_BUSY;
     if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
     if (mlgpu_proc_rings(g->nodes[node].kind) == 0) return gfail(g, MLGPU_ERR_INVALID, "graph_set_max_delay: not a delay node");
     if (!(maxDelayInSamples >= 0.f) || maxDelayInSamples > 16777216.f) return gfail(g, MLGPU_ERR_RANGE, "graph_set_max_delay: 0 .. 2^24 samples");
@@ -2017,11 +1436,8 @@ extern "C"
     if (mux && (nIn < 2 || nIn > 1 + MLGPU_ROUTE_MAX_SIGNALS)) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_route: multiplex takes a selector and 1..8 signals");
     if (!mux && (nIn != 2 || nOutputs < 1 || nOutputs > MLGPU_ROUTE_MAX_SIGNALS || index < 0 || index >= nOutputs))
       return -gfail(g, MLGPU_ERR_INVALID, "graph_add_route: demultiplex takes (selector, signal), 1..8 outputs, 0 <= index < n_outputs");
-    Node n;
-    n.type = NODE_ROUTE;
-    n.kind = route;
+    Node n(NODE_ROUTE, route, name);
     n.in.assign(inputs, inputs + nIn);
-    n.name = name ? name : "";
     n.slot = index;
     n.nOut = nOutputs;
     return addNode(g, std::move(n));
@@ -2029,9 +1445,7 @@ extern "C"
   int mlgpu_graph_add_const(mlgpu_graph* g, float value)
   {
     if (!g) return -MLGPU_ERR_INVALID;
-    Node n;
-    n.type = NODE_CONST;
-    n.kind = 0;
+    Node n(NODE_CONST, 0, nullptr);
     n.value = value;
     n.slot = g->nConsts;
     const int id = addNode(g, std::move(n));
@@ -2073,9 +1487,7 @@ extern "C"
 
   int mlgpu_graph_begin_region(mlgpu_graph* g, int region, const int* inputs, int nIn, int* regionInputs)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (region != MLGPU_REGION_UPSAMPLE_2X && region != MLGPU_REGION_DOWNSAMPLE_2X) return gfail(g, MLGPU_ERR_INVALID, "graph_begin_region: unknown region kind");
     if (nIn < 0 || nIn > 8 || (nIn > 0 && (!inputs || !regionInputs))) return gfail(g, MLGPU_ERR_INVALID, "graph_begin_region: 0..8 inputs");
     int depth = 0;
@@ -2134,18 +1546,13 @@ extern "C"
     if (!g) return -MLGPU_ERR_INVALID;
     if (!opKnown(op)) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_op: unknown op");
     if (nIn != opArity(op) || !inputs) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_op: wrong number of inputs");
-    Node n;
-    n.type = NODE_OP;
-    n.kind = op;
+    Node n(NODE_OP, op, name);
     n.in.assign(inputs, inputs + nIn);
-    n.name = name ? name : "";
     return addNode(g, std::move(n));
   }
   int mlgpu_graph_add_output(mlgpu_graph* g, int node)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (node < 0 || node >= (int)g->nodes.size()) return gfail(g, MLGPU_ERR_RANGE, "graph_add_output: unknown node");
     if (g->outputs.size() >= MLGPU_GRAPH_MAX_OUTPUTS) return gfail(g, MLGPU_ERR_UNSUPPORTED, "too many graph outputs");
     g->outputs.push_back(node);
@@ -2155,9 +1562,7 @@ extern "C"
   // voices / group channels, channel c = ((0 + voice[c * group]) + voice[c * group + 1]) + ... in that order
   int mlgpu_graph_set_output_group_sum(mlgpu_graph* g, int index, int group)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (index < 0 || index >= (int)g->outputs.size()) return gfail(g, MLGPU_ERR_RANGE, "graph_set_output_group_sum: no such output");
     if (group != 0 && group != 2 && group != 4 && group != 8 && group != 16)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_set_output_group_sum: groups of 2, 4, 8 or 16 voices (other sizes: mlgpu_mixdown_groups)");
@@ -2171,9 +1576,7 @@ extern "C"
   // the output layout, and scratch reserved with mlgpu_mixdown_reserve(engine, voices x mixed outputs, vectors).
   int mlgpu_graph_set_output_mixdown(mlgpu_graph* g, int index, int on)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (index < 0 || index >= (int)g->outputs.size()) return gfail(g, MLGPU_ERR_RANGE, "graph_set_output_mixdown: no such output");
     if (on && g->outputGroup[index]) return gfail(g, MLGPU_ERR_INVALID, "graph_set_output_mixdown: the output is a group sum already");
     if (on == 2 && mlgpu_mixdown_shard_level(g->V) == 0)
@@ -2258,7 +1661,7 @@ extern "C"
     bool groupedOrEvents = g->hasEventRows;
     for (size_t o = 0; o < g->outputs.size(); ++o) groupedOrEvents = groupedOrEvents || g->outputGroup[o] != 0;
     const bool partialOk = g->V % 64 == 0 || !groupedOrEvents;
-    if (g->transposedRings && g->totalRings && !partialOk)
+    if (g->rings == RingLayout::TRANSPOSED && g->totalRings && !partialOk)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 2 with voice sums or event rows inside the kernel needs whole wavefronts (voices a multiple of 64)");
     for (size_t o = 0; o < g->outputs.size(); ++o)
       if (g->outputMix[o] && !partialOk)
@@ -2281,9 +1684,9 @@ extern "C"
     // layout 4 (sector trips) serves delay nodes of the outer graph; one inside a rate region keeps layout 1's per-sample form
     bool ringInRegion = false;
     for (const Node& n : g->nodes) ringInRegion = ringInRegion || (n.type == NODE_PROC && n.region >= 0 && mlgpu_proc_rings(n.kind) != 0);
-    if (g->sectorRings && ringInRegion)
+    if (g->rings == RingLayout::SECTORS && ringInRegion)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 4 (sector trips) does not serve a delay line inside a rate region (layout 1 or 3 for this graph)");
-    if (g->transposedIfPossible)
+    if (g->delayLayout == 3)
     {
       // "the best form": one or two rings - the transposed windows (0.72-0.74 of the HBM peak on the strings bank); more - the sector
       // trips (no LDS, every ring's loads in the trip's prologue: profiles/r06_ring_layouts.txt); where neither applies, layout 1
@@ -2294,18 +1697,17 @@ extern "C"
       for (const Node& n : g->nodes) anyPitchbendable = anyPitchbendable || (n.type == NODE_PROC && n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY);
       const bool sectorFits = !ringInRegion && g->totalRings > 0 && ldsLayout4 + ldsOther <= kLdsBytes;
       const bool preferSectors = sectorFits && (anyPitchbendable || g->totalRings > 2);
-      g->transposedRings = !preferSectors && partialOk && g->totalRings <= 4 && ldsLayout2 + ldsOther <= kLdsBytes;
-      g->sectorRings = !g->transposedRings && sectorFits;
+      const bool transposed = !preferSectors && partialOk && g->totalRings <= 4 && ldsLayout2 + ldsOther <= kLdsBytes;
       // more rings than any windowed form has LDS for (the reference's reverb example: 24): the default rows
-      if (!g->transposedRings && !g->sectorRings && ldsLayout1 + ldsOther > kLdsBytes) g->windowedRings = false;
+      g->rings = transposed ? RingLayout::TRANSPOSED : sectorFits ? RingLayout::SECTORS : ldsLayout1 + ldsOther > kLdsBytes ? RingLayout::ROWS : RingLayout::WINDOWS;
     }
-    if (g->transposedRings && ldsLayout2 + ldsOther > kLdsBytes)
+    if (g->rings == RingLayout::TRANSPOSED && ldsLayout2 + ldsOther > kLdsBytes)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 2 needs 40 KiB of LDS per ring (" + kib(ldsLayout2) + " for " + std::to_string(g->totalRings) +
                                                  " rings) next to " + kib(ldsOther) + " of output strips and tables; a workgroup has 160 KiB (layout 1 or 3 for this graph)");
-    if (g->sectorRings && ldsLayout4 + ldsOther > kLdsBytes)
+    if (g->rings == RingLayout::SECTORS && ldsLayout4 + ldsOther > kLdsBytes)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 4 needs 8 KiB of LDS per ring and 16 KiB per delay node (" + kib(ldsLayout4) + " for this graph) next to " +
                                                  kib(ldsOther) + " of output strips and tables; a workgroup has 160 KiB (layout 1 or 3 for this graph)");
-    if (!g->transposedRings && !g->sectorRings && g->windowedRings && ldsLayout1 + ldsOther > kLdsBytes)
+    if (g->rings == RingLayout::WINDOWS && ldsLayout1 + ldsOther > kLdsBytes)
       return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layouts 1 and 4 need 8 KiB of LDS per ring (" + kib(ldsLayout1) + " for " + std::to_string(g->totalRings) +
                                                  " rings) next to " + kib(ldsOther) + " of output strips and tables; a workgroup has 160 KiB");
     if (ldsOther > kLdsBytes)
@@ -2319,13 +1721,13 @@ extern "C"
     g->rowAddr64 = rowAddr32 && !strcmp(rowAddr32, "0");
     // ring layout 0: rows behind 32-bit offsets where every delay node's memory stays below 4 GiB (VoiceMem::ringPtr)
     g->rowAddr32 = false;
-    if (!g->windowedRings && g->totalRings && g->V < ((size_t)1 << 22) && !g->rowAddr64)
+    if (g->rings == RingLayout::ROWS && g->totalRings && g->V < ((size_t)1 << 22) && !g->rowAddr64)
       g->rowAddr32 = true;  // (node by node in the generator: a ring of the bank at most 4 GiB)
     // ring layout 0: the outer graph's ring reads by LDS-DMA ahead of the sample's arithmetic, a 256-byte landing slot per read and wavefront
     g->earlyRows = false;
     g->earlySlots = 0;
     for (Node& n : g->nodes) n.earlySlot = -1;
-    if (!g->windowedRings && g->totalRings && !(earlyReads && !strcmp(earlyReads, "0")))
+    if (g->rings == RingLayout::ROWS && g->totalRings && !(earlyReads && !strcmp(earlyReads, "0")))
     {
       int slots = 0;
       for (Node& n : g->nodes)
@@ -2343,15 +1745,18 @@ extern "C"
       else
         for (Node& n : g->nodes) n.earlySlot = -1;
     }
+    planEarlyReads(g);
     // delay graphs wait on their ring reads: two quads per trip keep more of them in flight (allpass4: 5.4 vs 4.5 x 10^10)
-    g->unrollQ = (g->totalRings && !g->windowedRings) ? 2 : 1;
+    g->unrollQ = (g->totalRings && g->rings == RingLayout::ROWS) ? 2 : 1;
     if (oscTrip)
     {
       const int t = atoi(oscTrip);
       g->oscTripQ = (t == 1 || t == 2 || t == 4) ? t : 0;
     }
-    if (g->sectorRings && g->totalRings && g->oscTripQ > 0) g->oscTripQ = 2;  // (one trip structure: the rings' trips are two quads)
-    if (!generateBudgeted(g, 0, g->source, g->emitted, g->log)) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc): " + g->log);
+    if (g->rings == RingLayout::SECTORS && g->totalRings && g->oscTripQ > 0) g->oscTripQ = 2;  // (one trip structure: the rings' trips are two quads)
+    const KernelForm form{graphVoicesPerLane(g), g->unrollQ, 0};
+    g->compiledVoicesPerLane = form.voicesPerLane;
+    if (!generateBudgeted(g, form, g->source, g->emitted, g->log)) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc): " + g->log);
     return MLGPU_OK;
   }
 
@@ -2378,9 +1783,9 @@ extern "C"
     if (st != MLGPU_OK) return st;
     if (!e) return MLGPU_OK;  // ahead of time: the code is in the memory and disk caches now (mlgpu_graph_compile_async on a graph without an engine)
     if (hipSetDevice(e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
-    CompiledModule* cm = compileAndLoad(e->device, g->source, g->log);
-    if (!cm) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc): " + g->log);
-    g->fn = getFunction(cm, "mlgpu_graph_kernel", g->log);
+    bool loaded = false;
+    g->fn = mlgpu_jit_function(e->device, g->source, "mlgpu_graph_kernel", g->log, &loaded);
+    if (!loaded) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc): " + g->log);
     if (!g->fn) return gfail(g, MLGPU_ERR_HIP, g->log);
     return MLGPU_OK;
   }
@@ -2458,7 +1863,7 @@ extern "C"
           if (n.type == NODE_FEEDBACK || n.type == NODE_EVENT_ROW || (n.type == NODE_PROC && (mlgpu_proc_rings(n.kind) || mlgpu_proc_is_vector_rate(n.kind)))) return false;
         return true;
       }();
-      const bool unrollFree = !(g->windowedRings && g->totalRings);
+      const bool unrollFree = !(g->rings != RingLayout::ROWS && g->totalRings);
       for (int vl = 1; vl <= (twoOk ? 2 : 1); ++vl)
         for (int u = 1; u <= (unrollFree ? 2 : 1); ++u)
         {
@@ -2616,23 +2021,18 @@ extern "C"
 
   int mlgpu_graph_set_delay_layout(mlgpu_graph* g, int windowed)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (windowed < 0 || windowed > 4)
       return gfail(g, MLGPU_ERR_INVALID, "graph_set_delay_layout: 0 (rows), 1 (32-byte sectors), 2 (transposed 64-byte pieces), 4 (sector trips) or 3 (the best of 2 / 4 / 1 for the graph)");
-    g->windowedRings = windowed != 0;
-    g->transposedRings = windowed == 2;
-    g->sectorRings = windowed == 4;
-    g->transposedIfPossible = windowed == 3;   // decided at compile, when the number of rings is known
+    static const RingLayout kRings[] = {RingLayout::ROWS, RingLayout::WINDOWS, RingLayout::TRANSPOSED, RingLayout::WINDOWS, RingLayout::SECTORS};
+    g->delayLayout = windowed;
+    g->rings = kRings[windowed];  // (layout 3: decided at compile, when the number of rings is known)
     return MLGPU_OK;
   }
 
   int mlgpu_graph_set_autotune(mlgpu_graph* g, int on)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     g->autotune = on != 0;
     return MLGPU_OK;
   }
@@ -2725,15 +2125,14 @@ extern "C"
   {
     if (!g) return -MLGPU_ERR_INVALID;
     if (g->job) return -MLGPU_ERR_BUSY;  // (layout 3 is being decided)
-    if (g->transposedIfPossible && !g->compiled) return 3;
-    return g->transposedRings ? 2 : (g->sectorRings ? 4 : (g->windowedRings ? 1 : 0));
+    static const int kApiLayout[] = {0, 1, 2, 4};  // (RingLayout)
+    if (g->delayLayout == 3 && !g->compiled) return 3;
+    return kApiLayout[(int)g->rings];
   }
 
   int mlgpu_graph_set_voices_per_lane(mlgpu_graph* g, int n)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (n < 0 || n > 2) return gfail(g, MLGPU_ERR_INVALID, "graph_set_voices_per_lane: 0 (automatic), 1 or 2");
     g->voicesPerLane = n;
     return MLGPU_OK;
@@ -2751,9 +2150,7 @@ extern "C"
 
   int mlgpu_graph_set_input_group(mlgpu_graph* g, int inputIndex, int group)
   {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph already compiled");
+    if (const int st = checkEditable(g)) return st;
     if (inputIndex < 0 || inputIndex >= g->nInputs) return gfail(g, MLGPU_ERR_RANGE, "graph_set_input_group: input index out of range");
     if (group < 1 || (size_t)group > g->V || g->V % (size_t)group) return gfail(g, MLGPU_ERR_INVALID, "graph_set_input_group: the voices are not a whole number of groups");
     g->inputGroup[inputIndex] = group;
@@ -2853,15 +2250,9 @@ extern "C"
         if (!v.failed && v.runs < 3 && (!trial || v.runs < trial->runs)) trial = &v;
       if (trial && !trial->fn)
       {
-        const int keepUnroll = g->unrollQ, keepVl = g->compiledVoicesPerLane;
-        g->unrollQ = trial->unroll;
         std::string src, log;
         std::vector<char> code;
-        const bool built = generateBudgeted(g, trial->vl, src, code, log);
-        g->unrollQ = keepUnroll;
-        g->compiledVoicesPerLane = keepVl;
-        CompiledModule* cm = built ? compileAndLoad(g->e->device, src, log) : nullptr;
-        trial->fn = cm ? getFunction(cm, "mlgpu_graph_kernel", log) : nullptr;
+        if (generateBudgeted(g, KernelForm{trial->vl, trial->unroll, 0}, src, code, log)) trial->fn = mlgpu_jit_function(g->e->device, src, "mlgpu_graph_kernel", log);
         if (!trial->fn)
         {
           trial->failed = true;
@@ -2904,7 +2295,7 @@ extern "C"
       if (est != MLGPU_OK) return gfail(g, est, "graph_process: the events object refused the block (see its last error)");
     }
     if (trial) hipEventRecord(g->tuneEv0, g->e->stream);
-    const hipError_t err = launchJit(fn, a, (g->V + (size_t)vl - 1) / (size_t)vl, g->e->stream);
+    const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->V + (size_t)vl - 1) / (size_t)vl, g->e->stream);
     if (err != hipSuccess)
     {
       if (eventStaging) mlgpu_events_abandoned_by_graph(g->events, eventStaging);  // (the lanes' record ranges back to "none": no kernel will consume them)

@@ -125,7 +125,7 @@ hipError_t mlgpu_launch_mixdown_groups(const float* sig, int layout, size_t grou
 hipError_t mlgpu_launch_route(bool demux, bool linear, const float* sel, size_t selElems, const float* const* ins, float* const* outs, int n,
                               size_t nElems, hipStream_t stream, uint32_t flags);
 
-// graph.hip — run-time fused kernels (hiprtc)
+// jit.hip, graph.hip — run-time fused kernels (hiprtc)
 // LDS strips of the generated kernels, in floats per WAVEFRONT, for the host's LDS budget (graph.hip does not include the device
 // headers; chains.hip asserts they equal mldev::kMixStrip / kGroup16Strip)
 constexpr int kHostMixStripFloats = 64 * 20 + 3 * 16 + 16;
@@ -133,6 +133,14 @@ constexpr int kHostGroup16StripFloats = 4 * (4 * 80 + 4);
 bool mlgpu_jit_chain(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log);  // honours e->strictSvf
 hipError_t mlgpu_jit_chain_launch(void* fn, const ChainArgs& a, hipStream_t stream);
 bool mlgpu_jit_chain_mix(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log);
+std::string mlgpu_jit_chain_source(const int32_t* kinds, int n, bool strictSvf, bool mix);
+// the code object of a generated source: from the memory cache, the disk cache or hiprtc (mlgpu_jit_stats counts which)
+bool mlgpu_jit_code(const std::string& source, std::vector<char>& code, std::string& log);
+bool mlgpu_jit_compile_only(const std::string& source, std::string& log);  // hiprtc alone, no caches, no device (mlgpu_jit_selftest)
+// a kernel of a generated source, its module loaded on `device` once per process (*loaded: the module is there, whatever the lookup found)
+hipFunction_t mlgpu_jit_function(int device, const std::string& source, const char* name, std::string& log, bool* loaded = nullptr);
+hipError_t mlgpu_jit_launch(hipFunction_t fn, void* args, size_t argBytes, size_t V, hipStream_t stream);  // blocks of 256 lanes over V
+bool mlgpu_jit_code_number(const std::vector<char>& code, const char* key, long& value);  // a number of the kernel's metadata note
 
 // coeffs.cpp
 void mlgpu_build_impulse_table(float* out17);
