@@ -5,6 +5,14 @@
         N > 1 by itself: starts N rank processes, rank r on GPU r (or `--launcher threads`: N host threads, one engine per
         device, in this process); under `python -m torch.distributed.run --nproc-per-node N ...` each process is one rank.
         Asking for more GPUs than are visible is an error, never a silent smaller run.
+    python bench.py --full ...
+        the same line with everything else this script measures beside the headline (see `--full` below).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: nothing else is launched or
+timed. `--full` adds, after the timed region and outside it: the launch-time distribution (laps), the same-pattern Gain kernel,
+the headline's HBM traffic from rocprofv3 counter passes in child processes, the CPU baseline, and for the default workload on one
+GPU every other BASELINE config, the widened rows, the paced north_star target and the 512-voice CRC parity against the CPU
+checkers (`--no-live-counters`, `--no-cpu-baseline`, `--no-extras` leave parts of that out).
 
 Default workload = BASELINE.json configs[2], the configuration the metric
 "voice-samples/sec (SawGen->SVF chain)" is quoted on:
@@ -24,7 +32,7 @@ Prints ONE JSON line on rank 0 with
                 launch from the rocprofv3 PMC passes of exactly this workload and size (profiles/pmc_workloads.json,
                 else null); `valu` = the VALU-issue bound from SQ_INSTS_VALU of the same passes; `bound` names
                 whichever fraction is higher
-  cpu_baseline  (N=1 only) the compiled reference (oracle/_ref) when present, else the plain-C port,
+  cpu_baseline  (--full, N=1 only) the compiled reference (oracle/_ref) when present, else the plain-C port,
                 timed on the host cores over a bounded sample of the same workload.
 """
 import argparse
@@ -715,8 +723,8 @@ def cpu_baseline_cfg5(budget_s=10.0, full=False):
                       "discarded, median of 5 (reference objects, g++ -O2 -fno-strict-aliasing, SSE2)"}
 
 
-# ---- every BASELINE config and the north_star target inside the one command the driver runs --------------------------------------
-# `python bench.py --gpus 1` (the default workload, cfg3) keeps its headline line exactly as it is and, after its timed region,
+# ---- every BASELINE config and the north_star target inside one command ----------------------------------------------------------
+# `python bench.py --gpus 1 --full` (the default workload, cfg3) keeps its headline line exactly as it is and, after its timed region,
 # times the other configurations in the same process - each from >= 5 timed steps, HIP events on the engine's stream, algorithmic
 # bytes as DESIGN 3.0 states them - and adds them as FLAT scalar keys under "roofline" (a driver that keeps scalars and drops nested
 # objects still sees them). The CPU comparison of each configuration (a 512-voice instance against the oracle, CRC of the bits) is
@@ -792,12 +800,13 @@ def cfg2_cases(eng, steps=5):
     return out
 
 
-def rt_case(eng, V=1048576, frames=64, blocks=1500, lead_in=50):
+def rt_case(eng, V=1048576, frames=64, blocks=1500, lead_in=50, two_calls=True):
     """BASELINE.json north_star "Target", measured as a real-time host would run it (tools/rt_target.cpp is the C++ original of this
     loop; the reference's is SignalProcessBuffer::process, source/app/MLSignalProcessBuffer.cpp:57-78): V SawGen -> Bandpass -> gain
     voices, one call per 64-frame block through mlgpu_process_buffer_process - voice bank, mixdown to one channel, D2H of that channel -
     with the host waiting out each 48 kHz block period. Reports the wall time of a call (p50 / p99 / max) against the period, the
-    calls that took longer than the period, and the voice kernel's free-running HIP-event time per block against the HBM peak."""
+    calls that took longer than the period, and the voice kernel's free-running HIP-event time per block against the HBM peak.
+    two_calls: after the fused form, a shorter paced run of the two-call form (voice bank, then mixdown) for comparison."""
     import ctypes
     import gc
     import madronalib_amd as ml
@@ -876,7 +885,7 @@ def rt_case(eng, V=1048576, frames=64, blocks=1500, lead_in=50):
     gc.disable()           # a collection in the middle of a block is this script's, not the device's
     try:
         us, misses, peak = paced((cb_seq if form == "sequence" else cb_one) if fused else cb_two, blocks)
-        us2 = paced(cb_two, max(100, blocks // 5))[0] if fused else None
+        us2 = paced(cb_two, max(100, blocks // 5))[0] if fused and two_calls else None
     finally:
         if gc_was:
             gc.enable()
@@ -1235,7 +1244,7 @@ def run_rank(args, rank, local_rank, world, rdv):
         raw, co = pmc["fetch_bytes_per_launch_raw"], META["coalesced_read_bytes"]
         traffic = pmc["write_bytes_per_launch"] + (2.0 * raw if co is None else raw + min(raw, 0.5 * co))
     traffic_source = "profiles/pmc_workloads.json (recorded for this build of the device code)" if traffic is not None else None
-    if (world == 1 and args.workload == "cfg3" and not args.no_live_counters and not args.voices and not args.vectors and not os.environ.get("MLGPU_BENCH_CHILD")
+    if (args.full and world == 1 and args.workload == "cfg3" and not args.no_live_counters and not args.voices and not args.vectors and not os.environ.get("MLGPU_BENCH_CHILD")
             and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) and "rocprof" not in os.environ.get("LD_PRELOAD", "")):   # (not under a profiler already)
         # the headline's HBM traffic measured by THIS run (weak point of round 5: the driver never saw a counter): ~15 s
         lt = live_traffic(args.workload, kernel_name)
@@ -1262,7 +1271,7 @@ def run_rank(args, rank, local_rank, world, rdv):
                          "source": "GRBM_GUI_ACTIVE / 8 XCDs (profiles/pmc_workloads.json) / " + span_what}
     # what the same access pattern reaches with (almost) no arithmetic, on this box, now: the honest ceiling of an HBM-bound launch
     streamed = args.workload in ("cfg4", "cfg5", "cfg5full", "cfg2")
-    if world == 1 and not args.sustained:
+    if args.full and world == 1 and not args.sustained:
         # The DISTRIBUTION of the kernel's launch durations, a leg of its own after the timed region (an event after every launch; the
         # headline's mean keeps its two events): the board runs these launches at its power cap and the launch time follows the shader
         # clock it is granted (profiles/r06_cfg3_spread.md) - p10 is not a speed the chip holds.
@@ -1275,7 +1284,7 @@ def run_rank(args, rank, local_rank, world, rdv):
                          "kernel_ms_laps": int(len(laps))})
         except Exception as ex:
             roof["kernel_ms_laps_error"] = repr(ex)
-    if world == 1 and args.workload in ("cfg3", "cfg4", "cfg5", "cfg5full"):
+    if args.full and world == 1 and args.workload in ("cfg3", "cfg4", "cfg5", "cfg5full"):
         try:
             gbs, cms = pattern_ceiling(eng, V, T, streamed)
             # (rounds 3-5 called this store_ceiling / stream_ceiling. It is a REFERENCE KERNEL - the same access pattern next to one multiply,
@@ -1364,7 +1373,7 @@ def run_rank(args, rank, local_rank, world, rdv):
         out["sustained"] = sustained_run(args, eng, step, launch, L, float(V) * T * 64, value)
     if args.oversubscribe:
         out["oversubscribed"] = f"{world} ranks on {len(set(buses))} GPU(s): launch-path test, not a scaling measurement"
-    extras = world == 1 and args.workload == "cfg3" and not args.no_extras and not args.voices and not args.vectors
+    extras = args.full and world == 1 and args.workload == "cfg3" and not args.no_extras and not args.voices and not args.vectors
     if extras:
         # the other BASELINE configs and the north_star target, timed in this process after the headline's region (flat keys)
         del launch, step
@@ -1375,48 +1384,51 @@ def run_rank(args, rank, local_rank, world, rdv):
         out["other_configs"] = full
         out["other_configs"]["seconds"] = time.perf_counter() - t_x
     if args.workload == "cfg2":
-        # each op and the fused pair, on the ramp and on noise (no data-dependent branches: same rate)
         from madronalib_amd.constants import Op
-        d_x, d_y = _keep
-        n_el = V * T * 64
-        d_noise = eng.to_device(np.random.default_rng(1).uniform(-np.pi, np.pi, n_el).astype(np.float32))
-        per_op = {}
-        reps = max(16, min(256, int(2 ** 34 / (8.0 * n_el))))
-        for label, op in (("sinApprox", Op.SIN_APPROX), ("expApprox", Op.EXP_APPROX), ("expApprox(sinApprox)", Op.EXP_APPROX_OF_SIN_APPROX)):
-            for data, src in (("ramp", d_x), ("noise", d_noise)):
-                for _ in range(8):
-                    eng.op_apply(op, src, None, None, d_y, n_el)
-                eng.timer_start()
-                for _ in range(reps):
-                    eng.op_apply(op, src, None, None, d_y, n_el)
-                per_op[f"{label} / {data}"] = n_el * reps / (eng.timer_stop_ms() * 1e-3)
-        out["config"]["per_op_voice_samples_per_s"] = per_op
+        if args.full:
+            # each op and the fused pair, on the ramp and on noise (no data-dependent branches: same rate)
+            d_x, d_y = _keep
+            n_el = V * T * 64
+            d_noise = eng.to_device(np.random.default_rng(1).uniform(-np.pi, np.pi, n_el).astype(np.float32))
+            per_op = {}
+            reps = max(16, min(256, int(2 ** 34 / (8.0 * n_el))))
+            for label, op in (("sinApprox", Op.SIN_APPROX), ("expApprox", Op.EXP_APPROX), ("expApprox(sinApprox)", Op.EXP_APPROX_OF_SIN_APPROX)):
+                for data, src in (("ramp", d_x), ("noise", d_noise)):
+                    for _ in range(8):
+                        eng.op_apply(op, src, None, None, d_y, n_el)
+                    eng.timer_start()
+                    for _ in range(reps):
+                        eng.op_apply(op, src, None, None, d_y, n_el)
+                    per_op[f"{label} / {data}"] = n_el * reps / (eng.timer_stop_ms() * 1e-3)
+            out["config"]["per_op_voice_samples_per_s"] = per_op
         # BASELINE's own size (65 536 voices: 32 MiB in + out) lives in the Infinity Cache; the HBM figure of the same kernel is taken
-        # at 4 194 304 voices (1 GiB) in the same run, and the line carries both
+        # at 4 194 304 voices (1 GiB) in the same run under --full, and the line carries both
         if world == 1 and V * T * 64 * 8 < (256 << 20):
             roof["bound"] = "on-die"
             roof["bound_evidence"] = {"working_set_MiB": V * T * 64 * 8 / 2 ** 20, "infinity_cache_MiB": 256}
-            # (this run launches the same kernel over 1 GiB too, below: per-kernel PMC means would mix the two sizes)
+            # (a --full run launches the same kernel over 1 GiB too, below, and so did the runs the counter records were taken from:
+            # per-kernel PMC means would mix the two sizes)
             for k in ("valu", "clock", "traffic", "pmc_case"):
                 roof[k] = None
-            Vb = 4194304
-            nb = Vb * 64
-            d_bx, d_by = eng.alloc(4 * nb), eng.alloc(4 * nb)
-            eng.op_apply(Op.SIN_APPROX, d_bx, None, None, d_by, nb)   # (values irrelevant to the rate: no data-dependent branches)
-            for _ in range(4):
-                eng.op_apply(Op.EXP_APPROX_OF_SIN_APPROX, d_bx, None, None, d_by, nb)
-            eng.sync()
-            eng.timer_start()
-            for _ in range(32):
-                eng.op_apply(Op.EXP_APPROX_OF_SIN_APPROX, d_bx, None, None, d_by, nb)
-            bms = eng.timer_stop_ms() / 32
-            out["roofline_at_1GiB"] = {"bound": "hbm", "voices": Vb, "achieved": 8.0 * nb / (bms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": 8.0 * nb / (bms * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel_ms": bms, "voice_samples_per_s": nb / (bms * 1e-3),
-                                       "note": "the same op_kernel over 4 194 304 voices x 1 DSPVector (512 MiB in, 512 MiB out): the HBM figure of config 2"}
-            d_bx.free()
-            d_by.free()
+            if args.full:   # (the 1 GiB leg)
+                Vb = 4194304
+                nb = Vb * 64
+                d_bx, d_by = eng.alloc(4 * nb), eng.alloc(4 * nb)
+                eng.op_apply(Op.SIN_APPROX, d_bx, None, None, d_by, nb)   # (values irrelevant to the rate: no data-dependent branches)
+                for _ in range(4):
+                    eng.op_apply(Op.EXP_APPROX_OF_SIN_APPROX, d_bx, None, None, d_by, nb)
+                eng.sync()
+                eng.timer_start()
+                for _ in range(32):
+                    eng.op_apply(Op.EXP_APPROX_OF_SIN_APPROX, d_bx, None, None, d_by, nb)
+                bms = eng.timer_stop_ms() / 32
+                out["roofline_at_1GiB"] = {"bound": "hbm", "voices": Vb, "achieved": 8.0 * nb / (bms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                           "frac": 8.0 * nb / (bms * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel_ms": bms, "voice_samples_per_s": nb / (bms * 1e-3),
+                                           "note": "the same op_kernel over 4 194 304 voices x 1 DSPVector (512 MiB in, 512 MiB out): the HBM figure of config 2"}
+                d_bx.free()
+                d_by.free()
     baselines = {"cfg2": cpu_baseline_cfg2, "cfg3": cpu_baseline_cfg3, "cfg4": cpu_baseline_cfg4, "cfg5": cpu_baseline_cfg5, "cfg5full": cpu_baseline_cfg5full}
-    if world == 1 and not args.no_cpu_baseline and args.workload in baselines:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload in baselines:
         try:
             out["cpu_baseline"] = baselines[args.workload]()
         except Exception as ex:  # the baseline is a report, never a reason to lose the GPU number
@@ -1526,7 +1538,7 @@ def run_rt(args, eng, info, V, T, L, rank, world, rdv):
         return run_rt_group(args, eng, info, V, T, L, rank, world, rdv)
     rdv.barrier()
     t0 = time.perf_counter()
-    r = rt_case(eng, V, 64 * T, blocks=L * args.steps, lead_in=max(1, L * args.warmup))
+    r = rt_case(eng, V, 64 * T, blocks=L * args.steps, lead_in=max(1, L * args.warmup), two_calls=args.full)
     elapsed = rdv.max(time.perf_counter() - t0)
     if rank != 0:
         return None
@@ -1639,11 +1651,16 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY: let ranks share devices (rank r on device r mod visible) so the N>1 launch paths can be exercised on "
                          "a box with fewer GPUs; the line says so and is not a scaling measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-counters", action="store_true", help="do not take the headline's FETCH_SIZE / WRITE_SIZE with rocprofv3 in child processes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: launch-time laps, the same-pattern Gain kernel, "
+                         "the headline's HBM traffic from rocprofv3 counter passes, the CPU baseline and, for cfg3 on one GPU, every other "
+                         "config, the widened rows, the paced target and the CRC parity against the CPU checkers (~35 s); a plain run does none of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the CRC parity")
+    ap.add_argument("--no-live-counters", action="store_true",
+                    help="with --full: do not take the headline's FETCH_SIZE / WRITE_SIZE with rocprofv3 in child processes")
     ap.add_argument("--no-extras", action="store_true",
-                    help="the default run (cfg3, one GPU) also times configs 2, 4, 5, the survey's patch and the paced 2^20-voice target and adds them "
-                         "as flat keys under roofline (~15 s); this switch leaves the headline alone")
+                    help="with --full: the default workload (cfg3, one GPU) also times configs 2, 4, 5, the survey's patch and the paced 2^20-voice "
+                         "target and adds them as flat keys under roofline (~15 s); this switch leaves those out")
     ap.add_argument("--cascade-lanes", type=int, default=None, choices=[-1, 0, 1, 2, 4],
                     help="force the form of SVF-cascade banks (mlgpu_engine_set_cascade_lanes): A/B runs of config 4")
     ap.add_argument("--two-streams", action="store_true",

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: 512-voice instances of the widened rows' bench workloads (the instrument bank, plucked strings,
 EventsToSignals, the Downsampler, the reference's reverb example) on the device and on the CPU checker. Used twice: as GPU parity tests
-(tests/test_gpu_widened_parity.py, bit for bit) and by bench.py's cpu_baseline leg, which prints the CRC-32 of both sides in the
+(tests/test_gpu_widened_parity.py, bit for bit) and by the cpu_baseline leg of bench.py --full, which prints the CRC-32 of both sides in the
 driver's line (`<leg>_crc_match`). Every case returns (got, want, checker) with got / want float32 arrays of the same shape.
 
 The workloads are bench.py's own (same graphs, same per-voice parameter functions, same kinds of input); only the size differs."""

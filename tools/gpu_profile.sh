@@ -9,11 +9,12 @@ export TMPDIR=/tmp
 root=$PWD
 for w in "$@"; do
   out=$root/gpurun_out/prof_${tag}_$w
+  res=${out%/*}/${tag}_$w    # (the result files sit next to the scratch folder)
   rm -rf $out; mkdir -p $out
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python $root/bench.py --workload $w --no-cpu-baseline > $root/gpurun_out/${tag}_${w}_bench_under_rocprof.json 2> $out/stderr.log )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python $root/bench.py --full --workload $w --no-cpu-baseline > ${res}_bench_under_rocprof.json 2> $out/stderr.log )
   f=$(find $out -name '*_kernel_stats.csv' | head -1)
-  [ -n "$f" ] && cp $f $root/gpurun_out/${tag}_${w}_kernel_stats.csv
-  python $root/bench.py --workload $w --no-cpu-baseline 2>/dev/null | tail -1 > $root/gpurun_out/${tag}_${w}_bench.json
-  echo "== $w"; head -3 $root/gpurun_out/${tag}_${w}_kernel_stats.csv; cat $root/gpurun_out/${tag}_${w}_bench.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline'])"
+  [ -n "$f" ] && cp $f ${res}_kernel_stats.csv
+  python $root/bench.py --full --workload $w --no-cpu-baseline 2>/dev/null | tail -1 > ${res}_bench.json
+  echo "== $w"; head -3 ${res}_kernel_stats.csv; cat ${res}_bench.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline'])"
   find $out -name '*.csv' -size +2M -delete
 done
