@@ -347,7 +347,10 @@ int mlgpu_validate(mlgpu_engine* e, const float* d_signal, size_t n_elems, uint6
  * layout_convert calls - are captured instead of run; mlgpu_sequence_launch replays them all with ONE graph launch, with the
  * arguments (buffers, vector counts) they were recorded with. Not recordable (MLGPU_ERR_INVALID while recording): calls that
  * wait for the device or work on the host per call (upload / download / sync, events_process, published_signal_write,
- * process_buffer), and graphs that count DSPVectors or are still tuning (a DOWNSAMPLE_2X region, autotune not settled). */
+ * process_buffer), and graphs that count DSPVectors or are still tuning (a DOWNSAMPLE_2X region, autotune not settled).
+ * Every *_destroy of an object an engine owns (bank, graph, events, transport, published signal, resampler, process buffer)
+ * is refused while its engine records, and while recorded sequences of the engine live it releases the object's device memory
+ * with the last of them; buffers only the library holds are replaced the same way when they grow. */
 typedef struct mlgpu_sequence mlgpu_sequence;
 int mlgpu_engine_begin_recording(mlgpu_engine* e);
 int mlgpu_engine_end_recording(mlgpu_engine* e, mlgpu_sequence** out);
@@ -786,7 +789,7 @@ typedef struct mlgpu_event /* ml::Event, MLEvent.h:31-53 */
 } mlgpu_event;
 typedef struct mlgpu_events mlgpu_events;
 int mlgpu_events_create(mlgpu_engine* e, size_t n_instruments, int polyphony /* setPolyphony, 1..16 */, mlgpu_events** out);
-int mlgpu_events_destroy(mlgpu_events* ev);   /* (while recorded sequences of the engine live, the memory is released with the last of them) */
+int mlgpu_events_destroy(mlgpu_events* ev);
 int mlgpu_events_clear(mlgpu_events* ev);                                   /* clear(), :330-340 */
 int mlgpu_events_set_sample_rate(mlgpu_events* ev, double sr);
 int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe);                   /* setProtocol("MIDI" / "MPE"); clears */

@@ -133,7 +133,25 @@ def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-class DeviceBuffer:
+class _Handle:
+    """A C-API object: close() destroys it once, with the destroy function `_destroy` names, and __del__ closes it. An engine's
+    objects go before the engine (Engine.close closes its children first), so once the engine is gone there is nothing to destroy."""
+    _destroy = None
+
+    def close(self):
+        engine = getattr(self, "engine", None)
+        if getattr(self, "h", None) and (engine is None or engine.h or isinstance(engine, OfflineEngine)):
+            getattr(self.L, self._destroy)(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer(_Handle):
     """A caller-owned HBM allocation (mlgpu_alloc)."""
 
     def __init__(self, engine, nbytes):
@@ -164,14 +182,8 @@ class DeviceBuffer:
 
     close = free
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
-
-class Engine:
+class Engine(_Handle):
     """One MI355X + one HIP stream (mlgpu_engine)."""
 
     def __init__(self, device=0, stream=None, urgency=0):
@@ -188,12 +200,6 @@ class Engine:
         self.h = h
         self.device = int(device)
         self._children = weakref.WeakSet()  # banks and buffers: released before the engine goes away
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _check(self, st):
         if st != 0:
@@ -406,8 +412,9 @@ class Engine:
         return _Recording(self)
 
 
-class Fence:
+class Fence(_Handle):
     """Ordering between two engines (= two HIP streams) of one device; see Engine.signal / Engine.wait."""
+    _destroy = "mlgpu_fence_destroy"
 
     def __init__(self, engine):
         self.engine, self.L = engine, engine.L
@@ -416,23 +423,13 @@ class Fence:
         self.h = h
         engine._children.add(self)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.mlgpu_fence_destroy(self.h)
-        self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Sequence:
+class Sequence(_Handle):
     """A recorded launch sequence (mlgpu_sequence)."""
+    _destroy = "mlgpu_sequence_destroy"
 
     def __init__(self, engine):
-        self.engine, self.h = engine, None
+        self.engine, self.L, self.h = engine, engine.L, None
 
     def launch(self):
         self.engine._check(self.engine.L.mlgpu_sequence_launch(self.h))
@@ -440,17 +437,6 @@ class Sequence:
     @property
     def num_nodes(self):
         return int(self.engine.L.mlgpu_sequence_num_nodes(self.h))
-
-    def close(self):
-        if self.h and self.engine.h:
-            self.engine.L.mlgpu_sequence_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _Recording:
@@ -471,21 +457,14 @@ class _Recording:
         return False
 
 
-class DSPBuffer:
+class DSPBuffer(_Handle):
     """The reference's DSPBuffer (MLDSPBuffer.h): a host SPSC float ring (mlgpu_dspbuffer)."""
+    _destroy = "mlgpu_dspbuffer_destroy"
 
     def __init__(self, size):
         self.L = _lib.load()
         self.h = ctypes.c_void_p(self.L.mlgpu_dspbuffer_create())
         self.size = self.L.mlgpu_dspbuffer_resize(self.h, int(size))
-
-    def __del__(self):
-        try:
-            if self.h:
-                self.L.mlgpu_dspbuffer_destroy(self.h)
-            self.h = None
-        except Exception:
-            pass
 
     def read_available(self):
         return self.L.mlgpu_dspbuffer_read_available(self.h)
@@ -540,9 +519,10 @@ def make_window(size, shape="triangle"):
     return out
 
 
-class ProcessBuffer:
+class ProcessBuffer(_Handle):
     """The reference's SignalProcessBuffer (MLSignalProcessBuffer.h) over the engine: host blocks of any size in and
     out, `fn(n_vectors, d_inputs, d_outputs)` called once per block with single-voice device signals (raw pointers)."""
+    _destroy = "mlgpu_process_buffer_destroy"
 
     _CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p))
 
@@ -553,17 +533,6 @@ class ProcessBuffer:
         engine._check(self.L.mlgpu_process_buffer_create(engine.h, n_inputs, n_outputs, max_frames, ctypes.byref(h)))
         self.h = h
         engine._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_process_buffer_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_pipelined(self, on=True):
         """Double-buffered mode: a call returns at once with what earlier calls computed; fixed delay latency_frames()."""
@@ -604,8 +573,9 @@ class Event(ctypes.Structure):  # mlgpu_event == ml::Event
                 ("value1", ctypes.c_float), ("value2", ctypes.c_float)]
 
 
-class Events:
+class Events(_Handle):
     """EventsToSignals (source/app/MLEventsToSignals.h) for n_instruments instruments of `polyphony` voices (mlgpu_events)."""
+    _destroy = "mlgpu_events_destroy"
     ROWS = ("pitch", "gate", "vox", "z", "x", "y", "mod", "time")
 
     def __init__(self, engine, n_instruments, polyphony, sr=48000.0):
@@ -617,17 +587,6 @@ class Events:
         self.V = self.n_instruments * self.polyphony
         engine._children.add(self)
         self.set_sample_rate(sr)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_events_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_sample_rate(self, sr):
         self.engine._check(self.L.mlgpu_events_set_sample_rate(self.h, float(sr)))
@@ -730,9 +689,10 @@ class Events:
         return np.stack([np.zeros((V, T * 64), np.float32) if b is None else b.download(np.float32, V * T * 64).reshape(V, T * 64) for b in bufs])
 
 
-class Transport:
+class Transport(_Handle):
     """AudioContext::ProcessTime (source/app/MLAudioContext.cpp:16-104) for n contexts (mlgpu_transport): the quarter-note phasor
     behind ctx->getBeatPhase(). index None = every context."""
+    _destroy = "mlgpu_transport_destroy"
     ALL = (1 << 64) - 1
 
     def __init__(self, engine, n, max_vectors):
@@ -741,17 +701,6 @@ class Transport:
         engine._check(self.L.mlgpu_transport_create(engine.h, int(n), int(max_vectors), ctypes.byref(h)))
         self.h, self.n = h, int(n)
         engine._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_transport_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def update_time(self, ppq_pos, bpm, is_playing, sample_rate, index=None):
         """AudioContext::updateTime: what the host reports for the start of the next process call."""
@@ -785,9 +734,10 @@ class Transport:
         return q.reshape(16 * T, self.n, 4).transpose(1, 0, 2).reshape(self.n, 64 * T)
 
 
-class PublishedSignal:
+class PublishedSignal(_Handle):
     """SignalProcessor::PublishedSignal (source/app/MLSignalProcessor.h:26-105): a decimated frame-major copy of a few
     channels of a few voices, for displays. write() takes device signals (DeviceBuffer) of `n_voices_total` voices."""
+    _destroy = "mlgpu_published_signal_destroy"
 
     def __init__(self, engine, max_frames, max_voices, channels, octaves_down):
         self.engine, self.L = engine, engine.L
@@ -796,17 +746,6 @@ class PublishedSignal:
         engine._check(self.L.mlgpu_published_signal_create(engine.h, int(max_frames), int(max_voices), self.channels, int(octaves_down), ctypes.byref(h)))
         self.h = h
         engine._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_published_signal_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def write(self, n_vectors, d_channels, n_voices_total, first_voice=0, n_voices=None, layout=Layout.QUAD):
         arr = (ctypes.c_void_p * self.channels)(*[ctypes.c_void_p(d.ptr) for d in d_channels])
@@ -834,8 +773,9 @@ class PublishedSignal:
         return self._get(self.L.mlgpu_published_signal_peek_latest, frames)[0]
 
 
-class Resampler:
+class Resampler(_Handle):
     """Downsampler / Upsampler (MLDSPFilters.h:1316-1473) for V voices: a HalfBandFilter cascade, one stage per octave."""
+    _destroy = "mlgpu_resampler_destroy"
 
     def __init__(self, engine, n_voices, octaves, up):
         self.engine, self.L = engine, engine.L
@@ -844,17 +784,6 @@ class Resampler:
         engine._check(self.L.mlgpu_resampler_create(engine.h, self.V, self.octaves, 1 if up else 0, ctypes.byref(h)))
         self.h = h
         engine._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_resampler_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def clear(self):
         self.engine._check(self.L.mlgpu_resampler_clear(self.h))
@@ -893,8 +822,9 @@ class Resampler:
         return res.download(np.float32, V * 64 * Tout).reshape(V, 64 * Tout)
 
 
-class Bank:
+class Bank(_Handle):
     """Runtime-sized Bank<T,ROWS> (reference MLDSPFunctional.h:321-360): V voices of one chain."""
+    _destroy = "mlgpu_bank_destroy"
 
     def __init__(self, engine, procs, n_voices):
         self.engine = engine
@@ -906,17 +836,6 @@ class Bank:
         engine._check(self.L.mlgpu_bank_create(engine.h, arr, len(self.procs), self.V, ctypes.byref(h)))
         self.h = h
         engine._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None) and self.engine.h:
-            self.L.mlgpu_bank_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def fused(self):
@@ -1057,13 +976,14 @@ class OfflineEngine:
             raise MlgpuError(st, "offline graph (no engine): status %d" % st)
 
 
-class Graph:
+class Graph(_Handle):
     """A run-time defined per-voice DAG of processors and ops, fused into one kernel (mlgpu_graph).
 
     Nodes are named (after the reference's proc convention, source/procs/MLProcMultiply.cpp:12-18) and
     are added in topological order. `description` form (see patches.py): a list of dicts
       {"name", "type": "input"|"param"|"const"|"proc"|"op", "kind": Proc.X / Op.X, "inputs": [names], "value"}
     """
+    _destroy = "mlgpu_graph_destroy"
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
                  live_constants=False, output_groups=None, input_groups=None, compile_now=True):
@@ -1100,11 +1020,6 @@ class Graph:
             if engine.h is not None and compile_now:
                 self.compile()
 
-    def close(self):
-        if getattr(self, "h", None) and (self.engine.h or isinstance(self.engine, OfflineEngine)):
-            self.L.mlgpu_graph_destroy(self.h)
-        self.h = None
-
     @property
     def device_bytes(self):
         """Device memory the compiled graph owns (mlgpu_graph_device_bytes)."""
@@ -1130,12 +1045,6 @@ class Graph:
         code, size = ctypes.c_void_p(), ctypes.c_size_t()
         self._check(self.L.mlgpu_graph_emit(self.h, ctypes.byref(code), ctypes.byref(size)))
         return self.source, ctypes.string_at(code, size.value)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _id(self, ref):
         return self.ids[ref] if isinstance(ref, str) else int(ref)

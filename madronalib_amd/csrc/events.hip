@@ -1044,22 +1044,22 @@ struct mlgpu_events
   std::vector<Instrument> inst;
   std::vector<std::vector<Rec>> laneRecs;  // per lane, this launch
   std::vector<uint32_t> dirtyLanes;        // lanes with records (most have none)
-  uint32_t* d_state{nullptr};
+  DeviceBuffer<uint32_t> d_state;
   // [lanes]: where a lane's records of the coming launch are, {0, 0} for none. Only the lanes that have records are written per
   // launch (a few hundred of 262 144: the list goes up in kilobytes where a start offset per lane was a megabyte over PCIe
   // every block), and a kernel that consumed a lane's records puts the {0, 0} back.
-  uint2* d_recRange{nullptr};
+  DeviceBuffer<uint2> d_recRange;
   // Two sets of upload buffers (pinned host + device): the records of launch k + 1 are routed and copied while the kernel of
   // launch k still runs; a set is reused only after the launch that read it has finished (its event).
   struct Staging
   {
-    Rec* h_recs{nullptr};
-    Rec* d_recs{nullptr};
-    uint4* h_dirty{nullptr};   // {lane, first record, one past the last, 0} for every lane that has records in this launch
-    uint4* d_dirty{nullptr};
+    PinnedBuffer<Rec> h_recs;
+    DeviceBuffer<Rec> d_recs;
+    PinnedBuffer<uint4> h_dirty;  // {lane, first record, one past the last, 0} for every lane that has records in this launch
+    DeviceBuffer<uint4> d_dirty;
     size_t recCapacity{0}, dirtyCapacity{0};
     size_t nDirtySet{0};       // lanes whose range set_rec_ranges_kernel has set for the block in flight and no kernel has consumed yet
-    hipEvent_t done{nullptr};
+    OwnedEvent done;
     bool pending{false};
   } stage[2];
   int stageIdx{0};
@@ -1067,16 +1067,16 @@ struct mlgpu_events
   std::vector<int> watched;
   int slotOf[kNumControllers];
   size_t ctlMaxVectors{0}, ctlCapacityVectors{0};  // longest launch allowed / what d_ctlOut was allocated for
-  float* d_ctlOut{nullptr};
-  uint32_t* d_ctlState{nullptr};
+  DeviceBuffer<float> d_ctlOut;
+  DeviceBuffer<uint32_t> d_ctlState;
   std::vector<std::vector<CtlRec>> ctlLaneRecs;
   std::vector<uint32_t> ctlDirty;
   struct CtlStaging
   {
-    CtlRec* h_recs{nullptr};
-    CtlRec* d_recs{nullptr};
-    uint32_t* h_recStart{nullptr};
-    uint32_t* d_recStart{nullptr};
+    PinnedBuffer<CtlRec> h_recs;
+    DeviceBuffer<CtlRec> d_recs;
+    PinnedBuffer<uint32_t> h_recStart;
+    DeviceBuffer<uint32_t> d_recStart;
     size_t recCapacity{0};
   } ctlStage[2];
   size_t ctlLanes() const { return watched.size() * nInstruments; }
@@ -1088,9 +1088,9 @@ struct mlgpu_events
   }
   uint32_t rowMask{0xFFu};                 // mlgpu_events_set_wanted_rows
   // e2s_ctl_kernel's outputs (mlgpu_events_prepare_for_graph): control records [T][kCtlRecWords][lanes] and the two side signals
-  uint32_t* d_ctlRecs{nullptr};
-  float* d_rowP{nullptr};
-  float* d_rowG{nullptr};
+  DeviceBuffer<uint32_t> d_ctlRecs;
+  DeviceBuffer<float> d_rowP;
+  DeviceBuffer<float> d_rowG;
   size_t ctlRecVectors{0};
   bool ctlRecReserved{false};  // mlgpu_events_reserve_for_graph was called: process calls never allocate, longer blocks are refused
   size_t lanes() const { return nInstruments * (size_t)group; }
@@ -1351,18 +1351,9 @@ void initialState(const mlgpu_events* ev, std::vector<uint32_t>& st)
 
 static void freeControllers(mlgpu_events* ev)
 {
-  if (ev->d_ctlOut) hipFree(ev->d_ctlOut);
-  if (ev->d_ctlState) hipFree(ev->d_ctlState);
-  ev->d_ctlOut = nullptr;
-  ev->d_ctlState = nullptr;
-  for (mlgpu_events::CtlStaging& st : ev->ctlStage)
-  {
-    if (st.h_recs) hipHostFree(st.h_recs);
-    if (st.d_recs) hipFree(st.d_recs);
-    if (st.h_recStart) hipHostFree(st.h_recStart);
-    if (st.d_recStart) hipFree(st.d_recStart);
-    st = mlgpu_events::CtlStaging();
-  }
+  ev->d_ctlOut.reset();
+  ev->d_ctlState.reset();
+  for (mlgpu_events::CtlStaging& st : ev->ctlStage) st = mlgpu_events::CtlStaging();
   ev->watched.clear();
   ev->ctlLaneRecs.clear();
   ev->ctlDirty.clear();
@@ -1372,63 +1363,29 @@ static void freeControllers(mlgpu_events* ev)
 extern "C"
 {
   // What a recorded sequence may still read is DEVICE memory only (event routing is refused while recording, so no replay ever
-  // touches the pinned staging or the hipEvents): the host side goes at once, the device buffers when no sequence can replay.
-  static void freeEventsHostSide(mlgpu_events* ev)
-  {
-    for (mlgpu_events::Staging& st : ev->stage)
-    {
-      if (st.h_recs) hipHostFree(st.h_recs);
-      if (st.h_dirty) hipHostFree(st.h_dirty);
-      if (st.done) hipEventDestroy(st.done);
-      st.h_recs = nullptr;
-      st.h_dirty = nullptr;
-      st.done = nullptr;
-    }
-    for (mlgpu_events::CtlStaging& st : ev->ctlStage)
-    {
-      if (st.h_recs) hipHostFree(st.h_recs);
-      if (st.h_recStart) hipHostFree(st.h_recStart);
-      st.h_recs = nullptr;
-      st.h_recStart = nullptr;
-    }
-    std::vector<Instrument>().swap(ev->inst);
-    std::vector<std::vector<Rec>>().swap(ev->laneRecs);
-    std::vector<std::vector<CtlRec>>().swap(ev->ctlLaneRecs);
-  }
-  static void freeEventsDeviceSide(mlgpu_events* ev)
-  {
-    if (ev->d_state) hipFree(ev->d_state);
-    if (ev->d_ctlRecs) hipFree(ev->d_ctlRecs);
-    if (ev->d_rowP) hipFree(ev->d_rowP);
-    if (ev->d_rowG) hipFree(ev->d_rowG);
-    if (ev->d_recRange) hipFree(ev->d_recRange);
-    freeControllers(ev);
-    for (mlgpu_events::Staging& st : ev->stage)
-    {
-      if (st.d_recs) hipFree(st.d_recs);
-      if (st.d_dirty) hipFree(st.d_dirty);
-    }
-    delete ev;
-  }
+  // touches the pinned staging or the hipEvents): the host side goes at once, the device buffers with the object. A host that
+  // keeps one long-lived sequence and churns events objects so holds on to their device buffers only - state and signals -, not
+  // to pinned memory and events.
   int mlgpu_events_destroy(mlgpu_events* ev)
   {
     if (!ev) return MLGPU_ERR_INVALID;
-    // waiting for the stream would invalidate a capture in progress
-    if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_destroy waits for the device: not while recording a sequence");
-    mlgpu_graph_forget_events(ev);  // graphs bound to this object (mlgpu_graph_bind_events) go back to "no events object"
-    hipSetDevice(ev->e->device);
-    hipStreamSynchronize(ev->e->stream);
-    freeEventsHostSide(ev);
-    // A recorded sequence of this engine may replay launches that read this object's device memory: the handle is gone for the
-    // caller now, that memory goes when the last sequence does (or with the engine). A host that keeps one long-lived sequence and
-    // churns events objects so holds on to their device buffers only - state and signals -, not to pinned memory and events.
-    if (ev->e->liveSequences > 0)
-    {
-      ev->e->deferredFrees.push_back([ev]() { freeEventsDeviceSide(ev); });
-      return MLGPU_OK;
-    }
-    freeEventsDeviceSide(ev);
-    return MLGPU_OK;
+    return ev->e->release(ev, "events_destroy", [](mlgpu_events* ev) {
+      mlgpu_graph_forget_events(ev);  // graphs bound to this object (mlgpu_graph_bind_events) go back to "no events object"
+      for (mlgpu_events::Staging& st : ev->stage)
+      {
+        st.h_recs.reset();
+        st.h_dirty.reset();
+        st.done.reset();
+      }
+      for (mlgpu_events::CtlStaging& st : ev->ctlStage)
+      {
+        st.h_recs.reset();
+        st.h_recStart.reset();
+      }
+      std::vector<Instrument>().swap(ev->inst);
+      std::vector<std::vector<Rec>>().swap(ev->laneRecs);
+      std::vector<std::vector<CtlRec>>().swap(ev->ctlLaneRecs);
+    });
   }
 
   int mlgpu_events_clear(mlgpu_events* ev)  // EventsToSignals::clear, :330-340
@@ -1445,7 +1402,7 @@ extern "C"
     std::vector<uint32_t> st;
     initialState(ev, st);
     if (hipSetDevice(ev->e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    return mlgpu_upload(ev->e, ev->d_state, st.data(), st.size() * sizeof(uint32_t));
+    return mlgpu_upload(ev->e, ev->d_state.get(), st.data(), st.size() * sizeof(uint32_t));
   }
 
   int mlgpu_events_create(mlgpu_engine* e, size_t nInstruments, int polyphony, mlgpu_events** out)
@@ -1457,7 +1414,7 @@ extern "C"
       e->lastError = "events_create: 1+ instruments, polyphony 1..16 (EventsToSignals::kMaxVoices)";
       return MLGPU_ERR_INVALID;
     }
-    mlgpu_events* ev = new (std::nothrow) mlgpu_events();
+    std::unique_ptr<mlgpu_events> ev(new (std::nothrow) mlgpu_events());
     if (!ev) return MLGPU_ERR_OOM;
     ev->e = e;
     for (int& x : ev->slotOf) x = -1;
@@ -1471,33 +1428,28 @@ extern "C"
     ev->inst.resize(nInstruments);
     ev->laneRecs.resize(ev->maxLanes);
     hipError_t err = hipSetDevice(e->device);
-    if (err == hipSuccess) err = hipMalloc((void**)&ev->d_state, sizeof(uint32_t) * (size_t)kStateWords * ev->maxLanes);
-    if (err == hipSuccess) err = hipMalloc((void**)&ev->d_recRange, sizeof(uint2) * ev->maxLanes);
-    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange, 0, sizeof(uint2) * ev->maxLanes, e->stream);
+    if (err == hipSuccess) err = allocate(ev->d_state, (size_t)kStateWords * ev->maxLanes);
+    if (err == hipSuccess) err = allocate(ev->d_recRange, ev->maxLanes);
+    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * ev->maxLanes, e->stream);
     for (mlgpu_events::Staging& st : ev->stage)
-      if (err == hipSuccess) err = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
+      if (err == hipSuccess) err = allocate(st.done, hipEventDisableTiming);
     if (err != hipSuccess)
     {
       e->lastError = std::string("events_create: ") + hipGetErrorString(err);
-      mlgpu_events_destroy(ev);
       return err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP;
     }
     for (Instrument& in : ev->inst) in.lastFreeVoiceFound = -1;
-    const int st = mlgpu_events_clear(ev);
+    const int st = mlgpu_events_clear(ev.get());
     for (Instrument& in : ev->inst) in.lastFreeVoiceFound = 0;  // setPolyphony calls clear() (:316-321)
-    if (st != MLGPU_OK)
-    {
-      mlgpu_events_destroy(ev);
-      return st;
-    }
-    *out = ev;
+    if (st != MLGPU_OK) return st;
+    *out = ev.release();
     return MLGPU_OK;
   }
 
   static int markRecalc(mlgpu_events* ev)
   {
     if (hipSetDevice(ev->e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    return mlgpu_fill32(ev->e, ev->d_state + (size_t)S_RECALC * ev->lanes(), 1u, ev->lanes());
+    return mlgpu_fill32(ev->e, ev->d_state.get() + (size_t)S_RECALC * ev->lanes(), 1u, ev->lanes());
   }
   int mlgpu_events_set_sample_rate(mlgpu_events* ev, double sr)
   {
@@ -1583,11 +1535,8 @@ extern "C"
     for (uint32_t l : ev->ctlDirty) nRecs += ev->ctlLaneRecs[l].size();
     if (nRecs + 1 > sg.recCapacity)
     {
-      if (sg.h_recs) hipHostFree(sg.h_recs);
-      if (sg.d_recs) hipFree(sg.d_recs);
-      sg.h_recs = sg.d_recs = nullptr;
       sg.recCapacity = std::max<size_t>(1024, 2 * (nRecs + 1));
-      if (hipMalloc((void**)&sg.d_recs, sizeof(CtlRec) * sg.recCapacity) != hipSuccess || hipHostMalloc((void**)&sg.h_recs, sizeof(CtlRec) * sg.recCapacity) != hipSuccess)
+      if (allocate(sg.d_recs, sg.recCapacity) != hipSuccess || allocate(sg.h_recs, sg.recCapacity) != hipSuccess)
       {
         sg.recCapacity = 0;
         return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
@@ -1599,18 +1548,18 @@ extern "C"
     {
       for (; next <= l; ++next) sg.h_recStart[next] = (uint32_t)n;
       const std::vector<CtlRec>& lr = ev->ctlLaneRecs[l];
-      memcpy(sg.h_recs + n, lr.data(), sizeof(CtlRec) * lr.size());
+      memcpy(sg.h_recs.get() + n, lr.data(), sizeof(CtlRec) * lr.size());
       n += lr.size();
     }
     for (; next <= lanes; ++next) sg.h_recStart[next] = (uint32_t)n;
-    hipError_t err = hipMemcpyAsync(sg.d_recStart, sg.h_recStart, sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs, sg.h_recs, sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream);
+    hipError_t err = hipMemcpyAsync(sg.d_recStart.get(), sg.h_recStart.get(), sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream);
     if (err != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process controller upload: ") + hipGetErrorString(err));
     CtlArgs a;
-    a.state = ev->d_ctlState;
-    a.recs = sg.d_recs;
-    a.recStart = sg.d_recStart;
-    a.out = ev->d_ctlOut;
+    a.state = ev->d_ctlState.get();
+    a.recs = sg.d_recs.get();
+    a.recStart = sg.d_recStart.get();
+    a.out = ev->d_ctlOut.get();
     a.nInstruments = ev->nInstruments;
     a.lanes = lanes;
     a.T = nVectors;
@@ -1635,11 +1584,11 @@ extern "C"
   static void abandonRanges(mlgpu_events* ev, mlgpu_events::Staging& sg)
   {
     if (!sg.nDirtySet) return;
-    hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream, (const uint4*)sg.d_dirty, sg.nDirtySet, ev->d_recRange);
+    hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream, (const uint4*)sg.d_dirty.get(), sg.nDirtySet, ev->d_recRange.get());
     (void)hipGetLastError();
     sg.nDirtySet = 0;
     // (the list must outlive the clearing pass: the next use of this staging buffer waits for `done`)
-    if (hipEventRecord(sg.done, ev->e->stream) == hipSuccess) sg.pending = true;
+    if (hipEventRecord(sg.done.get(), ev->e->stream) == hipSuccess) sg.pending = true;
   }
 
   static int prepare(mlgpu_events* ev, size_t nVectors, int startOffset, EventsDev& dev, mlgpu_events::Staging*& sgOut)
@@ -1682,17 +1631,14 @@ extern "C"
     mlgpu_events::Staging& sg = ev->stage[ev->stageIdx];
     sgOut = &sg;
     ev->stageIdx ^= 1;
-    if (sg.pending && hipEventSynchronize(sg.done) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
+    if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
     sg.pending = false;
     size_t nRecs = 0;
     for (uint32_t l : ev->dirtyLanes) nRecs += ev->laneRecs[l].size();
     if (nRecs + 1 > sg.recCapacity)
     {
-      if (sg.h_recs) hipHostFree(sg.h_recs);
-      if (sg.d_recs) hipFree(sg.d_recs);
-      sg.h_recs = sg.d_recs = nullptr;
       sg.recCapacity = std::max<size_t>(4096, 2 * (nRecs + 1));
-      if (hipMalloc((void**)&sg.d_recs, sizeof(Rec) * sg.recCapacity) != hipSuccess || hipHostMalloc((void**)&sg.h_recs, sizeof(Rec) * sg.recCapacity) != hipSuccess)
+      if (allocate(sg.d_recs, sg.recCapacity) != hipSuccess || allocate(sg.h_recs, sg.recCapacity) != hipSuccess)
       {
         sg.recCapacity = 0;
         return efail(ev, MLGPU_ERR_OOM, "events_process: record buffer");
@@ -1701,11 +1647,8 @@ extern "C"
     const size_t nDirty = ev->dirtyLanes.size();
     if (nDirty > sg.dirtyCapacity)
     {
-      if (sg.h_dirty) hipHostFree(sg.h_dirty);
-      if (sg.d_dirty) hipFree(sg.d_dirty);
-      sg.h_dirty = sg.d_dirty = nullptr;
       sg.dirtyCapacity = std::max<size_t>(1024, 2 * nDirty);
-      if (hipMalloc((void**)&sg.d_dirty, sizeof(uint4) * sg.dirtyCapacity) != hipSuccess || hipHostMalloc((void**)&sg.h_dirty, sizeof(uint4) * sg.dirtyCapacity) != hipSuccess)
+      if (allocate(sg.d_dirty, sg.dirtyCapacity) != hipSuccess || allocate(sg.h_dirty, sg.dirtyCapacity) != hipSuccess)
       {
         sg.dirtyCapacity = 0;
         return efail(ev, MLGPU_ERR_OOM, "events_process: lane list");
@@ -1717,17 +1660,17 @@ extern "C"
       for (uint32_t l : ev->dirtyLanes)
       {
         const std::vector<Rec>& lr = ev->laneRecs[l];
-        memcpy(sg.h_recs + n, lr.data(), sizeof(Rec) * lr.size());
+        memcpy(sg.h_recs.get() + n, lr.data(), sizeof(Rec) * lr.size());
         sg.h_dirty[i++] = make_uint4(l, (uint32_t)n, (uint32_t)(n + lr.size()), 0u);
         n += lr.size();
       }
     }
     hipError_t cerr = hipSuccess;
-    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty, sg.h_dirty, sizeof(uint4) * nDirty, hipMemcpyHostToDevice, e->stream);
-    if (cerr == hipSuccess && nRecs) cerr = hipMemcpyAsync(sg.d_recs, sg.h_recs, sizeof(Rec) * nRecs, hipMemcpyHostToDevice, e->stream);
+    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(uint4) * nDirty, hipMemcpyHostToDevice, e->stream);
+    if (cerr == hipSuccess && nRecs) cerr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(Rec) * nRecs, hipMemcpyHostToDevice, e->stream);
     if (cerr == hipSuccess && nDirty)
     {
-      hipLaunchKernelGGL(set_rec_ranges_kernel, dim3((unsigned)((nDirty + 255) / 256)), dim3(256), 0, e->stream, (const uint4*)sg.d_dirty, nDirty, ev->d_recRange);
+      hipLaunchKernelGGL(set_rec_ranges_kernel, dim3((unsigned)((nDirty + 255) / 256)), dim3(256), 0, e->stream, (const uint4*)sg.d_dirty.get(), nDirty, ev->d_recRange.get());
       cerr = hipGetLastError();
       if (cerr == hipSuccess) sg.nDirtySet = nDirty;
     }
@@ -1759,16 +1702,16 @@ extern "C"
     dev.s.mpe = ev->mpe ? 1 : 0;
     dev.ctl = nullptr;
     dev.rowP = dev.rowG = nullptr;
-    dev.state = ev->d_state;
-    dev.recs = sg.d_recs;
-    dev.recRange = ev->d_recRange;
+    dev.state = ev->d_state.get();
+    dev.recs = sg.d_recs.get();
+    dev.recRange = ev->d_recRange.get();
     dev.lanes = lanes;
     return MLGPU_OK;
   }
   static int launched(mlgpu_events* ev, mlgpu_events::Staging& sg)
   {
     sg.nDirtySet = 0;  // (the consuming kernel clears the ranges it read)
-    if (hipEventRecord(sg.done, ev->e->stream) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: event");
+    if (hipEventRecord(sg.done.get(), ev->e->stream) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: event");
     sg.pending = true;  // no wait here: the host goes on routing the next block while this one runs
     return MLGPU_OK;
   }
@@ -1831,21 +1774,17 @@ extern "C"
     const size_t lanes = ev->lanes();
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     hipStreamSynchronize(e->stream);
-    hipFree(ev->d_ctlRecs);
-    hipFree(ev->d_rowP);
-    hipFree(ev->d_rowG);
-    ev->d_ctlRecs = nullptr;
-    ev->d_rowP = ev->d_rowG = nullptr;
+    // recorded graph launches have these pointers baked in: the old buffers are retired, the new ones serve from now on
+    e->retire(std::move(ev->d_ctlRecs));
+    e->retire(std::move(ev->d_rowP));
+    e->retire(std::move(ev->d_rowG));
     ev->ctlRecVectors = 0;
-    const size_t rowBytes = sizeof(float) * 64 * nVectors * lanes;
-    if (hipMalloc((void**)&ev->d_ctlRecs, sizeof(uint32_t) * kCtlRecWords * nVectors * lanes) != hipSuccess || hipMalloc((void**)&ev->d_rowP, rowBytes) != hipSuccess ||
-        hipMalloc((void**)&ev->d_rowG, rowBytes) != hipSuccess)
+    if (allocate(ev->d_ctlRecs, kCtlRecWords * nVectors * lanes) != hipSuccess || allocate(ev->d_rowP, 64 * nVectors * lanes) != hipSuccess ||
+        allocate(ev->d_rowG, 64 * nVectors * lanes) != hipSuccess)
     {
-      hipFree(ev->d_ctlRecs);
-      hipFree(ev->d_rowP);
-      hipFree(ev->d_rowG);
-      ev->d_ctlRecs = nullptr;
-      ev->d_rowP = ev->d_rowG = nullptr;
+      ev->d_ctlRecs.reset();
+      ev->d_rowP.reset();
+      ev->d_rowG.reset();
       return efail(ev, MLGPU_ERR_OOM, "events as graph source nodes: control records and side signals");
     }
     ev->ctlRecVectors = nVectors;
@@ -1899,9 +1838,9 @@ extern "C"
     a.state = dev->state;
     a.recs = (const Rec*)dev->recs;
     a.recRange = dev->recRange;
-    a.ctl = ev->d_ctlRecs;
-    a.rowP = (float4*)ev->d_rowP;
-    a.rowG = (float4*)ev->d_rowG;
+    a.ctl = ev->d_ctlRecs.get();
+    a.rowP = (float4*)ev->d_rowP.get();
+    a.rowG = (float4*)ev->d_rowG.get();
     a.lanes = lanes;
     a.T = nVectors;
     a.flags = e->kflags;
@@ -1913,9 +1852,9 @@ extern "C"
       abandonRanges(ev, *sg);
       return efail(ev, MLGPU_ERR_HIP, std::string("events control kernel launch: ") + hipGetErrorString(err));
     }
-    dev->ctl = ev->d_ctlRecs;
-    dev->rowP = (const float4*)ev->d_rowP;
-    dev->rowG = (const float4*)ev->d_rowG;
+    dev->ctl = ev->d_ctlRecs.get();
+    dev->rowP = (const float4*)ev->d_rowP.get();
+    dev->rowG = (const float4*)ev->d_rowG.get();
     return MLGPU_OK;
   }
   // the graph's voice kernel (which consumes the ranges) could not be launched after prepare_for_graph had succeeded
@@ -1954,12 +1893,10 @@ extern "C"
       }
       if (e->liveSequences > 0)
         return efail(ev, MLGPU_ERR_INVALID, "events_watch_controllers would move the controller signals that recorded sequences of this engine may read: destroy them first");
-      float* fresh = nullptr;
-      const size_t bytes = sizeof(float) * 64 * maxVectors * ev->ctlLanes();
-      if (hipMalloc((void**)&fresh, bytes) != hipSuccess) return efail(ev, MLGPU_ERR_OOM, "events_watch_controllers: controller signals");
-      hipMemsetAsync(fresh, 0, bytes, e->stream);
-      hipFree(ev->d_ctlOut);
-      ev->d_ctlOut = fresh;
+      DeviceBuffer<float> fresh;
+      if (allocate(fresh, 64 * maxVectors * ev->ctlLanes()) != hipSuccess) return efail(ev, MLGPU_ERR_OOM, "events_watch_controllers: controller signals");
+      hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * ev->ctlLanes(), e->stream);
+      ev->d_ctlOut = std::move(fresh);
       ev->ctlMaxVectors = ev->ctlCapacityVectors = maxVectors;
       return MLGPU_OK;
     }
@@ -1972,14 +1909,14 @@ extern "C"
     ev->ctlMaxVectors = ev->ctlCapacityVectors = maxVectors;
     const size_t lanes = ev->ctlLanes();
     ev->ctlLaneRecs.resize(lanes);
-    hipError_t err = hipMalloc((void**)&ev->d_ctlOut, sizeof(float) * 64 * maxVectors * lanes);
-    if (err == hipSuccess) err = hipMalloc((void**)&ev->d_ctlState, sizeof(uint32_t) * (size_t)kCtlWords * lanes);
+    hipError_t err = allocate(ev->d_ctlOut, 64 * maxVectors * lanes);
+    if (err == hipSuccess) err = allocate(ev->d_ctlState, (size_t)kCtlWords * lanes);
     for (mlgpu_events::CtlStaging& st : ev->ctlStage)
     {
-      if (err == hipSuccess) err = hipMalloc((void**)&st.d_recStart, sizeof(uint32_t) * (lanes + 1));
-      if (err == hipSuccess) err = hipHostMalloc((void**)&st.h_recStart, sizeof(uint32_t) * (lanes + 1));
+      if (err == hipSuccess) err = allocate(st.d_recStart, lanes + 1);
+      if (err == hipSuccess) err = allocate(st.h_recStart, lanes + 1);
     }
-    if (err == hipSuccess) err = hipMemsetAsync(ev->d_ctlOut, 0, sizeof(float) * 64 * maxVectors * lanes, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(ev->d_ctlOut.get(), 0, sizeof(float) * 64 * maxVectors * lanes, e->stream);
     if (err != hipSuccess)
     {
       freeControllers(ev);
@@ -2004,12 +1941,12 @@ extern "C"
         W(C_GLIDE + 3, lane) = 1u;           // mCurrVec is one value
         W(C_GLIDE + 4, lane) = bits;
       }
-    return mlgpu_upload(e, ev->d_ctlState, st.data(), st.size() * sizeof(uint32_t));
+    return mlgpu_upload(e, ev->d_ctlState.get(), st.data(), st.size() * sizeof(uint32_t));
   }
   const float* mlgpu_events_controller_signal(mlgpu_events* ev, int slot)
   {
     if (!ev || slot < 0 || (size_t)slot >= ev->watched.size()) return nullptr;
-    return ev->d_ctlOut + (size_t)slot * 64 * ev->ctlCapacityVectors * ev->nInstruments;
+    return ev->d_ctlOut.get() + (size_t)slot * 64 * ev->ctlCapacityVectors * ev->nInstruments;
   }
   int mlgpu_events_is_midi(mlgpu_events* ev) { return (ev && !ev->mpe) ? 1 : 0; }
   mlgpu_engine* mlgpu_events_engine(mlgpu_events* ev) { return ev ? ev->e : nullptr; }

@@ -141,13 +141,13 @@ struct mlgpu_graph
   bool strictSvf{false};  // the engine's mode when the graph was made (mlgpu_engine_set_strict_svf)
   std::string source, log;
   hipFunction_t fn{nullptr};
-  float* d_coeffs{nullptr};
-  uint32_t* d_state{nullptr};
-  float* d_params{nullptr};
-  float* d_consts{nullptr};      // live constants: [nConsts] floats
+  DeviceBuffer<float> d_coeffs;
+  DeviceBuffer<uint32_t> d_state;
+  DeviceBuffer<float> d_params;
+  DeviceBuffer<float> d_consts;  // live constants: [nConsts] floats
   int nConsts{0};
   bool liveConsts{false};        // const nodes read d_consts instead of being literals of the generated code
-  float* d_mem{nullptr};
+  DeviceBuffer<float> d_mem;
   std::vector<char> emitted;     // mlgpu_graph_emit: the gfx950 code object
   size_t memFloatsPerVoice{0};
   int delayLayout{0};            // as mlgpu_graph_set_delay_layout took it (3: the best of 2 / 4 / 1 for the graph)
@@ -194,7 +194,7 @@ struct mlgpu_graph
   };
   bool autotune{false}, tuned{false};
   std::vector<Variant> variants;
-  hipEvent_t tuneEv0{nullptr}, tuneEv1{nullptr};
+  OwnedEvent tuneEv0, tuneEv1;
   int activeVl{1};               // of the kernel in `fn`
   int inLayoutOverride[MLGPU_GRAPH_MAX_INPUTS];  // -1: none
   mlgpu_graph()
@@ -1289,28 +1289,19 @@ extern "C"
   int mlgpu_graph_destroy(mlgpu_graph* g)
   {
     if (!g) return MLGPU_ERR_INVALID;
-    if (g->job)  // a compile in flight owns the graph: wait for it (seconds at most), then let it go
+    const auto forget = [](mlgpu_graph* g)
     {
-      g->job->th.join();
-      delete g->job;
-      g->job = nullptr;
-    }
-    {
+      if (g->job)  // a compile in flight owns the graph: wait for it (seconds at most), then let it go
+      {
+        g->job->th.join();
+        delete g->job;
+        g->job = nullptr;
+      }
       std::lock_guard<std::mutex> lock(g_boundMutex);
       g_boundGraphs.erase(g);
-    }
-    if (g->e)
-    {
-      hipSetDevice(g->e->device);
-      hipStreamSynchronize(g->e->stream);
-    }
-    if (g->d_coeffs) hipFree(g->d_coeffs);
-    if (g->d_state) hipFree(g->d_state);
-    if (g->d_params) hipFree(g->d_params);
-    if (g->d_consts) hipFree(g->d_consts);
-    if (g->d_mem) hipFree(g->d_mem);
-    if (g->tuneEv0) hipEventDestroy(g->tuneEv0);
-    if (g->tuneEv1) hipEventDestroy(g->tuneEv1);
+    };
+    if (g->e) return g->e->release(g, "graph_destroy", forget);
+    forget(g);  // a graph for mlgpu_graph_emit only: no device memory
     delete g;
     return MLGPU_OK;
   }
@@ -1876,24 +1867,24 @@ extern "C"
       g->tuned = g->variants.size() < 2;
     }
     const size_t V = g->V;
-    hipError_t err = hipMalloc((void**)&g->d_coeffs, sizeof(float) * V * (size_t)(g->NC + 1));
-    if (err == hipSuccess) err = hipMalloc((void**)&g->d_state, sizeof(uint32_t) * V * (size_t)(g->NS + 1));
-    if (err == hipSuccess) err = hipMalloc((void**)&g->d_params, sizeof(float) * V * (size_t)(g->nParams + 1));
+    hipError_t err = allocate(g->d_coeffs, V * (size_t)(g->NC + 1));
+    if (err == hipSuccess) err = allocate(g->d_state, V * (size_t)(g->NS + 1));
+    if (err == hipSuccess) err = allocate(g->d_params, V * (size_t)(g->nParams + 1));
     const size_t memV = g->memVoices();
-    if (err == hipSuccess && g->memFloatsPerVoice) err = hipMalloc((void**)&g->d_mem, sizeof(float) * memV * g->memFloatsPerVoice);
-    if (err == hipSuccess && g->memFloatsPerVoice) err = hipMemsetAsync(g->d_mem, 0, sizeof(float) * memV * g->memFloatsPerVoice, e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_state, 0, sizeof(uint32_t) * V * (size_t)(g->NS + 1), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_coeffs, 0, sizeof(float) * V * (size_t)(g->NC + 1), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_params, 0, sizeof(float) * V * (size_t)(g->nParams + 1), e->stream);
+    if (err == hipSuccess && g->memFloatsPerVoice) err = allocate(g->d_mem, memV * g->memFloatsPerVoice);
+    if (err == hipSuccess && g->memFloatsPerVoice) err = hipMemsetAsync(g->d_mem.get(), 0, sizeof(float) * memV * g->memFloatsPerVoice, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_state.get(), 0, sizeof(uint32_t) * V * (size_t)(g->NS + 1), e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_coeffs.get(), 0, sizeof(float) * V * (size_t)(g->NC + 1), e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_params.get(), 0, sizeof(float) * V * (size_t)(g->nParams + 1), e->stream);
     if (err == hipSuccess && g->liveConsts)
     {
-      err = hipMalloc((void**)&g->d_consts, sizeof(float) * (size_t)(g->nConsts + 1));
+      err = allocate(g->d_consts, (size_t)(g->nConsts + 1));
       for (const Node& n : g->nodes)
         if (n.type == NODE_CONST && err == hipSuccess)
         {
           uint32_t u;
           memcpy(&u, &n.value, 4);
-          err = mlgpu_launch_fill32((uint32_t*)g->d_consts + n.slot, u, 1, e->stream);
+          err = mlgpu_launch_fill32((uint32_t*)g->d_consts.get() + n.slot, u, 1, e->stream);
         }
     }
     for (const Node& n : g->nodes)
@@ -1905,12 +1896,12 @@ extern "C"
       {
         uint32_t u;
         memcpy(&u, &dc[i], 4);
-        if (u) err = mlgpu_launch_fill32((uint32_t*)g->d_coeffs + (size_t)(n.cOff + i) * V, u, V, e->stream);
+        if (u) err = mlgpu_launch_fill32((uint32_t*)g->d_coeffs.get() + (size_t)(n.cOff + i) * V, u, V, e->stream);
       }
       uint32_t words[MLGPU_MAX_PROC_STATE];
       mlgpu_proc_clear_state(n.kind, words, false);
       for (int i = 0; i < n.ns && err == hipSuccess; ++i)
-        err = mlgpu_launch_fill32(g->d_state + (size_t)(n.sOff + i) * V, words[i], V, e->stream);
+        err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * V, words[i], V, e->stream);
     }
     if (err != hipSuccess) return gfail(g, err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP, std::string("graph_compile: ") + hipGetErrorString(err));
     g->compiled = true;
@@ -1926,7 +1917,7 @@ extern "C"
     hipError_t err = hipSetDevice(g->e->device);  // (a host thread may drive engines on several devices in turn)
     if (n.type == NODE_FEEDBACK)
     {
-      for (int i = 0; i < n.ns && err == hipSuccess; ++i) err = mlgpu_launch_fill32(g->d_state + (size_t)(n.sOff + i) * g->V, 0u, g->V, g->e->stream);
+      for (int i = 0; i < n.ns && err == hipSuccess; ++i) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->V, 0u, g->V, g->e->stream);
     }
     else if (n.type == NODE_PROC)
     {
@@ -1934,9 +1925,9 @@ extern "C"
       mlgpu_proc_clear_state(n.kind, words, true);
       const uint64_t mask = mlgpu_proc_clear_mask(n.kind);
       for (int i = 0; i < n.ns && err == hipSuccess; ++i)
-        if ((mask >> (i < 64 ? i : 63)) & 1) err = mlgpu_launch_fill32(g->d_state + (size_t)(n.sOff + i) * g->V, words[i], g->V, g->e->stream);
+        if ((mask >> (i < 64 ? i : 63)) & 1) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->V, words[i], g->V, g->e->stream);
       if (err == hipSuccess && n.ringLen)
-        err = mlgpu_launch_fill32((uint32_t*)g->d_mem + n.memOff * g->memVoices(), 0u, n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * g->memVoices(), g->e->stream);
+        err = mlgpu_launch_fill32((uint32_t*)g->d_mem.get() + n.memOff * g->memVoices(), 0u, n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * g->memVoices(), g->e->stream);
     }
     if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, hipGetErrorString(err));
     return MLGPU_OK;
@@ -1971,7 +1962,7 @@ extern "C"
     int st = checkNode(g, node, NODE_PARAM);
     if (st) return st;
     if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_set_param: compile first / null");
-    return mlgpu_upload(g->e, g->d_params + (size_t)g->nodes[node].slot * g->V, h, sizeof(float) * g->V);
+    return mlgpu_upload(g->e, g->d_params.get() + (size_t)g->nodes[node].slot * g->V, h, sizeof(float) * g->V);
   }
   int mlgpu_graph_set_param_uniform(mlgpu_graph* g, int node, float value)
   {
@@ -1980,7 +1971,7 @@ extern "C"
     if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph_set_param: compile first");
     uint32_t u;
     memcpy(&u, &value, 4);
-    return mlgpu_fill32(g->e, g->d_params + (size_t)g->nodes[node].slot * g->V, u, g->V);
+    return mlgpu_fill32(g->e, g->d_params.get() + (size_t)g->nodes[node].slot * g->V, u, g->V);
   }
   int mlgpu_graph_num_coeffs(mlgpu_graph* g, int node) { return checkNode(g, node, NODE_PROC) ? -1 : g->nodes[node].nc; }
   int mlgpu_graph_num_state(mlgpu_graph* g, int node) { return checkStateNode(g, node) ? -1 : g->nodes[node].ns; }
@@ -1990,7 +1981,7 @@ extern "C"
     if (st) return st;
     if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_set_coeff: compile first / null");
     if (idx < 0 || idx >= g->nodes[node].nc) return gfail(g, MLGPU_ERR_RANGE, "coefficient index out of range");
-    return mlgpu_upload(g->e, g->d_coeffs + (size_t)(g->nodes[node].cOff + idx) * g->V, h, sizeof(float) * g->V);
+    return mlgpu_upload(g->e, g->d_coeffs.get() + (size_t)(g->nodes[node].cOff + idx) * g->V, h, sizeof(float) * g->V);
   }
   int mlgpu_graph_set_coeff_uniform(mlgpu_graph* g, int node, int idx, float value)
   {
@@ -2000,7 +1991,7 @@ extern "C"
     if (idx < 0 || idx >= g->nodes[node].nc) return gfail(g, MLGPU_ERR_RANGE, "coefficient index out of range");
     uint32_t u;
     memcpy(&u, &value, 4);
-    return mlgpu_fill32(g->e, g->d_coeffs + (size_t)(g->nodes[node].cOff + idx) * g->V, u, g->V);
+    return mlgpu_fill32(g->e, g->d_coeffs.get() + (size_t)(g->nodes[node].cOff + idx) * g->V, u, g->V);
   }
   int mlgpu_graph_get_state(mlgpu_graph* g, int node, int idx, uint32_t* h)
   {
@@ -2008,7 +1999,7 @@ extern "C"
     if (st) return st;
     if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_get_state: compile first / null");
     if (idx < 0 || idx >= g->nodes[node].ns) return gfail(g, MLGPU_ERR_RANGE, "state index out of range");
-    return mlgpu_download(g->e, h, g->d_state + (size_t)(g->nodes[node].sOff + idx) * g->V, sizeof(uint32_t) * g->V);
+    return mlgpu_download(g->e, h, g->d_state.get() + (size_t)(g->nodes[node].sOff + idx) * g->V, sizeof(uint32_t) * g->V);
   }
   int mlgpu_graph_set_state(mlgpu_graph* g, int node, int idx, const uint32_t* h)
   {
@@ -2016,7 +2007,7 @@ extern "C"
     if (st) return st;
     if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_set_state: compile first / null");
     if (idx < 0 || idx >= g->nodes[node].ns) return gfail(g, MLGPU_ERR_RANGE, "state index out of range");
-    return mlgpu_upload(g->e, g->d_state + (size_t)(g->nodes[node].sOff + idx) * g->V, h, sizeof(uint32_t) * g->V);
+    return mlgpu_upload(g->e, g->d_state.get() + (size_t)(g->nodes[node].sOff + idx) * g->V, h, sizeof(uint32_t) * g->V);
   }
 
   int mlgpu_graph_set_delay_layout(mlgpu_graph* g, int windowed)
@@ -2055,7 +2046,7 @@ extern "C"
     if (!g->compiled) return MLGPU_OK;
     uint32_t u;
     memcpy(&u, &value, 4);
-    return mlgpu_fill32(g->e, g->d_consts + g->nodes[node].slot, u, 1);
+    return mlgpu_fill32(g->e, g->d_consts.get() + g->nodes[node].slot, u, 1);
   }
   // Same nodes, same wiring? (what a second capture of the same user code produces when only host-side numbers changed)
   static const char* structureDifference(const mlgpu_graph* a, const mlgpu_graph* b)
@@ -2163,7 +2154,7 @@ extern "C"
     if (st) return st;
     if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph_set_state: compile first");
     if (idx < 0 || idx >= g->nodes[node].ns) return gfail(g, MLGPU_ERR_RANGE, "state index out of range");
-    return mlgpu_fill32(g->e, g->d_state + (size_t)(g->nodes[node].sOff + idx) * g->V, value, g->V);
+    return mlgpu_fill32(g->e, g->d_state.get() + (size_t)(g->nodes[node].sOff + idx) * g->V, value, g->V);
   }
 
   int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
@@ -2196,16 +2187,16 @@ extern "C"
     if ((g->nInputs && !d_inputs) || (g->nControls && !d_controls) || !d_outputs) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null signal list");
     GraphArgs a;
     memset(&a, 0, sizeof(a));
-    a.coeffs = g->d_coeffs;
-    a.state = g->d_state;
-    a.params = g->d_params;
-    a.consts = g->d_consts;
-    a.mem = g->d_mem;
+    a.coeffs = g->d_coeffs.get();
+    a.state = g->d_state.get();
+    a.params = g->d_params.get();
+    a.consts = g->d_consts.get();
+    a.mem = g->d_mem.get();
     a.V = g->V;
     a.T = T;
     a.t0 = g->vectorCount;
     a.flags = g->e->kflags;
-    a.impulseTable = g->e->d_impulseTable;
+    a.impulseTable = g->e->d_impulseTable.get();
     for (int i = 0; i < g->nInputs; ++i)
     {
       if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null / misaligned input");
@@ -2229,7 +2220,7 @@ extern "C"
     for (size_t o = 0; o < g->outputs.size(); ++o)
       if (g->outputMix[o])
       {
-        a.out[o] = makeView(g->e->d_mixScratch + nMix * mixRegion, MLGPU_LAYOUT_QUAD, g->V, T);
+        a.out[o] = makeView(g->e->d_mixScratch.get() + nMix * mixRegion, MLGPU_LAYOUT_QUAD, g->V, T);
         ++nMix;
       }
     if (nMix * mixRegion > g->e->mixScratchFloats)
@@ -2281,7 +2272,7 @@ extern "C"
     }
     const hipFunction_t fn = trial ? trial->fn : g->fn;
     const int vl = trial ? trial->vl : g->activeVl;
-    if (trial && !g->tuneEv0 && (hipEventCreate(&g->tuneEv0) != hipSuccess || hipEventCreate(&g->tuneEv1) != hipSuccess))
+    if (trial && !g->tuneEv0 && (allocate(g->tuneEv0) != hipSuccess || allocate(g->tuneEv1) != hipSuccess))
       return gfail(g, MLGPU_ERR_HIP, "graph_process: hipEventCreate");
     // event rows: the host half of the EventsToSignals block (routing the block's events into records, their upload) goes first,
     // on the same stream; the kernel then walks the records itself
@@ -2294,7 +2285,7 @@ extern "C"
       g->eventOffset = -1;
       if (est != MLGPU_OK) return gfail(g, est, "graph_process: the events object refused the block (see its last error)");
     }
-    if (trial) hipEventRecord(g->tuneEv0, g->e->stream);
+    if (trial) hipEventRecord(g->tuneEv0.get(), g->e->stream);
     const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->V + (size_t)vl - 1) / (size_t)vl, g->e->stream);
     if (err != hipSuccess)
     {
@@ -2310,16 +2301,16 @@ extern "C"
       if (g->outputMix[o])
       {
         const hipError_t merr = g->outputMixShard[o]
-                                    ? mlgpu_launch_mixdown_rows_partial(mixGroups, T, g->e->d_mixScratch + r * mixRegion, d_outputs[o], mlgpu_mixdown_shard_level(g->V) - 1, g->e->stream, g->e->kflags)
-                                    : mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch + r * mixRegion, d_outputs[o], g->e->stream, g->e->kflags);
+                                    ? mlgpu_launch_mixdown_rows_partial(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], mlgpu_mixdown_shard_level(g->V) - 1, g->e->stream, g->e->kflags)
+                                    : mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream, g->e->kflags);
         if (merr != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "graph_process: the mixdown's later stages");
         ++r;
       }
     if (trial)
     {
-      hipEventRecord(g->tuneEv1, g->e->stream);
+      hipEventRecord(g->tuneEv1.get(), g->e->stream);
       float ms = 0.f;
-      if (hipEventSynchronize(g->tuneEv1) == hipSuccess && hipEventElapsedTime(&ms, g->tuneEv0, g->tuneEv1) == hipSuccess)
+      if (hipEventSynchronize(g->tuneEv1.get()) == hipSuccess && hipEventElapsedTime(&ms, g->tuneEv0.get(), g->tuneEv1.get()) == hipSuccess)
       {
         if (trial->runs >= 1) trial->bestMs = std::min(trial->bestMs, ms / (float)T);
         trial->runs++;

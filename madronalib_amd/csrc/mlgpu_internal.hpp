@@ -1,17 +1,54 @@
 // mlgpu_internal.hpp — shared between the translation units of libmlgpu.so (not installed).
 #pragma once
 #include <atomic>
-#include <functional>
-#include <vector>
+#include <memory>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mlgpu.h"
 #include "mlgpu_device_args.hpp"
+
+// Owning device memory, pinned host memory and HIP events: every handle frees what it holds by deleting its members
+struct DeviceFree
+{
+  static hipError_t allocate(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  void operator()(void* p) const { hipFree(p); }
+};
+struct HostFree
+{
+  static hipError_t allocate(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  void operator()(void* p) const { hipHostFree(p); }
+};
+struct EventDestroy
+{
+  void operator()(hipEvent_t ev) const { hipEventDestroy(ev); }
+};
+template <class T> using DeviceBuffer = std::unique_ptr<T[], DeviceFree>;
+template <class T> using PinnedBuffer = std::unique_ptr<T[], HostFree>;
+using OwnedEvent = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+
+// `out` replaced by `count` fresh elements (empty if that fails): the old buffer is freed first
+template <class T, class Free>
+hipError_t allocate(std::unique_ptr<T[], Free>& out, size_t count)
+{
+  out.reset();
+  T* p = nullptr;
+  const hipError_t err = Free::allocate((void**)&p, sizeof(T) * count);
+  out.reset(err == hipSuccess ? p : nullptr);
+  return err;
+}
+inline hipError_t allocate(OwnedEvent& out, unsigned flags = hipEventDefault)
+{
+  hipEvent_t ev = nullptr;
+  const hipError_t err = hipEventCreateWithFlags(&ev, flags);
+  out.reset(err == hipSuccess ? ev : nullptr);
+  return err;
+}
 
 struct mlgpu_engine
 {
@@ -20,33 +57,54 @@ struct mlgpu_engine
   bool ownsStream{false};
   int cuCount{256};
   std::string lastError;
-  float* d_impulseTable{nullptr};  // 17 floats (ImpulseGen windowed sinc), built on the host
-  hipEvent_t ev0{nullptr}, ev1{nullptr};
-  std::vector<hipEvent_t> lapEvents;  // mlgpu_timer_laps_*: created once, reused
+  DeviceBuffer<float> d_impulseTable;  // 17 floats (ImpulseGen windowed sinc), built on the host
+  OwnedEvent ev0, ev1;
+  std::vector<OwnedEvent> lapEvents;  // mlgpu_timer_laps_*: created once, reused
   size_t lapCount{0}, lapMax{0};
   bool jitEnabled{true};  // fuse unknown chains / graphs with hiprtc (mlgpu_engine_set_jit)
   bool strictSvf{false};  // banks and graphs made from now on get kernels compiled with MLGPU_SVF_STRICT 1 (mlgpu_engine_set_strict_svf)
-  float* d_mixScratch{nullptr};  // mixdown partial sums, grown on demand
+  DeviceBuffer<float> d_mixScratch;  // mixdown partial sums, grown on demand
   size_t mixScratchFloats{0};
-  unsigned long long* d_validate{nullptr};  // {count, first index} of mlgpu_validate, allocated with the engine
+  DeviceBuffer<unsigned long long> d_validate;  // {count, first index} of mlgpu_validate, allocated with the engine
   uint32_t kflags{0};  // MLGPU_KFLAG_* handed to every arithmetic kernel (mlgpu_engine_set_flush_denormals)
   bool recording{false};  // between mlgpu_engine_begin_recording and _end_recording: launches are captured, not run
   int liveSequences{0};   // recorded sequences not yet destroyed: they hold device pointers, so buffers handed out must not move
-  // objects destroyed while recorded sequences might still replay launches that read them: freed when the last sequence goes
-  // (mlgpu_sequence_destroy) or with the engine
-  std::vector<std::function<void()>> deferredFrees;
-  void runDeferredFrees()
+  // what recorded sequences might still replay launches that read (objects destroyed, buffers replaced): freed when the last
+  // sequence goes (mlgpu_sequence_destroy) or with the engine
+  std::vector<std::shared_ptr<void>> deferredFrees;
+  void runDeferredFrees() { std::vector<std::shared_ptr<void>>().swap(deferredFrees); }
+  // An object or buffer that recorded launches may read, given up: freed now, or with the last sequence while one lives
+  void retire(std::shared_ptr<void> owner)
   {
-    std::vector<std::function<void()>> todo;
-    todo.swap(deferredFrees);
-    for (auto& f : todo) f();
+    if (liveSequences > 0) deferredFrees.push_back(std::move(owner));
+  }
+  // The destroy function of every object this engine owns ends here. Refused while recording: waiting for the stream would
+  // invalidate the capture. Otherwise the stream is drained, `atOnce` frees what no replay reads, and the object is retired.
+  template <class T, class AtOnce>
+  int release(T* obj, const char* what, AtOnce atOnce)
+  {
+    if (recording)
+    {
+      lastError = std::string(what) + " waits for the device: not while recording a sequence";
+      return MLGPU_ERR_INVALID;
+    }
+    hipSetDevice(device);
+    hipStreamSynchronize(stream);
+    atOnce(obj);
+    retire(std::unique_ptr<T>(obj));
+    return MLGPU_OK;
+  }
+  template <class T>
+  int release(T* obj, const char* what)
+  {
+    return release(obj, what, [](T*) {});
   }
 };
 
 struct mlgpu_fence  // mlgpu_engine_signal / mlgpu_engine_wait: a point in one engine's stream that another engine's stream can wait for
 {
   int device{0};
-  hipEvent_t ev{nullptr};
+  OwnedEvent ev;
   std::atomic<bool> signalled{false};  // set by the signalling engine's host thread, read by the waiting engine's
 };
 

@@ -39,9 +39,9 @@ struct mlgpu_process_buffer
   // set 0 only; the pipelined mode alternates, so block k + 1 is gathered and uploaded while block k is still on the device
   struct Stage
   {
-    float* h{nullptr};
-    float* d{nullptr};
-    hipEvent_t done{nullptr};
+    PinnedBuffer<float> h;
+    DeviceBuffer<float> d;
+    OwnedEvent done;
     size_t K{0};          // vectors in flight in this set (0: nothing pending)
   } stage[2];
   int cur{0};
@@ -50,6 +50,11 @@ struct mlgpu_process_buffer
   size_t syncRingSize{0}; // size of an output ring of the synchronous mode (the K rule saturates there)
   std::vector<const float*> d_in;
   std::vector<float*> d_out;
+  ~mlgpu_process_buffer()
+  {
+    for (auto* b : in) mlgpu_dspbuffer_destroy(b);
+    for (auto* b : out) mlgpu_dspbuffer_destroy(b);
+  }
 };
 
 namespace
@@ -58,7 +63,7 @@ namespace
 int retire(mlgpu_process_buffer* p, mlgpu_process_buffer::Stage& sg)
 {
   if (!sg.K) return MLGPU_OK;
-  if (hipEventSynchronize(sg.done) != hipSuccess)
+  if (hipEventSynchronize(sg.done.get()) != hipSuccess)
   {
     p->e->lastError = "process_buffer_process: waiting for a block";
     return MLGPU_ERR_HIP;
@@ -66,7 +71,7 @@ int retire(mlgpu_process_buffer* p, mlgpu_process_buffer::Stage& sg)
   const size_t nIn = p->in.size(), nOut = p->out.size(), chan = sg.K * MLGPU_FLOATS_PER_DSPVECTOR;
   for (size_t k = 0; k < sg.K; ++k)
     for (size_t c = 0; c < nOut; ++c)
-      mlgpu_dspbuffer_write(p->out[c], sg.h + (nIn + c) * chan + k * MLGPU_FLOATS_PER_DSPVECTOR, MLGPU_FLOATS_PER_DSPVECTOR);
+      mlgpu_dspbuffer_write(p->out[c], sg.h.get() + (nIn + c) * chan + k * MLGPU_FLOATS_PER_DSPVECTOR, MLGPU_FLOATS_PER_DSPVECTOR);
   sg.K = 0;
   return MLGPU_OK;
 }
@@ -77,26 +82,7 @@ extern "C"
   int mlgpu_process_buffer_destroy(mlgpu_process_buffer* p)
   {
     if (!p) return MLGPU_ERR_INVALID;
-    if (p->e && p->e->recording)
-    {
-      p->e->lastError = "process_buffer_destroy waits for the device: not while recording a sequence";
-      return MLGPU_ERR_INVALID;
-    }
-    if (p->e)
-    {
-      hipSetDevice(p->e->device);
-      hipStreamSynchronize(p->e->stream);
-    }
-    for (auto* b : p->in) mlgpu_dspbuffer_destroy(b);
-    for (auto* b : p->out) mlgpu_dspbuffer_destroy(b);
-    for (auto& sg : p->stage)
-    {
-      if (sg.h) hipHostFree(sg.h);
-      if (sg.d) hipFree(sg.d);
-      if (sg.done) hipEventDestroy(sg.done);
-    }
-    delete p;
-    return MLGPU_OK;
+    return p->e->release(p, "process_buffer_destroy");
   }
 
   int mlgpu_process_buffer_create(mlgpu_engine* e, size_t nInputs, size_t nOutputs, size_t maxFrames, mlgpu_process_buffer** out)
@@ -109,7 +95,7 @@ extern "C"
       e->lastError = "process_buffer_create: bad sizes";
       return MLGPU_ERR_INVALID;
     }
-    mlgpu_process_buffer* p = new (std::nothrow) mlgpu_process_buffer();
+    std::unique_ptr<mlgpu_process_buffer> p(new (std::nothrow) mlgpu_process_buffer());
     if (!p) return MLGPU_ERR_OOM;
     p->e = e;
     p->maxFrames = maxFrames;
@@ -122,8 +108,7 @@ extern "C"
       // when a host overdrives them (a ring that is full overwrites its oldest data, MLDSPBuffer.h:162-167)
       if (!b || mlgpu_dspbuffer_resize(b, (int)maxFrames) == 0)
       {
-        if (b) mlgpu_dspbuffer_destroy(b);
-        mlgpu_process_buffer_destroy(p);
+        mlgpu_dspbuffer_destroy(b);
         return MLGPU_ERR_OOM;
       }
       (i < nInputs ? p->in : p->out).push_back(b);
@@ -133,19 +118,18 @@ extern "C"
     hipError_t err = hipSetDevice(e->device);
     for (auto& sg : p->stage)
     {
-      if (err == hipSuccess) err = hipHostMalloc((void**)&sg.h, sizeof(float) * (floats + 4), hipHostMallocDefault);
-      if (err == hipSuccess) err = hipMalloc((void**)&sg.d, sizeof(float) * (floats + 4));
-      if (err == hipSuccess) err = hipEventCreateWithFlags(&sg.done, hipEventDisableTiming);
+      if (err == hipSuccess) err = allocate(sg.h, floats + 4);
+      if (err == hipSuccess) err = allocate(sg.d, floats + 4);
+      if (err == hipSuccess) err = allocate(sg.done, hipEventDisableTiming);
     }
     if (err != hipSuccess)
     {
       e->lastError = std::string("process_buffer_create: ") + hipGetErrorString(err);
-      mlgpu_process_buffer_destroy(p);
       return err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP;
     }
     p->d_in.resize(nInputs);
     p->d_out.resize(nOutputs);
-    *out = p;
+    *out = p.release();
     return MLGPU_OK;
   }
 
@@ -213,20 +197,20 @@ extern "C"
       const size_t chan = K * MLGPU_FLOATS_PER_DSPVECTOR;  // floats per channel in this block
       for (size_t c = 0; c < nIn; ++c)
         for (size_t k = 0; k < K; ++k)  // one DSPVector at a time: zeros when the ring runs dry (DSPBuffer::read(), :257)
-          mlgpu_dspbuffer_read_vector(p->in[c], sg.h + c * chan + k * MLGPU_FLOATS_PER_DSPVECTOR);
+          mlgpu_dspbuffer_read_vector(p->in[c], sg.h.get() + c * chan + k * MLGPU_FLOATS_PER_DSPVECTOR);
       hipError_t err = hipSetDevice(e->device);
-      if (err == hipSuccess && nIn) err = hipMemcpyAsync(sg.d, sg.h, sizeof(float) * nIn * chan, hipMemcpyHostToDevice, e->stream);
+      if (err == hipSuccess && nIn) err = hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(float) * nIn * chan, hipMemcpyHostToDevice, e->stream);
       if (err != hipSuccess)
       {
         e->lastError = std::string("process_buffer_process (H2D): ") + hipGetErrorString(err);
         return MLGPU_ERR_HIP;
       }
-      for (size_t c = 0; c < nIn; ++c) p->d_in[c] = sg.d + c * chan;
-      for (size_t c = 0; c < nOut; ++c) p->d_out[c] = sg.d + (nIn + c) * chan;
+      for (size_t c = 0; c < nIn; ++c) p->d_in[c] = sg.d.get() + c * chan;
+      for (size_t c = 0; c < nOut; ++c) p->d_out[c] = sg.d.get() + (nIn + c) * chan;
       const int st = fn(user, K, p->d_in.data(), p->d_out.data());
       if (st != MLGPU_OK) return st;
-      err = hipMemcpyAsync(sg.h + nIn * chan, sg.d + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream);
-      if (err == hipSuccess) err = hipEventRecord(sg.done, e->stream);
+      err = hipMemcpyAsync(sg.h.get() + nIn * chan, sg.d.get() + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream);
+      if (err == hipSuccess) err = hipEventRecord(sg.done.get(), e->stream);
       if (err != hipSuccess)
       {
         e->lastError = std::string("process_buffer_process (D2H): ") + hipGetErrorString(err);

@@ -53,9 +53,10 @@ struct mlgpu_published_signal
   size_t maxFrames{0}, maxVoices{0};
   int channels{0}, octavesDown{0};
   int downsampleCtr{0};  // PublishedSignal::downsampleCtr_, carried from call to call
-  float* d_stage{nullptr};
-  float* h_stage{nullptr};
+  DeviceBuffer<float> d_stage;
+  PinnedBuffer<float> h_stage;
   size_t stageFloats{0};
+  ~mlgpu_published_signal() { mlgpu_dspbuffer_destroy(ring); }
 };
 
 extern "C"
@@ -63,16 +64,7 @@ extern "C"
   int mlgpu_published_signal_destroy(mlgpu_published_signal* p)
   {
     if (!p) return MLGPU_ERR_INVALID;
-    if (p->e)
-    {
-      hipSetDevice(p->e->device);
-      hipStreamSynchronize(p->e->stream);
-    }
-    if (p->ring) mlgpu_dspbuffer_destroy(p->ring);
-    if (p->d_stage) hipFree(p->d_stage);
-    if (p->h_stage) hipHostFree(p->h_stage);
-    delete p;
-    return MLGPU_OK;
+    return p->e->release(p, "published_signal_destroy");
   }
 
   int mlgpu_published_signal_create(mlgpu_engine* e, int maxFrames, int maxVoices, int channels, int octavesDown, mlgpu_published_signal** out)
@@ -84,7 +76,7 @@ extern "C"
       e->lastError = "published_signal_create: frames >= 1, voices >= 1, 1..16 channels, 0..6 octaves down";
       return MLGPU_ERR_INVALID;
     }
-    mlgpu_published_signal* p = new (std::nothrow) mlgpu_published_signal();
+    std::unique_ptr<mlgpu_published_signal> p(new (std::nothrow) mlgpu_published_signal());
     if (!p) return MLGPU_ERR_OOM;
     p->e = e;
     p->maxFrames = (size_t)maxFrames;
@@ -93,12 +85,8 @@ extern "C"
     p->octavesDown = octavesDown;
     p->ring = mlgpu_dspbuffer_create();
     // buffer_.resize(maxFrames * channels * maxVoices), MLSignalProcessor.cpp:16
-    if (!p->ring || mlgpu_dspbuffer_resize(p->ring, maxFrames * channels * maxVoices) == 0)
-    {
-      mlgpu_published_signal_destroy(p);
-      return MLGPU_ERR_OOM;
-    }
-    *out = p;
+    if (!p->ring || mlgpu_dspbuffer_resize(p->ring, maxFrames * channels * maxVoices) == 0) return MLGPU_ERR_OOM;
+    *out = p.release();
     return MLGPU_OK;
   }
 
@@ -128,11 +116,8 @@ extern "C"
     if (floats > p->stageFloats)
     {
       hipStreamSynchronize(e->stream);
-      if (p->d_stage) hipFree(p->d_stage);
-      if (p->h_stage) hipHostFree(p->h_stage);
-      p->d_stage = p->h_stage = nullptr;
       p->stageFloats = 0;
-      if (hipMalloc((void**)&p->d_stage, floats * sizeof(float)) != hipSuccess || hipHostMalloc((void**)&p->h_stage, floats * sizeof(float)) != hipSuccess)
+      if (allocate(p->d_stage, floats) != hipSuccess || allocate(p->h_stage, floats) != hipSuccess)
       {
         e->lastError = "published_signal_write: out of memory for the staging buffers";
         return MLGPU_ERR_OOM;
@@ -149,7 +134,7 @@ extern "C"
       }
       a.ch[j] = makeView(d_channels[j], layout, nVoicesTotal, nVectors);
     }
-    a.out = p->d_stage;
+    a.out = p->d_stage.get();
     a.firstVoice = firstVoice;
     a.nVoices = nVoices;
     a.T = nVectors;
@@ -161,7 +146,7 @@ extern "C"
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(publish_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, e->stream, a);
     hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(p->h_stage, p->d_stage, floats * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(p->h_stage.get(), p->d_stage.get(), floats * sizeof(float), hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (err != hipSuccess)
     {
@@ -169,7 +154,7 @@ extern "C"
       return MLGPU_ERR_HIP;
     }
     const size_t perVoice = (size_t)framesPerVector * (size_t)p->channels;
-    for (size_t i = 0; i < nVectors * nVoices; ++i) mlgpu_dspbuffer_write(p->ring, p->h_stage + i * perVoice, perVoice);
+    for (size_t i = 0; i < nVectors * nVoices; ++i) mlgpu_dspbuffer_write(p->ring, p->h_stage.get() + i * perVoice, perVoice);
     return MLGPU_OK;
   }
 

@@ -194,7 +194,7 @@ struct mlgpu_resampler
   size_t V{0};
   int octaves{0};
   bool up{false};
-  float* d_state{nullptr};
+  DeviceBuffer<float> d_state;
 };
 
 extern "C"
@@ -202,18 +202,14 @@ extern "C"
   int mlgpu_resampler_destroy(mlgpu_resampler* r)
   {
     if (!r) return MLGPU_ERR_INVALID;
-    hipSetDevice(r->e->device);
-    hipStreamSynchronize(r->e->stream);
-    if (r->d_state) hipFree(r->d_state);
-    delete r;
-    return MLGPU_OK;
+    return r->e->release(r, "resampler_destroy");
   }
 
   int mlgpu_resampler_clear(mlgpu_resampler* r)  // Downsampler::clear :1391-1399 / Upsampler::clear :1461-1469
   {
     if (!r) return MLGPU_ERR_INVALID;
     if (hipSetDevice(r->e->device) != hipSuccess) return MLGPU_ERR_HIP;
-    const hipError_t err = hipMemsetAsync(r->d_state, 0, sizeof(float) * r->V * (size_t)(r->octaves * 9 + 1), r->e->stream);
+    const hipError_t err = hipMemsetAsync(r->d_state.get(), 0, sizeof(float) * r->V * (size_t)(r->octaves * 9 + 1), r->e->stream);
     if (err != hipSuccess)
     {
       r->e->lastError = std::string("resampler_clear: ") + hipGetErrorString(err);
@@ -231,32 +227,26 @@ extern "C"
       e->lastError = "resampler_create: 1+ voices, 0..6 octaves";
       return MLGPU_ERR_INVALID;
     }
-    mlgpu_resampler* r = new (std::nothrow) mlgpu_resampler();
+    std::unique_ptr<mlgpu_resampler> r(new (std::nothrow) mlgpu_resampler());
     if (!r) return MLGPU_ERR_OOM;
     r->e = e;
     r->V = nVoices;
     r->octaves = octaves;
     r->up = up != 0;
     hipError_t err = hipSetDevice(e->device);
-    if (err == hipSuccess) err = hipMalloc((void**)&r->d_state, sizeof(float) * nVoices * (size_t)(octaves * 9 + 1));
+    if (err == hipSuccess) err = allocate(r->d_state, nVoices * (size_t)(octaves * 9 + 1));
     if (err != hipSuccess)
     {
       e->lastError = std::string("resampler_create: ") + hipGetErrorString(err);
-      delete r;
       return err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP;
     }
-    const int st = mlgpu_resampler_clear(r);
-    if (st != MLGPU_OK)
-    {
-      mlgpu_resampler_destroy(r);
-      return st;
-    }
-    *out = r;
+    if (const int st = mlgpu_resampler_clear(r.get())) return st;
+    *out = r.release();
     return MLGPU_OK;
   }
 
-  int mlgpu_resampler_get_state(mlgpu_resampler* r, float* h) { return r ? mlgpu_download(r->e, h, r->d_state, sizeof(float) * r->V * (size_t)r->octaves * 9) : MLGPU_ERR_INVALID; }
-  int mlgpu_resampler_set_state(mlgpu_resampler* r, const float* h) { return r ? mlgpu_upload(r->e, r->d_state, h, sizeof(float) * r->V * (size_t)r->octaves * 9) : MLGPU_ERR_INVALID; }
+  int mlgpu_resampler_get_state(mlgpu_resampler* r, float* h) { return r ? mlgpu_download(r->e, h, r->d_state.get(), sizeof(float) * r->V * (size_t)r->octaves * 9) : MLGPU_ERR_INVALID; }
+  int mlgpu_resampler_set_state(mlgpu_resampler* r, const float* h) { return r ? mlgpu_upload(r->e, r->d_state.get(), h, sizeof(float) * r->V * (size_t)r->octaves * 9) : MLGPU_ERR_INVALID; }
 
   int mlgpu_resampler_process(mlgpu_resampler* r, size_t nVectorsIn, const float* d_in, int inLayout, float* d_out, int outLayout)
   {
@@ -279,7 +269,7 @@ extern "C"
     ResampleArgs a;
     a.in = makeView(d_in, inLayout, r->V, nVectorsIn);
     a.out = makeView(d_out, outLayout, r->V, nOut);
-    a.state = r->d_state;
+    a.state = r->d_state.get();
     a.V = r->V;
     a.flags = e->kflags;
     a.quadsIn = nVectorsIn * 16;

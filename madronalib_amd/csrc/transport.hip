@@ -76,14 +76,14 @@ struct mlgpu_transport
   size_t n{0}, maxVectors{0}, capacityVectors{0}, vectors{0};  // capacityVectors: what d_out was allocated for (>= maxVectors)
   std::vector<TimeState> st;
   std::vector<uint32_t> dirty;
-  float* d_omega{nullptr};
-  double* d_dpdt{nullptr};
-  float* d_out{nullptr};
+  DeviceBuffer<float> d_omega;
+  DeviceBuffer<double> d_dpdt;
+  DeviceBuffer<float> d_out;
   struct Staging
   {
-    Update* h{nullptr};
-    Update* d{nullptr};
-    hipEvent_t done{nullptr};
+    PinnedBuffer<Update> h;
+    DeviceBuffer<Update> d;
+    OwnedEvent done;
     bool pending{false};
   } stage[2];
   int stageIdx{0};
@@ -158,19 +158,7 @@ extern "C"
   int mlgpu_transport_destroy(mlgpu_transport* t)
   {
     if (!t) return MLGPU_ERR_INVALID;
-    hipSetDevice(t->e->device);
-    hipStreamSynchronize(t->e->stream);
-    if (t->d_omega) hipFree(t->d_omega);
-    if (t->d_dpdt) hipFree(t->d_dpdt);
-    if (t->d_out) hipFree(t->d_out);
-    for (mlgpu_transport::Staging& s : t->stage)
-    {
-      if (s.h) hipHostFree(s.h);
-      if (s.d) hipFree(s.d);
-      if (s.done) hipEventDestroy(s.done);
-    }
-    delete t;
-    return MLGPU_OK;
+    return t->e->release(t, "transport_destroy");
   }
 
   int mlgpu_transport_create(mlgpu_engine* e, size_t n, size_t maxVectors, mlgpu_transport** out)
@@ -182,32 +170,31 @@ extern "C"
       e->lastError = "transport_create: 1+ contexts, max_vectors = the longest launch (1+)";
       return MLGPU_ERR_INVALID;
     }
-    mlgpu_transport* t = new (std::nothrow) mlgpu_transport();
+    std::unique_ptr<mlgpu_transport> t(new (std::nothrow) mlgpu_transport());
     if (!t) return MLGPU_ERR_OOM;
     t->e = e;
     t->n = n;
     t->maxVectors = t->capacityVectors = maxVectors;
     t->st.resize(n);
     hipError_t err = hipSetDevice(e->device);
-    if (err == hipSuccess) err = hipMalloc((void**)&t->d_omega, sizeof(float) * n);
-    if (err == hipSuccess) err = hipMalloc((void**)&t->d_dpdt, sizeof(double) * n);
-    if (err == hipSuccess) err = hipMalloc((void**)&t->d_out, sizeof(float) * 64 * maxVectors * n);
+    if (err == hipSuccess) err = allocate(t->d_omega, n);
+    if (err == hipSuccess) err = allocate(t->d_dpdt, n);
+    if (err == hipSuccess) err = allocate(t->d_out, 64 * maxVectors * n);
     for (mlgpu_transport::Staging& s : t->stage)
     {
-      if (err == hipSuccess) err = hipMalloc((void**)&s.d, sizeof(Update) * n);
-      if (err == hipSuccess) err = hipHostMalloc((void**)&s.h, sizeof(Update) * n);
-      if (err == hipSuccess) err = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
+      if (err == hipSuccess) err = allocate(s.d, n);
+      if (err == hipSuccess) err = allocate(s.h, n);
+      if (err == hipSuccess) err = allocate(s.done, hipEventDisableTiming);
     }
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_omega, 0, sizeof(float) * n, e->stream);  // omega_{0}, dpdt_{0}
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_dpdt, 0, sizeof(double) * n, e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_out, 0, sizeof(float) * 64 * maxVectors * n, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_omega.get(), 0, sizeof(float) * n, e->stream);  // omega_{0}, dpdt_{0}
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_dpdt.get(), 0, sizeof(double) * n, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_out.get(), 0, sizeof(float) * 64 * maxVectors * n, e->stream);
     if (err != hipSuccess)
     {
       e->lastError = std::string("transport_create: ") + hipGetErrorString(err);
-      mlgpu_transport_destroy(t);
       return err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP;
     }
-    *out = t;
+    *out = t.release();
     return MLGPU_OK;
   }
 
@@ -227,11 +214,10 @@ extern "C"
       return tfail(t, MLGPU_ERR_INVALID, "transport_reserve would move the beat-phase signal that recorded sequences of this engine may read: destroy them first");
     if (hipSetDevice(t->e->device) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "hipSetDevice");
     hipStreamSynchronize(t->e->stream);
-    float* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, sizeof(float) * 64 * maxVectors * t->n) != hipSuccess) return tfail(t, MLGPU_ERR_OOM, "transport_reserve");
-    hipMemsetAsync(fresh, 0, sizeof(float) * 64 * maxVectors * t->n, t->e->stream);
-    hipFree(t->d_out);
-    t->d_out = fresh;  // mlgpu_transport_beat_phase returns the new pointer from now on
+    DeviceBuffer<float> fresh;
+    if (allocate(fresh, 64 * maxVectors * t->n) != hipSuccess) return tfail(t, MLGPU_ERR_OOM, "transport_reserve");
+    hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * t->n, t->e->stream);
+    t->d_out = std::move(fresh);  // mlgpu_transport_beat_phase returns the new pointer from now on
     t->maxVectors = t->capacityVectors = maxVectors;
     return MLGPU_OK;
   }
@@ -275,7 +261,7 @@ extern "C"
     {
       mlgpu_transport::Staging& sg = t->stage[t->stageIdx];
       t->stageIdx ^= 1;
-      if (sg.pending && hipEventSynchronize(sg.done) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: waiting for the launch before last");
+      if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: waiting for the launch before last");
       sg.pending = false;
       size_t n = 0;
       for (uint32_t i : t->dirty)
@@ -285,12 +271,12 @@ extern "C"
         s.dirty = s.setOmega = false;
       }
       t->dirty.clear();
-      if (hipMemcpyAsync(sg.d, sg.h, sizeof(Update) * n, hipMemcpyHostToDevice, e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: upload");
-      hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, sg.d, n, t->d_omega, t->d_dpdt);
-      if (hipEventRecord(sg.done, e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: event");
+      if (hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(Update) * n, hipMemcpyHostToDevice, e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: upload");
+      hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, sg.d.get(), n, t->d_omega.get(), t->d_dpdt.get());
+      if (hipEventRecord(sg.done.get(), e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: event");
       sg.pending = true;
     }
-    hipLaunchKernelGGL(transport_kernel, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, e->stream, t->d_omega, t->d_dpdt, t->d_out, t->n, nVectors);
+    hipLaunchKernelGGL(transport_kernel, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, e->stream, t->d_omega.get(), t->d_dpdt.get(), t->d_out.get(), t->n, nVectors);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {
@@ -306,7 +292,7 @@ extern "C"
     return MLGPU_OK;
   }
 
-  const float* mlgpu_transport_beat_phase(mlgpu_transport* t) { return t ? t->d_out : nullptr; }
+  const float* mlgpu_transport_beat_phase(mlgpu_transport* t) { return t ? t->d_out.get() : nullptr; }
   uint64_t mlgpu_transport_samples_since_start(mlgpu_transport* t, size_t index) { return (t && index < t->n) ? t->st[index].samplesSinceStart : 0; }
   double mlgpu_transport_bpm(mlgpu_transport* t, size_t index) { return (t && index < t->n) ? t->st[index].bpm : 0.; }
 }

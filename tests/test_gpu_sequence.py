@@ -109,3 +109,96 @@ def test_what_cannot_be_recorded(eng):
         eng.op_apply(Op.ADD, buf, buf, None, buf, 64 * 64)
     seq.launch()
     eng.sync()
+
+
+def _reader(eng, kind, V=256):
+    """An object of `kind` and a launch that reads its device memory into `out` (n floats), the same bits every time it replays."""
+    import madronalib_amd as ml
+    n = V * 64
+    out = eng.alloc(4 * 2 * n)
+    x = eng.alloc(4 * n).upload(np.sin(np.arange(n, dtype=np.float32) * 0.01).astype(np.float32))
+    if kind == "bank":
+        obj = eng.bank([Proc.GAIN], V)
+        obj.set_coeff(0, 0, 0.5)
+        obj.set_input_const(np.linspace(0.1, 1.0, V, dtype=np.float32))
+        return obj, lambda: obj.process(1, out), out, n
+    if kind == "graph":
+        obj = ml.Graph(eng, V, [dict(name="x", type="input"), dict(name="p", type="param"),
+                                dict(name="y", type="op", kind=Op.MULTIPLY, inputs=["x", "p"])], ["y"])
+        obj.set_param("p", np.linspace(0.5, 2.0, V, dtype=np.float32))
+        return obj, lambda: obj.process(1, [x], [out]), out, n
+    if kind == "resampler":
+        obj = ml.Resampler(eng, V, 1, True)
+
+        def launch():
+            obj.clear()                       # every replay starts from the same filter state
+            obj.process(1, x, out)
+        return obj, launch, out, 2 * n
+    assert kind == "transport"
+    obj = ml.Transport(eng, 4, 2)
+    obj.update_time(0.0, 120.0, True, 48000.0)
+    obj.process_host(2)                       # the beat-phase signal a recorded launch reads
+    m = 4 * 64 * 2
+
+    def launch():                             # the C call: Engine.op_apply takes buffer objects, not the beat-phase pointer
+        assert eng.L.mlgpu_op_apply(eng.h, Op.ABS, obj.beat_phase, None, None, out.ptr, m) == ml.Status.OK
+    return obj, launch, out, m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["bank", "graph", "resampler", "transport"])
+def test_destroy_under_a_live_sequence(eng, kind):
+    """An object destroyed while a recorded sequence that reads it lives is gone for its owner at once; its device memory stays
+    until the last sequence goes, so the sequence replays the same bits."""
+    import madronalib_amd as ml
+    obj, launch, out, n = _reader(eng, kind)
+    with eng.record() as seq:
+        launch()
+    try:
+        seq.launch()
+        first = out.download(np.float32, n)
+        assert np.abs(first).max() > 0
+        assert getattr(obj.L, obj._destroy)(obj.h) == ml.Status.OK
+        obj.h = None
+        # memory freed by the destroy would be handed out again here
+        junk = [eng.alloc(4 * n).upload(np.full(n, np.nan, np.float32)) for _ in range(8)]
+        out.upload(np.zeros(n, np.float32))
+        seq.launch()
+        again = out.download(np.float32, n)
+        assert (again.view(np.uint32) == first.view(np.uint32)).all()
+        for j in junk:
+            j.free()
+    finally:
+        seq.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["bank", "graph", "events", "transport", "published_signal", "resampler", "process_buffer"])
+def test_destroy_while_recording_is_refused(eng, kind):
+    """Destroying waits for the device, which would invalidate the capture: every handle refuses while its engine records, the
+    recording still gives a sequence that launches, and the object stays usable."""
+    import madronalib_amd as ml
+    V = 64
+    a, b = eng.alloc(4 * V * 64), eng.alloc(4 * V * 64 * 2)
+    make, use = {
+        "bank": (lambda: eng.bank([Proc.GAIN], V), lambda o: o.process_host(1)),
+        "graph": (lambda: ml.Graph(eng, V, [dict(name="x", type="input"), dict(name="y", type="op", kind=Op.ADD, inputs=["x", "x"])], ["y"]),
+                  lambda o: o.process(1, [a], [b])),
+        "events": (lambda: ml.Events(eng, 4, 2), lambda o: o.process_host(1)),
+        "transport": (lambda: ml.Transport(eng, 4, 2), lambda o: o.process_host(1)),
+        "published_signal": (lambda: ml.PublishedSignal(eng, 256, 4, 1, 0), lambda o: o.write(1, [a], V, 0, 4)),
+        "resampler": (lambda: ml.Resampler(eng, V, 1, True), lambda o: o.process(1, a, b)),
+        "process_buffer": (lambda: ml.ProcessBuffer(eng, 1, 1, 64), lambda o: o.process([np.zeros(64, np.float32)], 64, lambda *_: None)),
+    }[kind]
+    obj = make()
+    with eng.record() as seq:
+        eng.op_apply(Op.ADD, a, a, None, a, V * 64)
+        st = getattr(obj.L, obj._destroy)(obj.h)
+        msg = eng.L.mlgpu_last_error(eng.h).decode()
+    assert st == ml.Status.ERR_INVALID and "not while recording" in msg
+    seq.launch()
+    eng.sync()
+    seq.close()
+    use(obj)
+    eng.sync()
+    obj.close()

@@ -197,8 +197,10 @@ def test_transport_survives_a_longer_reservation(eng):
 def test_signal_buffers_do_not_move_under_recorded_sequences(eng):
     """The beat-phase and controller signals are buffers whose device pointers callers hold and recorded sequences replay:
     a shorter reservation keeps the allocation (same pointer), a longer one is refused while a sequence of the engine is alive
-    (afterwards it goes through); an events object destroyed meanwhile is gone for its owner and freed with the last sequence."""
+    (afterwards it goes through); an events object destroyed meanwhile is gone for its owner and freed with the last sequence.
+    Buffers only the library holds (an events object's graph-source buffers) do grow under the sequence."""
     import madronalib_amd as ml
+    from madronalib_amd import patches
     tr = ml.Transport(eng, 4, 8)
     p0 = tr.beat_phase
     tr.reserve(2)
@@ -210,6 +212,15 @@ def test_signal_buffers_do_not_move_under_recorded_sequences(eng):
     c0 = ev.controller_signal(0)
     ev.watch_controllers([7, 11], 2)
     assert ev.controller_signal(0) == c0
+    src = ml.Events(eng, 16, 4, 48000.0)             # an events object with a graph bound to it
+    src.set_wanted_rows([0, 1])
+    desc, outn = patches.synth16(pitch_input=True, event_rows=True)
+    g = ml.Graph(eng, 64, desc, outn)
+    g.bind_events(src)
+    g.clear()
+    d_out = eng.alloc(4 * 64 * 8 * 64)
+    src.reserve_for_graph(2)
+    g.process_events(2, 0, [], [d_out])
     bank = eng.bank([Proc.SINE_GEN], 64)
     bank.set_input_const(np.full(64, 0.01, np.float32))
     out = eng.alloc(4 * 64 * 64)
@@ -229,6 +240,10 @@ def test_signal_buffers_do_not_move_under_recorded_sequences(eng):
         doomed.watch_controllers([7], 2)
         assert doomed.L.mlgpu_events_destroy(doomed.h) == ml.Status.OK
         doomed.h = None
+        # the graph-source buffers of an events object are the library's alone: they grow under a live sequence, the old ones
+        # are kept for it
+        src.reserve_for_graph(8)
+        g.process_events(8, 0, [], [d_out])
         seq.launch()                                  # (the sequence still replays)
         eng.sync()
     finally:
@@ -236,6 +251,8 @@ def test_signal_buffers_do_not_move_under_recorded_sequences(eng):
     tr.reserve(32)
     assert tr.process_host(32).shape[1] == 32 * 64
     ev.watch_controllers([7, 11], 64)
+    g.close()
+    src.close()
     ev.close()
     tr.close()
     bank.close()
