@@ -66,44 +66,15 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
   float cx = u2f(SW(S_X)), cy = u2f(SW(S_Y)), cz = u2f(SW(S_Z)), chanPress = u2f(SW(S_CHANPRESS));
   uint32_t age = SW(S_AGE), ageStep = SW(S_AGE_STEP);
   bool inhibit = SW(S_INHIBIT_GLIDE) != 0, needsRecalc = SW(S_RECALC) != 0;
-  float pgCurr = u2f(SW(S_PG_CURR)), pgStep = u2f(SW(S_PG_STEP)), pgTarget = u2f(SW(S_PG_TARGET)), pgDy = u2f(SW(S_PG_DY));
-  int32_t pgRemaining = (int32_t)SW(S_PG_REMAINING), pgPerGlide = (int32_t)SW(S_PG_PER_GLIDE);
+  PitchGlide pg;
+  pg.curr = u2f(SW(S_PG_CURR)), pg.step = u2f(SW(S_PG_STEP)), pg.target = u2f(SW(S_PG_TARGET)), pg.dyPerSample = u2f(SW(S_PG_DY));
+  pg.remaining = (int32_t)SW(S_PG_REMAINING), pg.perGlide = (int32_t)SW(S_PG_PER_GLIDE);
   uint32_t driftSeed = SW(S_DRIFT_SEED);
   int32_t driftCounter = (int32_t)SW(S_DRIFT_COUNTER), driftNext = (int32_t)SW(S_DRIFT_NEXT);
   float driftValue = u2f(SW(S_DRIFT_VALUE));
   // the seven glides stay in HBM between uses: each row loop loads the one or two it needs (5 words), so their
   // registers are not live everywhere
 #define GS(i) (S + (size_t)(S_GLIDES + (i) * kGlideWords) * ln)
-
-  auto setPitchGlideTime = [&](int32_t t) {  // SampleAccurateLinearGlide::setGlideTimeInSamples, MLDSPGens.h:527-532
-    pgPerGlide = t < 1 ? 1 : t;
-    pgDy = 1.0f / (float)pgPerGlide;
-  };
-  auto pitchGlideNext = [&](float f) {  // nextSample, :541-580
-    if (f != pgTarget)
-    {
-      pgTarget = f;
-      pgRemaining = pgPerGlide;
-    }
-    if (pgRemaining < 0) {}
-    else if (pgRemaining == 0)
-    {
-      pgCurr = pgTarget;
-      pgStep = 0.f;
-      pgRemaining--;
-    }
-    else if (pgRemaining == pgPerGlide)
-    {
-      pgStep = (pgTarget - pgCurr) * pgDy;
-      pgRemaining--;
-    }
-    else
-    {
-      pgCurr += pgStep;
-      pgRemaining--;
-    }
-    return pgCurr;
-  };
 
   const uint2 recRange = live ? a.recRange[L] : make_uint2(0u, 0u);  // this lane's records of this launch: [x, y)
   uint32_t cursor = recRange.x;
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
   // glide (8 s per glide: always moving) are fetched together, the block is computed in time order in registers (the pitch glide may
   // be moving: it is stepped sample by sample as ever; what each vector does to the drift glide - hold / end / start / continue -
   // depends on the drift counter alone), rows are written as they come, the slots go back once. Same operations on the same
-  // values as the general loop; the state variables are this kernel's own, so the two forms alternate freely.
+  // values as the general loop (drift_step, PitchGlide::next); the state variables are this kernel's own, so the two forms alternate freely.
   constexpr int kBlock = 4;
   typedef float f32x4b __attribute__((ext_vector_type(4)));
   for (size_t t = 0; t < a.T; ++t)
@@ -220,18 +191,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
           if (onB)
           {
             // the drift part of Voice::beginProcess (:115-126), then the drift glide's own start of a vector
-            driftCounter += MLGPU_FLOATS_PER_DSPVECTOR;
-            if (driftCounter >= driftNext)
-            {
-              driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;
-              const float d = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-              driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;
-              const float d2 = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-              const float nextTimeMul = 1.0f + abs_ps(d2);
-              driftValue = d;
-              driftCounter = 0;
-              driftNext = (int32_t)(a.s.sr * (double)nextTimeMul * (double)8.0f);
-            }
+            drift_step(driftSeed, driftCounter, driftNext, driftValue, a.s.sr);
             gd.beginVectorKnown(driftValue, a.s.driftGlideVectors, a.s.driftGlideDy, eff63);
             cm[b] = gd.mode();
             cu[b] = gd.isUniform();
@@ -246,9 +206,8 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
             gd.endVector();
           }
         }
-        const bool pgMoves = __builtin_amdgcn_ballot_w64(onB && !(pgRemaining < 0 && pgTarget == pitch)) != 0;  // any lane's pitch glide
-        const float pg0Curr = pgCurr, pg0Step = pgStep, pg0Target = pgTarget;  // the pitch glide as the block starts
-        const int32_t pg0Remaining = pgRemaining;
+        const bool pgMoves = __builtin_amdgcn_ballot_w64(onB && !(pg.remaining < 0 && pg.target == pitch)) != 0;  // any lane's pitch glide
+        const PitchGlide pg0 = pg;  // the pitch glide as the block starts
         constexpr int kHalf = 32;
 #pragma unroll 1
         for (int h = 0; h < 64; h += kHalf)
@@ -256,16 +215,13 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
           float c[kHalf];
 #pragma unroll
           for (int i = 0; i < kHalf; ++i) c[i] = slotsLive ? u2f(gs[(size_t)(5 + h + i) * ln]) : 0.f;
-          pgCurr = pg0Curr;
-          pgStep = pg0Step;
-          pgTarget = pg0Target;
-          pgRemaining = pg0Remaining;
+          pg = pg0;
           f32x4b* pb = (f32x4b*)sp.base + t * sp.strideT + outVoice * sp.strideV + (size_t)(h / 4) * sp.strideQ;
 #pragma unroll
           for (int b = 0; b < kBlock; ++b, pb += sp.strideT)
           {
             if (onB && pgMoves)
-              for (int n = 0; n < h; ++n) (void)pitchGlideNext(pitch);  // the samples of this vector before this half
+              for (int n = 0; n < h; ++n) (void)pg.next(pitch);  // the samples of this vector before this half
             f32x4b* pq = pb;
 #pragma unroll
             for (int q = 0; q < kHalf / 4; ++q, pq += sp.strideQ)
@@ -288,7 +244,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
                     else v = (cu[b] ? cuval[b] : c[i]) + cstep[b];
                     c[i] = v;
                   }
-                  vPitch = pitchGlideNext(pitch);
+                  vPitch = pg.next(pitch);
                   vPitch = vPitch + bendTerm;
                   vPitch = vPitch + (v * a.s.driftAmount) * 0.02f;           // kDriftScale, :247
                 }
@@ -297,7 +253,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
               if (storePitch) __builtin_nontemporal_store(o, pq);
             }
             if (onB && pgMoves)
-              for (int n = h + kHalf; n < 64; ++n) (void)pitchGlideNext(pitch);  // ... and after it
+              for (int n = h + kHalf; n < 64; ++n) (void)pg.next(pitch);  // ... and after it
           }
           if (wrote)
 #pragma unroll
@@ -319,24 +275,8 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
     bool noteHere = false;  // a note record of this lane falls into this vector
     if (awake && active)
     {
-      // ---- Voice::beginProcess, :75-113 ----
-      if (needsRecalc)
-      {
-        if (!inhibit) setPitchGlideTime(a.s.pitchGlideSamples);
-        needsRecalc = false;
-      }
-      driftCounter += MLGPU_FLOATS_PER_DSPVECTOR;
-      if (driftCounter >= driftNext)
-      {
-        driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;  // RandomScalarSource::getFloat, MLDSPScalarMath.h:189-202
-        const float d = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-        driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;
-        const float d2 = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-        const float nextTimeMul = 1.0f + abs_ps(d2);
-        driftValue = d;
-        driftCounter = 0;
-        driftNext = (int32_t)(a.s.sr * (double)nextTimeMul * (double)8.0f);
-      }
+      begin_process(a.s, needsRecalc, inhibit, pg, driftSeed, driftCounter, driftNext, driftValue);
+      needsRecalc = false;
       // ---- values that only matter at the end of the vector: apply them now (endProcess, :218-247) ----
       for (uint32_t r = cursor; r < vend; ++r)
       {
@@ -539,7 +479,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
           float vPitch = 0.f;
           if (on)
           {
-            vPitch = pitchGlideNext(pitch);
+            vPitch = pg.next(pitch);
             const float bendSig = gb.nextWith(GS(0), ln, n, cb[k]), driftSig = gd.nextWith(GS(5), ln, n, cd[k]);
             vPitch = vPitch + (bendSig * pitchBendScale) * (1.f / 12);         // :244
             vPitch = vPitch + (driftSig * a.s.driftAmount) * 0.02f;           // kDriftScale, :247
@@ -552,7 +492,7 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
     else
     {
     RecCache recCache;
-    if (on) note_rewind(a.recs, nc, vend, velocity, pitch, age, ageStep, inhibit, a.s.pitchGlideSamples, setPitchGlideTime, pitchGlideNext);
+    if (on) note_rewind(a.recs, nc, vend, velocity, pitch, age, ageStep, inhibit, pg, a.s.pitchGlideSamples);
 #pragma unroll 1
     for (int q = 0; q < 16; ++q)
     {
@@ -564,8 +504,8 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
         float vPitch = 0.f, vGate = 0.f, vTime = 0.f;
         if (on)
         {
-          note_frame(a.recs, recCache, nc, vend, n, preApplied, velocity, pitch, age, ageStep, inhibit, a.s.pitchGlideSamples, wantTime, srD, setPitchGlideTime,
-                     pitchGlideNext, vPitch, vGate, vTime);
+          note_frame(a.recs, recCache, nc, vend, n, preApplied, velocity, pitch, age, ageStep, inhibit, pg, a.s.pitchGlideSamples, wantTime, srD, vPitch, vGate,
+                     vTime);
           const float bendSig = gb.next(GS(0), ln, n), driftSig = gd.next(GS(5), ln, n);
           vPitch = vPitch + (bendSig * pitchBendScale) * (1.f / 12);         // :244
           vPitch = vPitch + (driftSig * a.s.driftAmount) * 0.02f;           // kDriftScale, :247
@@ -604,8 +544,8 @@ __global__ __launch_bounds__(256, 4) void e2s_kernel(const E2SArgs aIn)
   SW(S_VELOCITY) = f2u(velocity); SW(S_PITCH) = f2u(pitch); SW(S_BEND) = f2u(bend); SW(S_MOD) = f2u(mod);
   SW(S_X) = f2u(cx); SW(S_Y) = f2u(cy); SW(S_Z) = f2u(cz); SW(S_CHANPRESS) = f2u(chanPress);
   SW(S_AGE) = age; SW(S_AGE_STEP) = ageStep; SW(S_INHIBIT_GLIDE) = inhibit ? 1u : 0u; SW(S_RECALC) = needsRecalc ? 1u : 0u;
-  SW(S_PG_CURR) = f2u(pgCurr); SW(S_PG_STEP) = f2u(pgStep); SW(S_PG_TARGET) = f2u(pgTarget); SW(S_PG_REMAINING) = (uint32_t)pgRemaining;
-  SW(S_PG_PER_GLIDE) = (uint32_t)pgPerGlide; SW(S_PG_DY) = f2u(pgDy);
+  SW(S_PG_CURR) = f2u(pg.curr); SW(S_PG_STEP) = f2u(pg.step); SW(S_PG_TARGET) = f2u(pg.target); SW(S_PG_REMAINING) = (uint32_t)pg.remaining;
+  SW(S_PG_PER_GLIDE) = (uint32_t)pg.perGlide; SW(S_PG_DY) = f2u(pg.dyPerSample);
   SW(S_DRIFT_SEED) = driftSeed; SW(S_DRIFT_COUNTER) = (uint32_t)driftCounter; SW(S_DRIFT_VALUE) = f2u(driftValue); SW(S_DRIFT_NEXT) = (uint32_t)driftNext;
 #undef GS
 #undef SW
@@ -662,8 +602,9 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
   float velocity = u2f(SW(S_VELOCITY)), pitch = u2f(SW(S_PITCH)), bend = u2f(SW(S_BEND)), cz = u2f(SW(S_Z));
   uint32_t age = SW(S_AGE), ageStep = SW(S_AGE_STEP);
   bool inhibit = SW(S_INHIBIT_GLIDE) != 0, needsRecalc = SW(S_RECALC) != 0;
-  float pgCurr = u2f(SW(S_PG_CURR)), pgStep = u2f(SW(S_PG_STEP)), pgTarget = u2f(SW(S_PG_TARGET)), pgDy = u2f(SW(S_PG_DY));
-  int32_t pgRemaining = (int32_t)SW(S_PG_REMAINING), pgPerGlide = (int32_t)SW(S_PG_PER_GLIDE);
+  PitchGlide pg;
+  pg.curr = u2f(SW(S_PG_CURR)), pg.step = u2f(SW(S_PG_STEP)), pg.target = u2f(SW(S_PG_TARGET)), pg.dyPerSample = u2f(SW(S_PG_DY));
+  pg.remaining = (int32_t)SW(S_PG_REMAINING), pg.perGlide = (int32_t)SW(S_PG_PER_GLIDE);
   uint32_t driftSeed = SW(S_DRIFT_SEED);
   int32_t driftCounter = (int32_t)SW(S_DRIFT_COUNTER), driftNext = (int32_t)SW(S_DRIFT_NEXT);
   float driftValue = u2f(SW(S_DRIFT_VALUE));
@@ -671,36 +612,6 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
   uint32_t* GB = S + (size_t)(S_GLIDES + 0 * kGlideWords) * ln;
   Glide gb;
   gb.load(GB, ln);
-
-  auto setPitchGlideTime = [&](int32_t t) {  // SampleAccurateLinearGlide::setGlideTimeInSamples, MLDSPGens.h:527-532
-    pgPerGlide = t < 1 ? 1 : t;
-    pgDy = 1.0f / (float)pgPerGlide;
-  };
-  auto pitchGlideNext = [&](float f) {  // nextSample, :541-580
-    if (f != pgTarget)
-    {
-      pgTarget = f;
-      pgRemaining = pgPerGlide;
-    }
-    if (pgRemaining < 0) {}
-    else if (pgRemaining == 0)
-    {
-      pgCurr = pgTarget;
-      pgStep = 0.f;
-      pgRemaining--;
-    }
-    else if (pgRemaining == pgPerGlide)
-    {
-      pgStep = (pgTarget - pgCurr) * pgDy;
-      pgRemaining--;
-    }
-    else
-    {
-      pgCurr += pgStep;
-      pgRemaining--;
-    }
-    return pgCurr;
-  };
 
   const uint2 recRange = a.recRange[lane];  // this lane's records of this launch: [x, y)
   uint32_t cursor = recRange.x;
@@ -722,24 +633,8 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
     bool noteHere = false;
     if (on)
     {
-      // ---- Voice::beginProcess, :75-126 ----
-      if (needsRecalc)
-      {
-        if (!inhibit) setPitchGlideTime(a.s.pitchGlideSamples);
-        needsRecalc = false;
-      }
-      driftCounter += MLGPU_FLOATS_PER_DSPVECTOR;
-      if (driftCounter >= driftNext)
-      {
-        driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;  // RandomScalarSource::getFloat, MLDSPScalarMath.h:189-202
-        const float d = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-        driftSeed = driftSeed * 0x0019660Du + 0x3C6EF35Fu;
-        const float d2 = u2f(((driftSeed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
-        const float nextTimeMul = 1.0f + abs_ps(d2);
-        driftValue = d;
-        driftCounter = 0;
-        driftNext = (int32_t)(a.s.sr * (double)nextTimeMul * (double)8.0f);
-      }
+      begin_process(a.s, needsRecalc, inhibit, pg, driftSeed, driftCounter, driftNext, driftValue);
+      needsRecalc = false;
       // ---- values that only matter at the end of the vector (endProcess, :218-247); the rows this form does not compute keep their
       //      values in memory ----
       float finalVelocity = velocity;
@@ -764,7 +659,7 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
     }
     const int bm = gb.mode();
     const bool heldB = (bm == 1) || (bm == 0 && gb.isUniform());
-    const bool pgBusy = on && (pitch != pgTarget || pgRemaining >= 0);
+    const bool pgBusy = on && (pitch != pg.target || pg.remaining >= 0);
     const bool walk = on && (noteHere || !heldB);
     const bool glideOnly = on && !walk && pgBusy;  // a portamento in progress, nothing else: the pitch glide's 64 steps, the gate held
     const float hvB = (bm == 1) ? gb.target : gb.uniformValue;
@@ -776,13 +671,13 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
         gate = velocity;
         age += (uint32_t)MLGPU_FLOATS_PER_DSPVECTOR * ageStep;
         const float bendTerm = (hvB * pitchBendScale) * (1.f / 12);  // :244
-        if (!glideOnly) P = pgCurr + bendTerm;  // the same for all 64 frames
+        if (!glideOnly) P = pg.curr + bendTerm;  // the same for all 64 frames
         else
         {
           f32x4* oP = (f32x4*)a.rowP + (t * 16) * ln + lane;
           // in the middle of a glide - 64 or more steps to go, the target unchanged - every frame of the vector is nextSample's last
           // branch (:571-576): mCurr += mStep. 64 dependent adds instead of 64 trips through the state machine.
-          if (pitch == pgTarget && pgRemaining >= MLGPU_FLOATS_PER_DSPVECTOR && pgRemaining < pgPerGlide)
+          if (pitch == pg.target && pg.remaining >= MLGPU_FLOATS_PER_DSPVECTOR && pg.remaining < pg.perGlide)
           {
 #pragma unroll 4
             for (int q = 0; q < 16; ++q, oP += ln)
@@ -791,12 +686,12 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
 #pragma unroll
               for (int k = 0; k < 4; ++k)
               {
-                pgCurr += pgStep;
-                vP[k] = pgCurr + bendTerm;
+                pg.curr += pg.step;
+                vP[k] = pg.curr + bendTerm;
               }
               __builtin_nontemporal_store(vP, oP);
             }
-            pgRemaining -= MLGPU_FLOATS_PER_DSPVECTOR;
+            pg.remaining -= MLGPU_FLOATS_PER_DSPVECTOR;
           }
           else
 #pragma unroll 1
@@ -804,7 +699,7 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
           {
             f32x4 vP;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) vP[k] = pitchGlideNext(pitch) + bendTerm;
+            for (int k = 0; k < 4; ++k) vP[k] = pg.next(pitch) + bendTerm;
             __builtin_nontemporal_store(vP, oP);
           }
         }
@@ -832,19 +727,9 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
             continue;
           }
           int dest = (int)((rc.typeTimeFlags >> 8) & 0xFF);
-          const uint32_t flags = rc.typeTimeFlags >> 16;
           if (!preApplied)
           {
-            if (type != REC_NOTE_OFF)
-            {
-              if (flags & 2) age = 0;  // doReset
-              ageStep = 1;
-            }
-            if (type == REC_NOTE_ON)
-            {
-              inhibit = !(flags & 1);
-              setPitchGlideTime((flags & 1) ? a.s.pitchGlideSamples : 0);
-            }
+            MLEV_NOTE_START(type, rc.typeTimeFlags >> 16, a.s.pitchGlideSamples, age, ageStep, inhibit, pg);
             preApplied = true;
           }
           if (type == REC_NOTE_RETRIG && dest == 0) dest = 1;
@@ -852,7 +737,7 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
         }
         return 64;
       };
-      note_rewind(a.recs, nc, vend, velocity, pitch, age, ageStep, inhibit, a.s.pitchGlideSamples, setPitchGlideTime, pitchGlideNext);
+      note_rewind(a.recs, nc, vend, velocity, pitch, age, ageStep, inhibit, pg, a.s.pitchGlideSamples);
       int quietUntil = heldB ? plan(0) : 0;  // frames [n, quietUntil) need no state machine (a moving bend: every frame does)
       f32x4* oP = (f32x4*)a.rowP + (t * 16) * ln + lane;
       f32x4* oG = (f32x4*)a.rowG + (t * 16) * ln + lane;
@@ -869,13 +754,13 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
           if (n < quietUntil)
           {
             vGate = velocity;
-            vPitch = pitchGlideNext(pitch) + bendTerm;
+            vPitch = pg.next(pitch) + bendTerm;
             age += ageStep;
           }
           else
           {
-            note_frame(a.recs, recCache, nc, vend, n, preApplied, velocity, pitch, age, ageStep, inhibit, a.s.pitchGlideSamples, false, 1.0, setPitchGlideTime,
-                       pitchGlideNext, vPitch, vGate, vTime);
+            note_frame(a.recs, recCache, nc, vend, n, preApplied, velocity, pitch, age, ageStep, inhibit, pg, a.s.pitchGlideSamples, false, 1.0, vPitch, vGate,
+                       vTime);
             const float bendSig = gb.next(GB, ln, n);
             vPitch = vPitch + (bendSig * pitchBendScale) * (1.f / 12);  // :244
             if (heldB) quietUntil = plan(n + 1);
@@ -908,8 +793,8 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
   SW(S_AWAKE) = awake ? 1u : 0u;
   SW(S_VELOCITY) = f2u(velocity); SW(S_PITCH) = f2u(pitch); SW(S_BEND) = f2u(bend); SW(S_Z) = f2u(cz);
   SW(S_AGE) = age; SW(S_AGE_STEP) = ageStep; SW(S_INHIBIT_GLIDE) = inhibit ? 1u : 0u; SW(S_RECALC) = needsRecalc ? 1u : 0u;
-  SW(S_PG_CURR) = f2u(pgCurr); SW(S_PG_STEP) = f2u(pgStep); SW(S_PG_TARGET) = f2u(pgTarget); SW(S_PG_REMAINING) = (uint32_t)pgRemaining;
-  SW(S_PG_PER_GLIDE) = (uint32_t)pgPerGlide; SW(S_PG_DY) = f2u(pgDy);
+  SW(S_PG_CURR) = f2u(pg.curr); SW(S_PG_STEP) = f2u(pg.step); SW(S_PG_TARGET) = f2u(pg.target); SW(S_PG_REMAINING) = (uint32_t)pg.remaining;
+  SW(S_PG_PER_GLIDE) = (uint32_t)pg.perGlide; SW(S_PG_DY) = f2u(pg.dyPerSample);
   SW(S_DRIFT_SEED) = driftSeed; SW(S_DRIFT_COUNTER) = (uint32_t)driftCounter; SW(S_DRIFT_VALUE) = f2u(driftValue); SW(S_DRIFT_NEXT) = (uint32_t)driftNext;
 #undef SW
 }

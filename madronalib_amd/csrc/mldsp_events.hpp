@@ -6,6 +6,7 @@
 #pragma once
 #include "mlgpu_device_args.hpp"
 #include "mldsp_math.hpp"
+#include "mldsp_procs.hpp"  // Proc<MLGPU_PROC_SAMPLE_ACCURATE_LINEAR_GLIDE>: the pitch glide
 
 namespace mlev
 {
@@ -89,61 +90,11 @@ struct Glide
   // beginVector for a caller that knows what mCurrVec[63] holds (it has the slots in registers): no memory access
   MLD void beginVectorKnown(float f, int32_t perGlide, float dyPerVector, float slot63)
   {
-    if (f != target)
-    {
-      target = f;
-      remaining = perGlide;
-    }
-    int m;
-    if (remaining < 0) m = 0;
-    else if (remaining == 0)
-    {
-      m = 1;
-      step = 0.f;
-      remaining--;
-    }
-    else if (remaining == perGlide)
-    {
-      m = 2;
-      startValue = isUniform() ? uniformValue : slot63;
-      step = (target - startValue) * dyPerVector;
-      remaining--;
-    }
-    else
-    {
-      m = 3;
-      remaining--;
-    }
-    modeFlags = (modeFlags & 4) | m;
+    beginVectorFrom(f, perGlide, dyPerVector, [=] { return slot63; });
   }
   MLD void beginVector(const uint32_t* st, size_t stride, float f, int32_t perGlide, float dyPerVector)
   {
-    if (f != target)
-    {
-      target = f;
-      remaining = perGlide;
-    }
-    int m;
-    if (remaining < 0) m = 0;
-    else if (remaining == 0)
-    {
-      m = 1;
-      step = 0.f;
-      remaining--;
-    }
-    else if (remaining == perGlide)
-    {
-      m = 2;
-      startValue = isUniform() ? uniformValue : u2f(st[(size_t)(5 + 63) * stride]);
-      step = (target - startValue) * dyPerVector;
-      remaining--;
-    }
-    else
-    {
-      m = 3;
-      remaining--;
-    }
-    modeFlags = (modeFlags & 4) | m;
+    beginVectorFrom(f, perGlide, dyPerVector, [=] { return u2f(st[(size_t)(5 + 63) * stride]); });
   }
   // mCurrVec[n] is read and rewritten at sample n only, so a quad's four slots can be fetched together (and a quad ahead):
   // a load per sample in the middle of the load -> add -> store chain made the whole kernel wait out a memory round trip
@@ -185,13 +136,102 @@ struct Glide
     else
       modeFlags &= 4;
   }
+
+ private:
+  // the start of a vector of LinearGlide::operator()(f) (:457-505), for both forms above. slot63() is asked only when a glide starts
+  // from a non-uniform mCurrVec: a load of slot 63 on every vector would add memory traffic to every vector.
+  template <class Slot63>
+  MLD void beginVectorFrom(float f, int32_t perGlide, float dyPerVector, Slot63 slot63)
+  {
+    if (f != target)
+    {
+      target = f;
+      remaining = perGlide;
+    }
+    int m;
+    if (remaining < 0) m = 0;
+    else if (remaining == 0)
+    {
+      m = 1;
+      step = 0.f;
+      remaining--;
+    }
+    else if (remaining == perGlide)
+    {
+      m = 2;
+      startValue = isUniform() ? uniformValue : slot63();
+      step = (target - startValue) * dyPerVector;
+      remaining--;
+    }
+    else
+    {
+      m = 3;
+      remaining--;
+    }
+    modeFlags = (modeFlags & 4) | m;
+  }
 };
 
 
+// The sample-accurate pitch glide of a voice (SampleAccurateLinearGlide, MLDSPGens.h:517-590): its state words are S_PG_*, its
+// nextSample is PitchGlide::next.
+typedef Proc<MLGPU_PROC_SAMPLE_ACCURATE_LINEAR_GLIDE> PitchGlide;
+MLD void set_pitch_glide_time(PitchGlide& pg, int32_t t)  // SampleAccurateLinearGlide::setGlideTimeInSamples, MLDSPGens.h:527-532
+{
+  pg.perGlide = t < 1 ? 1 : t;
+  pg.dyPerSample = 1.0f / (float)pg.perGlide;
+}
+
+// The drift random walk of Voice::beginProcess (:115-126): once per DSPVector; at the change time a new value and the time of the change
+// after it, two draws of RandomScalarSource::getFloat (MLDSPScalarMath.h:189-202).
+MLD void drift_step(uint32_t& seed, int32_t& counter, int32_t& next, float& value, double sr)
+{
+  counter += MLGPU_FLOATS_PER_DSPVECTOR;
+  if (counter >= next)
+  {
+    auto draw = [&] {
+      seed = seed * 0x0019660Du + 0x3C6EF35Fu;
+      return u2f(((seed >> 9) & 0x007FFFFFu) | 0x3F800000u) * 2.f - 3.f;
+    };
+    const float d = draw();
+    const float nextTimeMul = 1.0f + abs_ps(draw());
+    value = d;
+    counter = 0;
+    next = (int32_t)(sr * (double)nextTimeMul * (double)8.0f);
+  }
+}
+
+// Voice::beginProcess (:75-126): the pitch glide's time if setSampleRate / setPitchGlideInSeconds asked for it (S_RECALC; the caller
+// clears its flag after this), then the drift random walk
+MLD void begin_process(const E2SSettings& s, bool needsRecalc, bool inhibit, PitchGlide& pg, uint32_t& seed, int32_t& counter, int32_t& next,
+                       float& value)
+{
+  if (needsRecalc && !inhibit) set_pitch_glide_time(pg, s.pitchGlideSamples);
+  drift_step(seed, counter, next, value, s.sr);
+}
+
+// A note record's own bookkeeping (writeNoteEvent, :115-216), done on the first frame that sees the record; flags = typeTimeFlags >> 16.
+// A macro, not a function: a function is optimised on its own before it is inlined, and every form of it tried cost e2s_ctl_kernel 47-51
+// and e2s_kernel 43-119 more instructions than this bookkeeping written in place.
+#define MLEV_NOTE_START(type, flags, pitchGlideSamples, age, ageStep, inhibit, pg)  \
+  do                                                                              \
+  {                                                                               \
+    if ((type) != REC_NOTE_OFF)                                                   \
+    {                                                                             \
+      if ((flags) & 2) (age) = 0; /* doReset */                                   \
+      (ageStep) = 1;                                                              \
+    }                                                                             \
+    if ((type) == REC_NOTE_ON)                                                    \
+    {                                                                             \
+      (inhibit) = !((flags) & 1);                                                 \
+      set_pitch_glide_time((pg), ((flags) & 1) ? (pitchGlideSamples) : 0);        \
+    }                                                                             \
+  } while (0)
+
 // One frame of a vector that holds note records: writeNoteEvent (:115-216) and its neighbours walked frame by frame - the note
 // records that end on frame n are applied, the gate, the sample-accurate pitch glide and the event age take their step. Shared by
-// e2s_kernel (all rows) and EventsVoice (pitch and gate inside a voice graph). The caller's state comes in by reference;
-// setPitchGlideTime(samples) and pitchGlideNext(pitch) are its two glide operations; vTime is written when wantTime.
+// e2s_kernel (all rows) and e2s_ctl_kernel (pitch and gate for a voice graph). The caller's state comes in by reference; vTime is written
+// when wantTime.
 // The frames of a vector look at the same pending record again and again (a note that starts at frame 40 is read by frames 0..40):
 // one record kept in registers, fetched again only when another index is asked for. Without it every frame is a memory round trip
 // behind the stores of the frame before (loads and stores of a wavefront complete in issue order).
@@ -210,10 +250,8 @@ struct RecCache
   }
 };
 
-template <class SetGlideTime, class GlideNext>
 MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t vend, int n, bool& preApplied, float& velocity, float& pitch, uint32_t& age, uint32_t& ageStep,
-                    bool& inhibit, int32_t pitchGlideSamples, bool wantTime, double srD, SetGlideTime setPitchGlideTime, GlideNext pitchGlideNext,
-                    float& vPitch, float& vGate, float& vTime)
+                    bool& inhibit, PitchGlide& pg, int32_t pitchGlideSamples, bool wantTime, double srD, float& vPitch, float& vGate, float& vTime)
 {
   bool retrigFrame = false;
   while (nc < vend)
@@ -226,19 +264,9 @@ MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t ven
       continue;
     }
     int dest = (int)((rc.typeTimeFlags >> 8) & 0xFF);
-    const uint32_t flags = rc.typeTimeFlags >> 16;
     if (!preApplied)
     {
-      if (type != REC_NOTE_OFF)
-      {
-        if (flags & 2) age = 0;  // doReset
-        ageStep = 1;
-      }
-      if (type == REC_NOTE_ON)
-      {
-        inhibit = !(flags & 1);
-        setPitchGlideTime((flags & 1) ? pitchGlideSamples : 0);
-      }
+      MLEV_NOTE_START(type, rc.typeTimeFlags >> 16, pitchGlideSamples, age, ageStep, inhibit, pg);
       preApplied = true;
     }
     if (type == REC_NOTE_RETRIG)
@@ -261,7 +289,7 @@ MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t ven
     break;
   }
   vGate = retrigFrame ? 0.f : velocity;
-  vPitch = pitchGlideNext(pitch);
+  vPitch = pg.next(pitch);
   age += ageStep;
   if (wantTime) vTime = (float)((double)age / srD);
   // A retrigger that lands on the frame where the previous note event of this voice ended (a note-on and a steal of
@@ -287,20 +315,7 @@ MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t ven
     // are this pattern too; without this line the second one's reset of the event age came a frame late: tools/events_soak.py)
     if ((R.typeTimeFlags & 0xFF) == REC_NOTE_RETRIG && rdest == 0) rdest = 1;
     if ((R.typeTimeFlags & 0xFF) != REC_NOTE_RETRIG || rdest != n + 1) break;
-    if (!preApplied)  // P's own bookkeeping, if this frame is the first one it sees
-    {
-      const uint32_t pflags = P.typeTimeFlags >> 16;
-      if (ptype != REC_NOTE_OFF)
-      {
-        if (pflags & 2) age = 0;
-        ageStep = 1;
-      }
-      if (ptype == REC_NOTE_ON)
-      {
-        inhibit = !(pflags & 1);
-        setPitchGlideTime((pflags & 1) ? pitchGlideSamples : 0);
-      }
-    }
+    if (!preApplied) MLEV_NOTE_START(ptype, P.typeTimeFlags >> 16, pitchGlideSamples, age, ageStep, inhibit, pg);  // P's own bookkeeping, if this frame is the first one it sees
     if (ptype == REC_NOTE_OFF) velocity = 0.f;  // P's new values
     else
     {
@@ -312,7 +327,7 @@ MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t ven
     ageStep = 1;
     preApplied = true;
     vGate = 0.f;                                // the retrigger frame
-    vPitch = pitchGlideNext(pitch);
+    vPitch = pg.next(pitch);
     age += ageStep;
     if (wantTime) vTime = (float)((double)age / srD);
   }
@@ -331,9 +346,8 @@ constexpr uint32_t REC_FLAG_REWIND = 4u;
 //   retrigger on frame d (>= 1): the frames [next, d - 1) step, then frame d - 1 - always, also when next == d - steps, next = d  (:169-183)
 // up to the LAST flagged record of the vector; nc is left there and the caller walks the vector from frame 0 as usual.
 // Found by tools/events_soak.py (8 of 2 100 random configurations: a note, then the pedal's release and the note's end in one DSPVector).
-template <class SetGlideTime, class GlideNext>
 MLD void note_rewind(const Rec* recs, uint32_t& nc, uint32_t vend, float& velocity, float& pitch, uint32_t& age, uint32_t& ageStep, bool& inhibit,
-                     int32_t pitchGlideSamples, SetGlideTime setPitchGlideTime, GlideNext pitchGlideNext)
+                     PitchGlide& pg, int32_t pitchGlideSamples)
 {
   uint32_t last = vend;
   for (uint32_t j = nc; j < vend; ++j)
@@ -349,17 +363,7 @@ MLD void note_rewind(const Rec* recs, uint32_t& nc, uint32_t vend, float& veloci
     const uint32_t type = rc.typeTimeFlags & 0xFF;
     if (type != REC_NOTE_ON && type != REC_NOTE_RETRIG && type != REC_NOTE_OFF) continue;
     int dest = (int)((rc.typeTimeFlags >> 8) & 0xFF);
-    const uint32_t flags = rc.typeTimeFlags >> 16;
-    if (type != REC_NOTE_OFF)
-    {
-      if (flags & 2) age = 0;  // doReset
-      ageStep = 1;
-    }
-    if (type == REC_NOTE_ON)
-    {
-      inhibit = !(flags & 1);
-      setPitchGlideTime((flags & 1) ? pitchGlideSamples : 0);
-    }
+    MLEV_NOTE_START(type, rc.typeTimeFlags >> 16, pitchGlideSamples, age, ageStep, inhibit, pg);
     int steps;
     if (type == REC_NOTE_RETRIG)
     {
@@ -370,7 +374,7 @@ MLD void note_rewind(const Rec* recs, uint32_t& nc, uint32_t vend, float& veloci
       steps = dest > next ? dest - next : 0;
     for (int i = 0; i < steps; ++i)
     {
-      (void)pitchGlideNext(pitch);
+      (void)pg.next(pitch);
       age += ageStep;
     }
     if (type == REC_NOTE_OFF) velocity = 0.f;
@@ -397,7 +401,8 @@ MLD void note_rewind(const Rec* recs, uint32_t& nc, uint32_t vend, float& veloci
 //     LinearGlide (8 s per glide, a new target every 8-16 s: moving most of the time in most wavefronts, its mCurrVec slots
 //     read and rewritten every vector - 8 B per voice-sample, what reading the two rows used to cost): pitch[n] = P[n] +
 //     (drift[n] * driftAmount) * kDriftScale, the reference's own operation order (:244, :247).
-// Same operations on the same values as e2s_kernel: a launch of either form leaves the state words the other expects.
+// Same operations on the same values as e2s_kernel (both use note_frame, note_rewind, PitchGlide and drift_step): a launch of either form
+// leaves the state words the other expects.
 // MIDI protocol only: one lane per playing voice, lane == voice index.
 enum : int
 {
