@@ -1027,7 +1027,8 @@ class Graph(_Handle):
 
     @property
     def delay_layout(self):
-        """The delay-ring layout in effect (mlgpu_graph_delay_layout): 0 rows, 1 sectors, 2 transposed pieces."""
+        """The delay-ring layout (mlgpu_graph_delay_layout): 0 rows, 1 32-byte sectors behind LDS windows, 2 transposed 64-byte pieces,
+        4 sector trips. Before compile: the layout asked for, 3 ("best") included; after compile: the one in effect, 3 resolved to 2, 4, 1 or 0."""
         return self._ret(self.L.mlgpu_graph_delay_layout(self.h), None)
 
     def workgroups_per_cu(self):

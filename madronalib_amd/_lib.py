@@ -6,6 +6,7 @@ entry fails loudly — there is no Python/CPU fallback.
 import ctypes
 import os
 import subprocess
+import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -52,6 +53,7 @@ def build(verbose=False):
 
 
 _lib = None
+_load_lock = threading.Lock()
 
 
 def load():
@@ -59,18 +61,18 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    alt = os.environ.get("MLGPU_LIB")   # an alternative build of the same ABI (A/B measurements of a kernel variant)
-    if alt:
-        _lib = ctypes.CDLL(alt)
-        _declare(_lib)
-        return _lib
-    if needs_build():
-        if os.path.exists("/opt/rocm/bin/hipcc") or os.environ.get("HIPCC"):
-            build()
-        elif not os.path.exists(LIB_PATH):
-            raise RuntimeError("libmlgpu.so is not built and hipcc is unavailable; run __graft_entry__.build()")
-    _lib = ctypes.CDLL(LIB_PATH)
-    _declare(_lib)
+    with _load_lock:   # (one thread builds and declares; the handle is published only with its signatures set)
+        if _lib is not None:
+            return _lib
+        alt = os.environ.get("MLGPU_LIB")   # an alternative build of the same ABI (A/B measurements of a kernel variant)
+        if not alt and needs_build():
+            if os.path.exists("/opt/rocm/bin/hipcc") or os.environ.get("HIPCC"):
+                build()
+            elif not os.path.exists(LIB_PATH):
+                raise RuntimeError("libmlgpu.so is not built and hipcc is unavailable; run __graft_entry__.build()")
+        lib = ctypes.CDLL(alt or LIB_PATH)
+        _declare(lib)
+        _lib = lib
     return _lib
 
 

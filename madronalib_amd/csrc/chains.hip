@@ -14,11 +14,14 @@
 // Compile with -ffp-contract=off (see mldsp_math.hpp).
 #include <string.h>
 
+#include "graph_codegen.hpp"
 #include "mlgpu_internal.hpp"
 #include "mldsp_kernels.hpp"
 
 using namespace mldev;
-static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip, "graph.hip's LDS budget counts these strips");
+static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip && kHostTurnClockShift == kTurnClockShift &&
+                  kHostGraphMaxInputs == MLGPU_GRAPH_MAX_INPUTS && kHostGraphMaxOutputs == MLGPU_GRAPH_MAX_OUTPUTS,
+              "graph_codegen.hpp's copies of what the device headers fix");
 
 namespace
 {

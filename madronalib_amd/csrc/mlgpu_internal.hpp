@@ -184,10 +184,6 @@ hipError_t mlgpu_launch_route(bool demux, bool linear, const float* sel, size_t 
                               size_t nElems, hipStream_t stream, uint32_t flags);
 
 // jit.hip, graph.hip — run-time fused kernels (hiprtc)
-// LDS strips of the generated kernels, in floats per WAVEFRONT, for the host's LDS budget (graph.hip does not include the device
-// headers; chains.hip asserts they equal mldev::kMixStrip / kGroup16Strip)
-constexpr int kHostMixStripFloats = 64 * 20 + 3 * 16 + 16;
-constexpr int kHostGroup16StripFloats = 4 * (4 * 80 + 4);
 bool mlgpu_jit_chain(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log);  // honours e->strictSvf
 hipError_t mlgpu_jit_chain_launch(void* fn, const ChainArgs& a, hipStream_t stream);
 bool mlgpu_jit_chain_mix(mlgpu_engine* e, const int32_t* kinds, int n, void** fnSignal, void** fnConst, std::string& log);

@@ -396,6 +396,72 @@ def test_offline_emit_of_round5_generator_forms():
     g.close()
 
 
+def _delay_chain(g, first, n, src):
+    from madronalib_amd.constants import Proc
+    for j in range(first, first + n):
+        g.add(f"d{j}", "proc", Proc.INTEGER_DELAY, [src], max_delay=300.0)
+        src = f"d{j}"
+    return src
+
+
+def test_emit_after_an_edit_describes_the_edited_graph():
+    """A graph stays editable after mlgpu_graph_emit, and the next emit is made of the description as it is then: new nodes, a new
+    output and the ring layout that "best" picks for three rings where it picked another for one."""
+    import madronalib_amd as ml
+    g = ml.Graph(ml.OfflineEngine(), 256, delay_windows="best")
+    g.add("x", "input")
+    g.add_output(_delay_chain(g, 0, 1, "x"))
+    first, _ = g.emit()
+    assert "MLGPU_RING_WINDOWS 2" in first and g.delay_layout == 3
+    g.add_output(_delay_chain(g, 1, 2, "d0"))
+    second, code = g.emit()
+    assert "MLGPU_RING_WINDOWS 3" in second and "MLGPU_RING_WINDOWS 2" not in second
+    assert "// d1\n" in second and "// d2\n" in second and "// d1\n" not in first
+    assert "y0_0[k] = n1_0;" in second and "y1_0[k] = n3_0;" in second and "y1_0" not in first
+    assert code[:4] == b"\x7fELF"
+    g.close()
+
+
+def test_emit_after_set_const_and_set_node_name_shows_them():
+    import struct
+    import madronalib_amd as ml
+    from madronalib_amd.constants import Op
+
+    def literal(value):
+        return "u2f(0x%08xu)" % struct.unpack("<I", struct.pack("<f", value))[0]
+
+    g = ml.Graph(ml.OfflineEngine(), 256)
+    g.add("x", "input")
+    g.add("k", "const", value=0.625)
+    g.add("y", "op", Op.MULTIPLY, ["x", "k"])
+    g.add_output("y")
+    first, _ = g.emit()
+    assert literal(0.625) in first and literal(0.375) not in first
+    g.set_const("k", 0.375)
+    second, _ = g.emit()
+    assert literal(0.375) in second and literal(0.625) not in second
+    assert "// scaled\n" not in second
+    g._check(g.L.mlgpu_graph_set_node_name(g.h, g.ids["y"], b"scaled"))
+    third, _ = g.emit()
+    assert "// scaled\n" in third and "// y\n" not in third and literal(0.375) in third
+    g.close()
+
+
+def test_emit_twice_without_an_edit_is_answered_from_the_graph():
+    import madronalib_amd as ml
+    from madronalib_amd.constants import Op
+    g = ml.Graph(ml.OfflineEngine(), 256)
+    g.add("x", "input")
+    g.add("k", "const", value=0.4375)
+    g.add("y", "op", Op.MULTIPLY, ["x", "k"])
+    g.add_output("y")
+    first = g.emit()
+    stats = ml.jit_stats()
+    assert g.emit() == first
+    assert ml.jit_stats() == stats   # (neither hiprtc nor the caches were asked again)
+    g.close()
+
+
 def test_kernels_travel_to_an_installation_without_hiprtc(monkeypatch):
     """libmlgpu.so does not link hiprtc (round 6): where the compiler is missing, a generated kernel works when its code is there. A
     graph is compiled ahead of time here (no device), every generated kernel of the process is exported as a bundle, the process then
