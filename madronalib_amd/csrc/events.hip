@@ -7,7 +7,9 @@
 //   HOST   the event routing: key states, voice allocation and stealing, unison, sustain pedal, MIDI / MPE channel
 //          rules (processEvent & co, MLEventsToSignals.cpp:445-870; findFreeVoice / findNearestVoice :892-935).
 //          Integer bookkeeping on a handful of events per block; it produces, per voice, a short list of timed
-//          records ("note on at frame 17 with pitch p, velocity v", "pitch bend is now b", ...).
+//          records ("note on at frame 17 with pitch p, velocity v", "pitch bend is now b", ...). That program is
+//          mlev::EventRouter (events_router.cpp, plain C++ without a HIP header); this file owns the device memory,
+//          packs the router's records into pinned staging buffers and uploads them.
 //   DEVICE everything per sample: Voice::beginProcess / writeNoteEvent / endProcess (:75-262) — the sample-accurate
 //          pitch glide, event age -> seconds, five vector-rate glides, the drift random walk, channel pressure and
 //          the MPE main-voice sums — one wavefront lane per voice, all state in HBM between launches only.
@@ -25,18 +27,13 @@
 #include "mlgpu_internal.hpp"
 #include "mldsp_math.hpp"
 #include "mldsp_events.hpp"
+#include "events_router.hpp"
 
 using namespace mldev;
 using namespace mlev;
 
 namespace
 {
-inline Rec makeRec(uint32_t vec, uint32_t type, int time, uint32_t flags, float v1, float v2)
-{
-  const uint32_t t = (uint32_t)std::min(std::max(time, 0), 64);  // destTime = clamp(e.time, 0, 64) (:121)
-  return Rec{vec, type | (t << 8) | (flags << 16), v1, v2};
-}
-
 // ROWS01: only the pitch and gate rows are wanted (what a Synth's voices usually read): an instance of the kernel without the controller
 // rows, the voice-index row and the elapsed-time row. Those are half of the general loop's code and registers; without them the
 // instance keeps its state in registers instead of scratch, and its loop has fewer memory round trips per DSPVector.
@@ -799,20 +796,8 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
 #undef SW
 }
 
-// ---- host: the event routing of EventsToSignals ------------------------------------------------------------------------
-constexpr int kMaxVoices = 16;        // EventsToSignals::kMaxVoices, MLEventsToSignals.h:48
-constexpr int kMaxPhysicalKeys = 128;
-// ---- smoothed controller signals (SmoothedController, MLEventsToSignals.h:170-180, .cpp:264-281; read by a process function
-// through AudioContext::getInputController, MLAudioContext.cpp:129) ----------------------------------------------------------
-// One signal per instrument per WATCHED controller number (mlgpu_events_watch_controllers): one lane per (slot, instrument).
-// Per DSPVector of an awake instrument: output = glide(inputValue), inputValue = the value of the last controller event of
-// that vector or before (:744, :431-436). The records are (vector, value) pairs; lanes without records just keep gliding.
-struct CtlRec
-{
-  uint32_t vecKind;  // vector index inside this launch << 1 | kind (0: inputValue = value, 1: the instrument woke up)
-  float value;
-};
-enum : int { C_AWAKE = 0, C_INPUT, C_GLIDE, kCtlWords = C_GLIDE + kGlideWords };
+// ---- smoothed controller signals: one lane per (watched controller slot, instrument); CtlRec and the C_* state words are in
+// mlev_format.hpp -------------------------------------------------------------------------------------------------------------
 struct CtlArgs
 {
   uint32_t* state;           // [kCtlWords][lanes]
@@ -885,50 +870,22 @@ __global__ __launch_bounds__(256) void ctl_kernel(const CtlArgs a)
   st[(size_t)C_AWAKE * ln] = awake ? 1u : 0u;
   st[(size_t)C_INPUT * ln] = f2u(input);
 }
-
-
-constexpr int kNumControllers = 129;
-constexpr int kChannelPressureControllerIdx = 128;
-
-struct KeyState
-{
-  int state{0};  // 0 off, 1 on, 2 sustained
-  float pitch{0.f};
-  uint32_t noteOnIndex{0};
-};
-struct HostVoice
-{
-  size_t creatorKeyIdx{0};
-  float currentVelocity{0.f};
-  int nextFrame{0};  // Voice::nextFrameToProcess inside the vector being routed (0 at its start: beginProcess, :115)
-};
-struct Instrument
-{
-  std::vector<mlgpu_event> events;  // time-sorted (addEvent, :367-372)
-  KeyState keys[kMaxPhysicalKeys];
-  HostVoice voices[kMaxVoices + 1];
-  int lastFreeVoiceFound{-1};
-  int newestVoice{-1};
-  bool sustainPedal{false};
-  uint32_t currentNoteOnIndex{0};
-  bool awake{false}, awakeSent{false};
-  std::vector<float> ctlInput;  // controllers[n].inputValue (:744), from the first controller event on
-};
 }  // namespace
 
+// the kernels read a lane's range as a uint4; the host router writes it as a LaneRange
+static_assert(sizeof(LaneRange) == sizeof(uint4) && offsetof(LaneRange, lane) == offsetof(uint4, x) && offsetof(LaneRange, first) == offsetof(uint4, y) &&
+                  offsetof(LaneRange, last) == offsetof(uint4, z) && offsetof(LaneRange, pad) == offsetof(uint4, w),
+              "LaneRange is the uint4 of set_rec_ranges_kernel");
+
+// ---- host: the event routing is mlev::EventRouter (events_router.cpp, plain C++); here its records go to the device ----------------
 struct mlgpu_events
 {
-  mlgpu_engine* e{nullptr};
-  size_t nInstruments{0};
-  int polyphony{0}, group{1}, slotBase{1};  // MIDI: one lane per playing voice; MPE: pow2 groups with the main voice at lane 0
-  size_t maxLanes{0};
-  bool mpe{false}, unison{false};
-  int voiceModCC{16};
+  mlgpu_events(mlgpu_engine* engine, size_t nInstruments, int polyphony) : e(engine), router(nInstruments, polyphony) {}
+  mlgpu_engine* e;
+  EventRouter router;  // key states, voice allocation, the protocol and its lane grouping, this launch's records
   double sr{0};
   float pitchBendRange{7.f}, mpePitchBendRange{24.f}, pitchGlideSeconds{0.f}, driftAmount{0.f};
-  std::vector<Instrument> inst;
-  std::vector<std::vector<Rec>> laneRecs;  // per lane, this launch
-  std::vector<uint32_t> dirtyLanes;        // lanes with records (most have none)
+  uint32_t rowMask{0xFFu};                 // mlgpu_events_set_wanted_rows
   DeviceBuffer<uint32_t> d_state;
   // [lanes]: where a lane's records of the coming launch are, {0, 0} for none. Only the lanes that have records are written per
   // launch (a few hundred of 262 144: the list goes up in kilobytes where a start offset per lane was a megabyte over PCIe
@@ -940,8 +897,8 @@ struct mlgpu_events
   {
     PinnedBuffer<Rec> h_recs;
     DeviceBuffer<Rec> d_recs;
-    PinnedBuffer<uint4> h_dirty;  // {lane, first record, one past the last, 0} for every lane that has records in this launch
-    DeviceBuffer<uint4> d_dirty;
+    PinnedBuffer<LaneRange> h_dirty;  // every lane that has records in this launch
+    DeviceBuffer<LaneRange> d_dirty;
     size_t recCapacity{0}, dirtyCapacity{0};
     size_t nDirtySet{0};       // lanes whose range set_rec_ranges_kernel has set for the block in flight and no kernel has consumed yet
     OwnedEvent done;
@@ -949,13 +906,9 @@ struct mlgpu_events
   } stage[2];
   int stageIdx{0};
   // watched controllers (mlgpu_events_watch_controllers): lane = slot * nInstruments + instrument
-  std::vector<int> watched;
-  int slotOf[kNumControllers];
   size_t ctlMaxVectors{0}, ctlCapacityVectors{0};  // longest launch allowed / what d_ctlOut was allocated for
   DeviceBuffer<float> d_ctlOut;
   DeviceBuffer<uint32_t> d_ctlState;
-  std::vector<std::vector<CtlRec>> ctlLaneRecs;
-  std::vector<uint32_t> ctlDirty;
   struct CtlStaging
   {
     PinnedBuffer<CtlRec> h_recs;
@@ -964,21 +917,12 @@ struct mlgpu_events
     DeviceBuffer<uint32_t> d_recStart;
     size_t recCapacity{0};
   } ctlStage[2];
-  size_t ctlLanes() const { return watched.size() * nInstruments; }
-  void pushCtl(size_t instrument, int slot, uint32_t vec, uint32_t kind, float value)
-  {
-    const size_t l = (size_t)slot * nInstruments + instrument;
-    if (ctlLaneRecs[l].empty()) ctlDirty.push_back((uint32_t)l);
-    ctlLaneRecs[l].push_back(CtlRec{(vec << 1) | kind, value});
-  }
-  uint32_t rowMask{0xFFu};                 // mlgpu_events_set_wanted_rows
   // e2s_ctl_kernel's outputs (mlgpu_events_prepare_for_graph): control records [T][kCtlRecWords][lanes] and the two side signals
   DeviceBuffer<uint32_t> d_ctlRecs;
   DeviceBuffer<float> d_rowP;
   DeviceBuffer<float> d_rowG;
   size_t ctlRecVectors{0};
   bool ctlRecReserved{false};  // mlgpu_events_reserve_for_graph was called: process calls never allocate, longer blocks are refused
-  size_t lanes() const { return nInstruments * (size_t)group; }
 };
 
 void mlgpu_graph_forget_events(mlgpu_events* ev);  // graph.hip
@@ -990,247 +934,56 @@ int efail(mlgpu_events* ev, int st, const std::string& what)
   if (ev && ev->e) ev->e->lastError = what;
   return st;
 }
-bool soonerThan(const mlgpu_event& a, const mlgpu_event& b)  // :356-364
+
+// a pinned + device pair of upload buffers, replaced by a larger one (twice the need, `least` at least) when `need` elements do not fit
+template <class T>
+bool growPair(PinnedBuffer<T>& host, DeviceBuffer<T>& dev, size_t& capacity, size_t need, size_t least)
 {
-  if (a.time != b.time) return a.time < b.time;
-  return a.type < b.type;
+  if (need <= capacity) return true;
+  capacity = std::max(least, 2 * need);
+  if (allocate(dev, capacity) == hipSuccess && allocate(host, capacity) == hipSuccess) return true;
+  capacity = 0;
+  return false;
 }
-int keyIndex(const mlgpu_events* ev, const mlgpu_event& e) { return ev->mpe ? e.channel : e.source_idx; }  // getKeyIndex, :21-42
 
-struct Router  // one instrument, one vector
+// the settings the kernels need, from the object's
+E2SSettings deviceSettings(const mlgpu_events* ev)
 {
-  mlgpu_events* ev;
-  Instrument& in;
-  size_t instIdx;
-  uint32_t vec;
-  void push(int voice, const Rec& r)
-  {
-    if (voice < 0 || voice > ev->polyphony) return;  // voices the device does not simulate (beyond the polyphony)
-    if (voice < ev->slotBase) return;  // MIDI mode: the MPE main voice is not simulated (its signals are not used, :437-445)
-    std::vector<Rec>& lr = ev->laneRecs[instIdx * (size_t)ev->group + (size_t)(voice - ev->slotBase)];
-    if (lr.empty()) ev->dirtyLanes.push_back((uint32_t)(instIdx * (size_t)ev->group + (size_t)(voice - ev->slotBase)));
-    lr.push_back(r);
-  }
-  // Voice::writeNoteEvent's host-visible effects (:115-216): creatorKeyIdx_ and currentVelocity
-  void note(int v, const mlgpu_event& e, uint32_t type, int keyIdx, bool doGlide, bool doReset)
-  {
-    HostVoice& hv = in.voices[v];
-    // writeNoteEvent ends with nextFrameToProcess = its own frame (:141, :204) - also when that lies BEFORE the frame the voice's
-    // previous note event of this vector ended on. Events come sorted by time, so only an event the reference makes up itself can do
-    // that: the note-off of a sustain-pedal release, built with Event's default time 0 (:833-836). The frames written so far are then
-    // written again by what follows; the record says so (REC_FLAG_REWIND) and the kernels replay it (mlev::note_rewind).
-    int dest = std::min(std::max((int)e.time, 0), MLGPU_FLOATS_PER_DSPVECTOR);
-    if (type == MLGPU_EVENT_NOTE_RETRIG && dest == 0) dest = 1;
-    const uint32_t rewind = (type == MLGPU_EVENT_NOTE_ON || type == MLGPU_EVENT_NOTE_RETRIG || type == MLGPU_EVENT_NOTE_OFF) && dest == 0 && hv.nextFrame > 0 ? (uint32_t)REC_FLAG_REWIND : 0u;
-    if (type == MLGPU_EVENT_NOTE_ON || type == MLGPU_EVENT_NOTE_RETRIG)
-    {
-      hv.creatorKeyIdx = (size_t)keyIdx;
-      hv.currentVelocity = e.value2;
-      hv.nextFrame = dest;
-      push(v, makeRec(vec, type == MLGPU_EVENT_NOTE_ON ? REC_NOTE_ON : REC_NOTE_RETRIG, e.time, (doGlide ? 1u : 0u) | (doReset ? 2u : 0u) | rewind, e.value1, e.value2));
-    }
-    else if (type == MLGPU_EVENT_NOTE_OFF)
-    {
-      hv.creatorKeyIdx = 0;
-      hv.currentVelocity = 0.f;
-      hv.nextFrame = dest;
-      push(v, makeRec(vec, REC_NOTE_OFF, e.time, rewind, 0.f, 0.f));
-    }
-    // kNoteSustain and everything else: no change (default:, :211-213)
-  }
-  size_t countHeldNotes() const  // :471-482
-  {
-    size_t n = 0;
-    for (int i = 0; i < kMaxPhysicalKeys; ++i) n += (in.keys[i].state == 1);
-    return n;
-  }
-  int findFreeVoice()  // :892-912
-  {
-    const int highest = ev->polyphony + 1;
-    int t = in.lastFreeVoiceFound;
-    for (int i = 1; i < ev->polyphony + 1; ++i)
-    {
-      t++;
-      if (t >= highest) t = 1;
-      if (in.voices[t].creatorKeyIdx == 0)
-      {
-        in.lastFreeVoiceFound = t;
-        return t;
-      }
-    }
-    return -1;
-  }
-  int findNearestVoice(int note)  // :922-937
-  {
-    int r = 0;
-    size_t minDist = 128;
-    for (int v = 1; v < ev->polyphony + 1; ++v)
-    {
-      const size_t dist = (size_t)std::abs(note - (int)in.voices[v].creatorKeyIdx);
-      if (dist < minDist)
-      {
-        minDist = dist;
-        r = v;
-      }
-    }
-    return r;
-  }
-  void noteOn(const mlgpu_event& e)  // :519-560
-  {
-    const int k = keyIndex(ev, e) & (kMaxPhysicalKeys - 1);
-    in.keys[k].state = 1;
-    in.keys[k].noteOnIndex = in.currentNoteOnIndex++;
-    in.keys[k].pitch = e.value1;
-    if (ev->unison)
-    {
-      const bool firstNote = (countHeldNotes() == 1);
-      for (int v = 1; v < ev->polyphony + 1; ++v) note(v, e, MLGPU_EVENT_NOTE_ON, k, !firstNote, firstNote);
-    }
-    else
-    {
-      int v = findFreeVoice();
-      if (v >= 1) note(v, e, MLGPU_EVENT_NOTE_ON, k, true, true);
-      else
-      {
-        v = findNearestVoice(e.source_idx);  // findVoiceToSteal, :914-918
-        note(v, e, MLGPU_EVENT_NOTE_RETRIG, k, true, true);
-      }
-      in.newestVoice = v;
-    }
-  }
-  void noteOff(const mlgpu_event& e)  // :562-632
-  {
-    const int k = keyIndex(ev, e) & (kMaxPhysicalKeys - 1);
-    in.keys[k].state = in.sustainPedal ? 2 : 0;
-    if (ev->unison)
-    {
-      if (countHeldNotes() == 0)
-      {
-        for (int v = 1; v < ev->polyphony + 1; ++v) note(v, e, MLGPU_EVENT_NOTE_OFF, 0, true, true);
-      }
-      else if ((size_t)k == in.voices[1].creatorKeyIdx)
-      {
-        mlgpu_event f = e;  // change note without retriggering the envelope, keeping the current velocity
-        f.value2 = in.voices[1].currentVelocity;
-        uint32_t maxIdx = 0, mostRecent = 0;
-        for (int i = 0; i < kMaxPhysicalKeys; ++i)
-          if (in.keys[i].state == 1 && in.keys[i].noteOnIndex > maxIdx)
-          {
-            maxIdx = in.keys[i].noteOnIndex;
-            mostRecent = (uint32_t)i;
-          }
-        f.value1 = in.keys[mostRecent].pitch;
-        for (int v = 1; v < ev->polyphony + 1; ++v) note(v, f, MLGPU_EVENT_NOTE_ON, (int)mostRecent, true, true);
-      }
-    }
-    else if (!in.sustainPedal)
-    {
-      for (int v = 1; v < ev->polyphony + 1; ++v)
-        if (in.voices[v].creatorKeyIdx == (size_t)k) note(v, e, MLGPU_EVENT_NOTE_OFF, k, true, true);
-    }
-  }
-  void setAll(uint32_t rec, float val)
-  {
-    for (int v = 1; v < ev->polyphony + 1; ++v) push(v, makeRec(vec, rec, 0, 0, val, 0.f));
-  }
-  void setMatching(uint32_t rec, int channel, float val)
-  {
-    for (int v = 1; v < ev->polyphony + 1; ++v)
-      if (in.voices[v].creatorKeyIdx == (size_t)channel) push(v, makeRec(vec, rec, 0, 0, val, 0.f));
-  }
-  void setControllerInput(size_t ctrl, float val)  // controllers[ctrl].inputValue = val (:650, :744)
-  {
-    if (in.ctlInput.empty()) in.ctlInput.assign(kNumControllers, 0.f);  // kept from the first controller event on, watched or not
-    in.ctlInput[ctrl] = val;
-    if (ev->slotOf[ctrl] >= 0) ev->pushCtl(instIdx, ev->slotOf[ctrl], vec, 0u, val);
-  }
-  void controller(const mlgpu_event& e)  // :735-822
-  {
-    const float val = e.value1;
-    const size_t ctrl = std::min((size_t)e.source_idx, (size_t)kNumControllers - 1);
-    setControllerInput(ctrl, val);
-    if (ctrl == kChannelPressureControllerIdx)  // controllers[128].inputValue is what MIDI channel pressure writes too
-      for (int v = 0; v < ev->polyphony + 1; ++v) push(v, makeRec(vec, REC_SET_CHANNEL_PRESSURE, 0, 0, val, 0.f));
-    if (ctrl == 120) return;  // "all sound off" clears the event buffer it is iterating in the reference (:749-755): not reproduced
-    if (ctrl == 123)
-    {
-      if (val == 0)  // all notes off, :757-769
-        for (int v = 0; v < kMaxVoices + 1; ++v) note(v, e, MLGPU_EVENT_NOTE_OFF, 0, false, true);
-      return;
-    }
-    for (int v = 1; v < ev->polyphony + 1; ++v)
-    {
-      if (ev->mpe && in.voices[v].creatorKeyIdx != (size_t)e.channel) continue;
-      if ((int)ctrl == ev->voiceModCC) push(v, makeRec(vec, REC_SET_MOD, 0, 0, val, 0.f));
-      if (ctrl == 73) push(v, makeRec(vec, REC_SET_X, 0, 0, val, 0.f));
-      else if (ctrl == 74) push(v, makeRec(vec, REC_SET_Y, 0, 0, val, 0.f));
-    }
-  }
-  void process(const mlgpu_event& e)  // processEvent, :485-515
-  {
-    switch (e.type)
-    {
-      case MLGPU_EVENT_NOTE_ON: noteOn(e); break;
-      case MLGPU_EVENT_NOTE_OFF: noteOff(e); break;
-      case MLGPU_EVENT_CONTROLLER: controller(e); break;
-      case MLGPU_EVENT_PITCH_BEND:  // :700-731
-        if (!ev->mpe) setAll(REC_SET_BEND, e.value1);
-        else if (e.channel == 1) push(0, makeRec(vec, REC_SET_BEND, 0, 0, e.value1, 0.f));
-        else if (e.channel != 0) setMatching(REC_SET_BEND, e.channel, e.value1);
-        break;
-      case MLGPU_EVENT_NOTE_PRESSURE:  // :676-698: per-key pressure in MIDI mode, ignored in MPE mode
-        if (!ev->mpe) setMatching(REC_SET_Z, e.source_idx, e.value1);
-        break;
-      case MLGPU_EVENT_CHANNEL_PRESSURE:  // :637-674
-        if (!ev->mpe)
-        {
-          setControllerInput(kChannelPressureControllerIdx, e.value1);
-          for (int v = 0; v < ev->polyphony + 1; ++v) push(v, makeRec(vec, REC_SET_CHANNEL_PRESSURE, 0, 0, e.value1, 0.f));
-        }
-        else if (e.channel == 1) push(0, makeRec(vec, REC_SET_Z, 0, 0, e.value1, 0.f));
-        else if (e.channel != 0) setMatching(REC_SET_Z, e.channel, e.value1);
-        break;
-      case MLGPU_EVENT_SUSTAIN_PEDAL:  // :824-842
-        in.sustainPedal = (e.value1 > 0.5f);
-        if (!in.sustainPedal)
-          for (int i = 1; i < ev->polyphony + 1; ++i)
-            if (in.keys[in.voices[i].creatorKeyIdx & (kMaxPhysicalKeys - 1)].state == 2)
-            {
-              mlgpu_event off{};
-              off.type = MLGPU_EVENT_NOTE_OFF;
-              note(i, off, MLGPU_EVENT_NOTE_OFF, 0, true, true);
-            }
-        break;
-      default: break;
-    }
-  }
-};
+  E2SSettings s;
+  memset(&s, 0, sizeof(s));
+  s.sr = ev->sr;
+  s.pitchBendRange = ev->pitchBendRange;
+  s.mpePitchBendRange = ev->mpePitchBendRange;
+  s.driftAmount = ev->driftAmount;
+  s.pitchGlideSamples = (int32_t)(ev->sr * ev->pitchGlideSeconds);  // :90
+  float c[2];
+  mlgpu_linear_glide_make_coeffs((float)(ev->sr * 0.02f), c);          // kGlideTimeSeconds / kControllerGlideTimeSeconds
+  memcpy(&s.glideVectors, &c[0], 4);
+  s.glideDy = c[1];
+  mlgpu_linear_glide_make_coeffs((float)(ev->sr * 8.0f), c);           // kDriftTimeSeconds
+  memcpy(&s.driftGlideVectors, &c[0], 4);
+  s.driftGlideDy = c[1];
+  mlgpu_linear_glide_make_coeffs((float)(int)(ev->sr * 0.02f), c);    // SmoothedController: int glideTimeInSamples = sr * 0.02f (:275)
+  memcpy(&s.ctlGlideVectors, &c[0], 4);
+  s.ctlGlideDy = c[1];
+  s.mpe = ev->router.mpe() ? 1 : 0;
+  return s;
+}
 
-// the state of freshly constructed / reset voices (EventsToSignals ctor :290-305, Voice::reset :58-84)
-void initialState(const mlgpu_events* ev, std::vector<uint32_t>& st)
+// what E2SArgs and E2SCtlArgs both take from a prepared block
+template <class Args>
+Args kernelArgs(const EventsDev& dev, size_t nVectors, uint32_t flags)
 {
-  const size_t lanes = ev->lanes();
-  st.assign((size_t)kStateWords * lanes, 0u);
-  auto W = [&](int word, size_t lane) -> uint32_t& { return st[(size_t)word * lanes + lane]; };
-  const uint32_t minusOne = 0xFFFFFFFFu;
-  for (size_t lane = 0; lane < lanes; ++lane)
-  {
-    const int slot = (int)(lane % (size_t)ev->group) + ev->slotBase;
-    W(S_PG_REMAINING, lane) = minusOne;       // SampleAccurateLinearGlide defaults, MLDSPGens.h:519-524
-    W(S_PG_PER_GLIDE, lane) = 32;
-    const float dy = 1.f / 32;
-    memcpy(&W(S_PG_DY, lane), &dy, 4);
-    W(S_DRIFT_SEED, lane) = (uint32_t)(slot * 232);  // driftSource.seed_ = voiceIndex * 232, :60
-    W(S_RECALC, lane) = 1u;
-    for (int gl = 0; gl < kNumGlides; ++gl)
-    {
-      const int base = S_GLIDES + gl * kGlideWords;
-      // reset() calls setValue(0) on bend / mod / x / y / z: remaining = 0; the drift and controller glides are
-      // default-constructed: remaining = -1 (MLDSPGens.h:441)
-      W(base + 2, lane) = (gl <= 4) ? 0u : minusOne;
-      W(base + 3, lane) = 1u;  // mCurrVec is all zeros: uniform
-    }
-  }
+  Args a;
+  memset(&a, 0, sizeof(a));
+  a.state = dev.state;
+  a.recs = (const Rec*)dev.recs;
+  a.recRange = dev.recRange;
+  a.lanes = dev.lanes;
+  a.T = nVectors;
+  a.flags = flags;
+  a.s = dev.s;
+  return a;
 }
 }  // namespace
 
@@ -1239,11 +992,8 @@ static void freeControllers(mlgpu_events* ev)
   ev->d_ctlOut.reset();
   ev->d_ctlState.reset();
   for (mlgpu_events::CtlStaging& st : ev->ctlStage) st = mlgpu_events::CtlStaging();
-  ev->watched.clear();
-  ev->ctlLaneRecs.clear();
-  ev->ctlDirty.clear();
+  ev->router.unwatch();
   ev->ctlMaxVectors = 0;
-  for (int& x : ev->slotOf) x = -1;
 }
 extern "C"
 {
@@ -1267,25 +1017,18 @@ extern "C"
         st.h_recs.reset();
         st.h_recStart.reset();
       }
-      std::vector<Instrument>().swap(ev->inst);
-      std::vector<std::vector<Rec>>().swap(ev->laneRecs);
-      std::vector<std::vector<CtlRec>>().swap(ev->ctlLaneRecs);
+      ev->router = EventRouter();
     });
   }
 
   int mlgpu_events_clear(mlgpu_events* ev)  // EventsToSignals::clear, :330-340
   {
     if (!ev) return MLGPU_ERR_INVALID;
-    for (Instrument& in : ev->inst)
-    {
-      in.events.clear();
-      for (HostVoice& v : in.voices) v = HostVoice();
-      in.lastFreeVoiceFound = 0;
-    }
+    ev->router.clear();
     // Voice::reset keeps the glides' and the drift's running state except what setValue(0) touches; a freshly built
     // bank and a cleared one differ only there. This implementation resets the device state completely.
     std::vector<uint32_t> st;
-    initialState(ev, st);
+    ev->router.initialVoiceState(st);
     if (hipSetDevice(ev->e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     return mlgpu_upload(ev->e, ev->d_state.get(), st.data(), st.size() * sizeof(uint32_t));
   }
@@ -1299,23 +1042,13 @@ extern "C"
       e->lastError = "events_create: 1+ instruments, polyphony 1..16 (EventsToSignals::kMaxVoices)";
       return MLGPU_ERR_INVALID;
     }
-    std::unique_ptr<mlgpu_events> ev(new (std::nothrow) mlgpu_events());
+    std::unique_ptr<mlgpu_events> ev(new (std::nothrow) mlgpu_events(e, nInstruments, polyphony));
     if (!ev) return MLGPU_ERR_OOM;
-    ev->e = e;
-    for (int& x : ev->slotOf) x = -1;
-    ev->nInstruments = nInstruments;
-    ev->polyphony = polyphony;
-    int pow2 = 1;
-    while (pow2 < polyphony + 1) pow2 <<= 1;
-    ev->maxLanes = nInstruments * (size_t)pow2;
-    ev->group = polyphony;  // MIDI (the default protocol)
-    ev->slotBase = 1;
-    ev->inst.resize(nInstruments);
-    ev->laneRecs.resize(ev->maxLanes);
+    const size_t maxLanes = ev->router.maxLanes();
     hipError_t err = hipSetDevice(e->device);
-    if (err == hipSuccess) err = allocate(ev->d_state, (size_t)kStateWords * ev->maxLanes);
-    if (err == hipSuccess) err = allocate(ev->d_recRange, ev->maxLanes);
-    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * ev->maxLanes, e->stream);
+    if (err == hipSuccess) err = allocate(ev->d_state, (size_t)kStateWords * maxLanes);
+    if (err == hipSuccess) err = allocate(ev->d_recRange, maxLanes);
+    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * maxLanes, e->stream);
     for (mlgpu_events::Staging& st : ev->stage)
       if (err == hipSuccess) err = allocate(st.done, hipEventDisableTiming);
     if (err != hipSuccess)
@@ -1323,9 +1056,7 @@ extern "C"
       e->lastError = std::string("events_create: ") + hipGetErrorString(err);
       return err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP;
     }
-    for (Instrument& in : ev->inst) in.lastFreeVoiceFound = -1;
     const int st = mlgpu_events_clear(ev.get());
-    for (Instrument& in : ev->inst) in.lastFreeVoiceFound = 0;  // setPolyphony calls clear() (:316-321)
     if (st != MLGPU_OK) return st;
     *out = ev.release();
     return MLGPU_OK;
@@ -1334,7 +1065,8 @@ extern "C"
   static int markRecalc(mlgpu_events* ev)
   {
     if (hipSetDevice(ev->e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    return mlgpu_fill32(ev->e, ev->d_state.get() + (size_t)S_RECALC * ev->lanes(), 1u, ev->lanes());
+    const size_t lanes = ev->router.lanes();
+    return mlgpu_fill32(ev->e, ev->d_state.get() + (size_t)S_RECALC * lanes, 1u, lanes);
   }
   int mlgpu_events_set_sample_rate(mlgpu_events* ev, double sr)
   {
@@ -1345,22 +1077,11 @@ extern "C"
   int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe)  // setProtocol clears (:92-96)
   {
     if (!ev) return MLGPU_ERR_INVALID;
-    ev->mpe = mpe != 0;
-    if (ev->mpe)
-    {
-      ev->group = 1;
-      while (ev->group < ev->polyphony + 1) ev->group <<= 1;
-      ev->slotBase = 0;
-    }
-    else
-    {
-      ev->group = ev->polyphony;
-      ev->slotBase = 1;
-    }
+    ev->router.setProtocol(mpe != 0);
     return mlgpu_events_clear(ev);
   }
-  int mlgpu_events_set_unison(mlgpu_events* ev, int on) { return ev ? (ev->unison = on != 0, MLGPU_OK) : MLGPU_ERR_INVALID; }
-  int mlgpu_events_set_mod_cc(mlgpu_events* ev, int cc) { return ev ? (ev->voiceModCC = cc, MLGPU_OK) : MLGPU_ERR_INVALID; }
+  int mlgpu_events_set_unison(mlgpu_events* ev, int on) { return ev ? (ev->router.setUnison(on != 0), MLGPU_OK) : MLGPU_ERR_INVALID; }
+  int mlgpu_events_set_mod_cc(mlgpu_events* ev, int cc) { return ev ? (ev->router.setModCC(cc), MLGPU_OK) : MLGPU_ERR_INVALID; }
   int mlgpu_events_set_pitch_bend_semitones(mlgpu_events* ev, float f) { return ev ? (ev->pitchBendRange = f, MLGPU_OK) : MLGPU_ERR_INVALID; }
   int mlgpu_events_set_mpe_pitch_bend_semitones(mlgpu_events* ev, float f) { return ev ? (ev->mpePitchBendRange = f, MLGPU_OK) : MLGPU_ERR_INVALID; }
   int mlgpu_events_set_drift_amount(mlgpu_events* ev, float f) { return ev ? (ev->driftAmount = f, MLGPU_OK) : MLGPU_ERR_INVALID; }
@@ -1376,67 +1097,42 @@ extern "C"
     ev->rowMask = mask & 0xFFu;
     return MLGPU_OK;
   }
-  size_t mlgpu_events_num_voices(mlgpu_events* ev) { return ev ? ev->nInstruments * (size_t)ev->polyphony : 0; }
-  int mlgpu_events_newest_voice(mlgpu_events* ev, size_t instrument) { return (ev && instrument < ev->nInstruments) ? ev->inst[instrument].newestVoice - 1 : -2; }
+  size_t mlgpu_events_num_voices(mlgpu_events* ev) { return ev ? ev->router.instruments() * (size_t)ev->router.polyphony() : 0; }
+  int mlgpu_events_newest_voice(mlgpu_events* ev, size_t instrument) { return (ev && instrument < ev->router.instruments()) ? ev->router.newestVoice(instrument) - 1 : -2; }
 
   int mlgpu_events_add_event(mlgpu_events* ev, size_t instrument, const mlgpu_event* e)  // addEvent, :367-372
   {
     if (!ev || !e) return MLGPU_ERR_INVALID;
-    if (instrument >= ev->nInstruments) return efail(ev, MLGPU_ERR_RANGE, "events_add_event: instrument out of range");
-    Instrument& in = ev->inst[instrument];
-    in.awake = true;
-    in.events.insert(std::lower_bound(in.events.begin(), in.events.end(), *e, soonerThan), *e);
+    if (instrument >= ev->router.instruments()) return efail(ev, MLGPU_ERR_RANGE, "events_add_event: instrument out of range");
+    ev->router.addEvent(instrument, *e);
     return MLGPU_OK;
   }
   int mlgpu_events_add_events(mlgpu_events* ev, const uint32_t* instruments, const mlgpu_event* events, size_t n)  // a block's events in one call
   {
     if (!ev || (n && (!instruments || !events))) return MLGPU_ERR_INVALID;
     for (size_t i = 0; i < n; ++i)
-      if (instruments[i] >= ev->nInstruments) return efail(ev, MLGPU_ERR_RANGE, "events_add_events: instrument out of range");
-    for (size_t i = 0; i < n; ++i)
-    {
-      Instrument& in = ev->inst[instruments[i]];
-      in.awake = true;
-      in.events.insert(std::lower_bound(in.events.begin(), in.events.end(), events[i], soonerThan), events[i]);
-    }
+      if (instruments[i] >= ev->router.instruments()) return efail(ev, MLGPU_ERR_RANGE, "events_add_events: instrument out of range");
+    for (size_t i = 0; i < n; ++i) ev->router.addEvent(instruments[i], events[i]);
     return MLGPU_OK;
   }
   int mlgpu_events_clear_events(mlgpu_events* ev)  // clearEvents, once per host block (MLSignalProcessBuffer.cpp:89)
   {
     if (!ev) return MLGPU_ERR_INVALID;
-    for (Instrument& in : ev->inst) in.events.clear();
+    ev->router.clearEvents();
     return MLGPU_OK;
   }
 
   // The controller lanes of one launch: their records uploaded into the staging set of this launch (free once the launch
   // before last has finished, which prepare() has just waited for), then ctl_kernel on the engine's stream - ahead of the
   // kernel that reads the signals.
-  static int processControllers(mlgpu_events* ev, size_t nVectors, int stageIdx)
+  static int processControllers(mlgpu_events* ev, size_t nVectors, int stageIdx, const E2SSettings& s)
   {
     mlgpu_engine* e = ev->e;
+    const EventRouter& router = ev->router;
     mlgpu_events::CtlStaging& sg = ev->ctlStage[stageIdx];
-    const size_t lanes = ev->ctlLanes();
-    size_t nRecs = 0;
-    for (uint32_t l : ev->ctlDirty) nRecs += ev->ctlLaneRecs[l].size();
-    if (nRecs + 1 > sg.recCapacity)
-    {
-      sg.recCapacity = std::max<size_t>(1024, 2 * (nRecs + 1));
-      if (allocate(sg.d_recs, sg.recCapacity) != hipSuccess || allocate(sg.h_recs, sg.recCapacity) != hipSuccess)
-      {
-        sg.recCapacity = 0;
-        return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
-      }
-    }
-    std::sort(ev->ctlDirty.begin(), ev->ctlDirty.end());
-    size_t next = 0, n = 0;
-    for (uint32_t l : ev->ctlDirty)
-    {
-      for (; next <= l; ++next) sg.h_recStart[next] = (uint32_t)n;
-      const std::vector<CtlRec>& lr = ev->ctlLaneRecs[l];
-      memcpy(sg.h_recs.get() + n, lr.data(), sizeof(CtlRec) * lr.size());
-      n += lr.size();
-    }
-    for (; next <= lanes; ++next) sg.h_recStart[next] = (uint32_t)n;
+    const size_t lanes = router.ctlLanes(), nRecs = router.ctlRecordCount();
+    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, 1024)) return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
+    router.packControllers(sg.h_recs.get(), sg.h_recStart.get());
     hipError_t err = hipMemcpyAsync(sg.d_recStart.get(), sg.h_recStart.get(), sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream);
     if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream);
     if (err != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process controller upload: ") + hipGetErrorString(err));
@@ -1445,24 +1141,18 @@ extern "C"
     a.recs = sg.d_recs.get();
     a.recStart = sg.d_recStart.get();
     a.out = ev->d_ctlOut.get();
-    a.nInstruments = ev->nInstruments;
+    a.nInstruments = router.instruments();
     a.lanes = lanes;
     a.T = nVectors;
-    a.slotStride = 64 * ev->ctlCapacityVectors * ev->nInstruments;  // (the capacity, not the current limit: a slot's signal stays where it is while the buffer is not replaced)
-    float c[2];
-    mlgpu_linear_glide_make_coeffs((float)(int)(ev->sr * 0.02f), c);  // int glideTimeInSamples = sr * kControllerGlideTimeSeconds (:275)
-    memcpy(&a.glideVectors, &c[0], 4);
-    a.glideDy = c[1];
+    a.slotStride = 64 * ev->ctlCapacityVectors * router.instruments();  // (the capacity, not the current limit: a slot's signal stays where it is while the buffer is not replaced)
+    a.glideVectors = s.ctlGlideVectors;
+    a.glideDy = s.ctlGlideDy;
     hipLaunchKernelGGL(ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
     err = hipGetLastError();
     if (err != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process controller launch: ") + hipGetErrorString(err));
     return MLGPU_OK;
   }
 
-  // Everything of processVector (:376-466) that happens on the host for nVectors DSPVectors starting at frame startOffset of the
-  // event times: the block's events routed into per-voice records, the records uploaded (asynchronously, into the staging set
-  // that is free), the settings the device needs. The caller launches the kernel that consumes them - e2s_kernel, or a voice
-  // graph whose pitch and gate rows are source nodes (graph.hip) - and then calls launched().
   // The per-lane record ranges are device state: set from the block's lane list, cleared by the kernel that consumes them. A block that
   // fails after they were set and before that kernel ran would leave them pointing into a staging buffer the NEXT block does not
   // use: put them back to "no records" (stream-ordered, the list is still in sg.d_dirty).
@@ -1476,82 +1166,29 @@ extern "C"
     if (hipEventRecord(sg.done.get(), ev->e->stream) == hipSuccess) sg.pending = true;
   }
 
+  // One block of nVectors DSPVectors starting at frame startOffset of the event times, up to the kernel that consumes it: the block's
+  // events routed into per-voice records, the records uploaded (asynchronously, into the staging set that is free), the controller
+  // lanes run, the settings the device needs. The caller launches the consuming kernel - e2s_kernel, or a voice graph whose pitch and
+  // gate rows are source nodes (graph.hip) - and then calls launched().
   static int prepare(mlgpu_events* ev, size_t nVectors, int startOffset, EventsDev& dev, mlgpu_events::Staging*& sgOut)
   {
     mlgpu_engine* e = ev->e;
-    // ---- route this launch's events into per-voice records ----
-    for (uint32_t l : ev->dirtyLanes) ev->laneRecs[l].clear();
-    ev->dirtyLanes.clear();
-    for (uint32_t l : ev->ctlDirty) ev->ctlLaneRecs[l].clear();
-    ev->ctlDirty.clear();
-    if (!ev->watched.empty() && nVectors > ev->ctlMaxVectors)
+    EventRouter& router = ev->router;
+    if (!router.watched().empty() && nVectors > ev->ctlMaxVectors)
       return efail(ev, MLGPU_ERR_RANGE, "events_process: more DSPVectors than events_watch_controllers reserved the controller signals for");
-    for (size_t i = 0; i < ev->nInstruments; ++i)
-    {
-      Instrument& in = ev->inst[i];
-      if (!in.awake) continue;
-      if (in.events.empty() && in.awakeSent) continue;  // nothing to route: the voices just keep gliding on the device
-      for (size_t t = 0; t < nVectors; ++t)
-      {
-        Router r{ev, in, i, (uint32_t)t};
-        for (int v = 0; v < kMaxVoices + 1; ++v) in.voices[v].nextFrame = 0;
-        if (!in.awakeSent)
-        {
-          for (int v = 0; v < ev->polyphony + 1; ++v) r.push(v, makeRec((uint32_t)t, REC_AWAKE, 0, 0, 0.f, 0.f));
-          for (size_t sl = 0; sl < ev->watched.size(); ++sl) ev->pushCtl(i, (int)sl, (uint32_t)t, 1u, 0.f);
-          in.awakeSent = true;
-        }
-        const int start = startOffset + (int)t * MLGPU_FLOATS_PER_DSPVECTOR, end = start + MLGPU_FLOATS_PER_DSPVECTOR;
-        for (const mlgpu_event& evt : in.events)
-          if (evt.time >= start && evt.time < end)
-          {
-            mlgpu_event local = evt;
-            local.time -= start;
-            r.process(local);
-          }
-      }
-    }
-    const size_t lanes = ev->lanes();
+    router.route(nVectors, startOffset);  // (before the wait below: block k + 1 is routed while block k runs)
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     mlgpu_events::Staging& sg = ev->stage[ev->stageIdx];
     sgOut = &sg;
     ev->stageIdx ^= 1;
     if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
     sg.pending = false;
-    size_t nRecs = 0;
-    for (uint32_t l : ev->dirtyLanes) nRecs += ev->laneRecs[l].size();
-    if (nRecs + 1 > sg.recCapacity)
-    {
-      sg.recCapacity = std::max<size_t>(4096, 2 * (nRecs + 1));
-      if (allocate(sg.d_recs, sg.recCapacity) != hipSuccess || allocate(sg.h_recs, sg.recCapacity) != hipSuccess)
-      {
-        sg.recCapacity = 0;
-        return efail(ev, MLGPU_ERR_OOM, "events_process: record buffer");
-      }
-    }
-    const size_t nDirty = ev->dirtyLanes.size();
-    if (nDirty > sg.dirtyCapacity)
-    {
-      sg.dirtyCapacity = std::max<size_t>(1024, 2 * nDirty);
-      if (allocate(sg.d_dirty, sg.dirtyCapacity) != hipSuccess || allocate(sg.h_dirty, sg.dirtyCapacity) != hipSuccess)
-      {
-        sg.dirtyCapacity = 0;
-        return efail(ev, MLGPU_ERR_OOM, "events_process: lane list");
-      }
-    }
-    std::sort(ev->dirtyLanes.begin(), ev->dirtyLanes.end());
-    {
-      size_t n = 0, i = 0;
-      for (uint32_t l : ev->dirtyLanes)
-      {
-        const std::vector<Rec>& lr = ev->laneRecs[l];
-        memcpy(sg.h_recs.get() + n, lr.data(), sizeof(Rec) * lr.size());
-        sg.h_dirty[i++] = make_uint4(l, (uint32_t)n, (uint32_t)(n + lr.size()), 0u);
-        n += lr.size();
-      }
-    }
+    const size_t nRecs = router.recordCount(), nDirty = router.dirtyLaneCount();
+    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, 4096)) return efail(ev, MLGPU_ERR_OOM, "events_process: record buffer");
+    if (!growPair(sg.h_dirty, sg.d_dirty, sg.dirtyCapacity, nDirty, 1024)) return efail(ev, MLGPU_ERR_OOM, "events_process: lane list");
+    router.pack(sg.h_recs.get(), sg.h_dirty.get());
     hipError_t cerr = hipSuccess;
-    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(uint4) * nDirty, hipMemcpyHostToDevice, e->stream);
+    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(LaneRange) * nDirty, hipMemcpyHostToDevice, e->stream);
     if (cerr == hipSuccess && nRecs) cerr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(Rec) * nRecs, hipMemcpyHostToDevice, e->stream);
     if (cerr == hipSuccess && nDirty)
     {
@@ -1561,36 +1198,19 @@ extern "C"
     }
     if (cerr != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process upload: ") + hipGetErrorString(cerr));
 
-    const int cst = ev->watched.empty() ? MLGPU_OK : processControllers(ev, nVectors, ev->stageIdx ^ 1);
+    dev.s = deviceSettings(ev);
+    const int cst = router.watched().empty() ? MLGPU_OK : processControllers(ev, nVectors, ev->stageIdx ^ 1, dev.s);
     if (cst != MLGPU_OK)
     {
       abandonRanges(ev, sg);
       return cst;
     }
-
-    memset(&dev.s, 0, sizeof(dev.s));
-    dev.s.sr = ev->sr;
-    dev.s.pitchBendRange = ev->pitchBendRange;
-    dev.s.mpePitchBendRange = ev->mpePitchBendRange;
-    dev.s.driftAmount = ev->driftAmount;
-    dev.s.pitchGlideSamples = (int32_t)(ev->sr * ev->pitchGlideSeconds);  // :90
-    float c[2];
-    mlgpu_linear_glide_make_coeffs((float)(ev->sr * 0.02f), c);          // kGlideTimeSeconds / kControllerGlideTimeSeconds
-    memcpy(&dev.s.glideVectors, &c[0], 4);
-    dev.s.glideDy = c[1];
-    mlgpu_linear_glide_make_coeffs((float)(ev->sr * 8.0f), c);           // kDriftTimeSeconds
-    memcpy(&dev.s.driftGlideVectors, &c[0], 4);
-    dev.s.driftGlideDy = c[1];
-    mlgpu_linear_glide_make_coeffs((float)(int)(ev->sr * 0.02f), c);    // SmoothedController: int glideTimeInSamples = sr * 0.02f
-    memcpy(&dev.s.ctlGlideVectors, &c[0], 4);
-    dev.s.ctlGlideDy = c[1];
-    dev.s.mpe = ev->mpe ? 1 : 0;
     dev.ctl = nullptr;
     dev.rowP = dev.rowG = nullptr;
     dev.state = ev->d_state.get();
     dev.recs = sg.d_recs.get();
     dev.recRange = ev->d_recRange.get();
-    dev.lanes = lanes;
+    dev.lanes = router.lanes();
     return MLGPU_OK;
   }
   static int launched(mlgpu_events* ev, mlgpu_events::Staging& sg)
@@ -1623,22 +1243,14 @@ extern "C"
     mlgpu_events::Staging* sg = nullptr;
     const int pst = prepare(ev, nVectors, startOffset, dev, sg);
     if (pst != MLGPU_OK) return pst;
-    E2SArgs a;
-    memset(&a, 0, sizeof(a));
-    a.state = dev.state;
-    a.recs = (const Rec*)dev.recs;
-    a.recRange = dev.recRange;
+    E2SArgs a = kernelArgs<E2SArgs>(dev, nVectors, e->kflags);
     const size_t lanes = dev.lanes;
-    const size_t V = ev->nInstruments * (size_t)ev->polyphony;
+    const size_t V = mlgpu_events_num_voices(ev);
     for (int r = 0; r < 8; ++r) a.out[r] = makeView(d_outputs[r], layout, V, nVectors);
-    a.lanes = lanes;
-    a.T = nVectors;
     a.rowMask = ev->rowMask;
-    a.flags = e->kflags;
-    a.group = ev->group;
-    a.slotBase = ev->slotBase;
-    a.polyphony = ev->polyphony;
-    a.s = dev.s;
+    a.group = ev->router.group();
+    a.slotBase = ev->router.slotBase();
+    a.polyphony = ev->router.polyphony();
     if ((a.rowMask & ~3u) == 0)
       hipLaunchKernelGGL(e2s_kernel<true>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
     else
@@ -1656,7 +1268,7 @@ extern "C"
   static int reserveCtlRecs(mlgpu_events* ev, size_t nVectors)
   {
     mlgpu_engine* e = ev->e;
-    const size_t lanes = ev->lanes();
+    const size_t lanes = ev->router.lanes();
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     hipStreamSynchronize(e->stream);
     // recorded graph launches have these pointers baked in: the old buffers are retired, the new ones serve from now on
@@ -1679,7 +1291,7 @@ extern "C"
   {
     if (!ev || maxVectors == 0) return MLGPU_ERR_INVALID;
     if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_reserve_for_graph allocates: not while recording a sequence");
-    if (ev->mpe) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
+    if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
     if (maxVectors != ev->ctlRecVectors)
     {
       const int st = reserveCtlRecs(ev, maxVectors);
@@ -1691,7 +1303,7 @@ extern "C"
   size_t mlgpu_events_graph_reserve_bytes(mlgpu_events* ev, size_t maxVectors)
   {
     if (!ev) return 0;
-    return (sizeof(uint32_t) * kCtlRecWords + 2 * sizeof(float) * 64) * maxVectors * ev->lanes();
+    return (sizeof(uint32_t) * kCtlRecWords + 2 * sizeof(float) * 64) * maxVectors * ev->router.lanes();
   }
 
   // for graph.hip: a graph whose event rows are bound to this object (mlgpu_graph_bind_events)
@@ -1701,9 +1313,9 @@ extern "C"
     if (nVectors == 0) return MLGPU_OK;
     if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events route on the host: not while recording a sequence");
     if (ev->sr == 0) return efail(ev, MLGPU_ERR_INVALID, "events: no sample rate (the reference does nothing, :385)");
-    if (ev->mpe) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
+    if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
     mlgpu_engine* e = ev->e;
-    const size_t lanes = ev->lanes();
+    const size_t lanes = ev->router.lanes();
     // the control records and the two side signals of e2s_ctl_kernel: sized by mlgpu_events_reserve_for_graph at setup. An object that
     // was never reserved grows them here on the first / a longer block (a setup-time convenience: it waits for the stream and allocates);
     // once a host has reserved, a longer block is refused before the router consumes its events and nothing is ever allocated here.
@@ -1718,18 +1330,10 @@ extern "C"
     const int st = prepare(ev, nVectors, startOffset, *dev, sg);
     *staging = sg;
     if (st != MLGPU_OK) return st;
-    E2SCtlArgs a;
-    memset(&a, 0, sizeof(a));
-    a.state = dev->state;
-    a.recs = (const Rec*)dev->recs;
-    a.recRange = dev->recRange;
+    E2SCtlArgs a = kernelArgs<E2SCtlArgs>(*dev, nVectors, e->kflags);
     a.ctl = ev->d_ctlRecs.get();
     a.rowP = (float4*)ev->d_rowP.get();
     a.rowG = (float4*)ev->d_rowG.get();
-    a.lanes = lanes;
-    a.T = nVectors;
-    a.flags = e->kflags;
-    a.s = dev->s;
     hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
@@ -1769,7 +1373,7 @@ extern "C"
     }
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     hipStreamSynchronize(e->stream);
-    if (n > 0 && ev->watched == std::vector<int>(numbers, numbers + n))  // the same controllers: only the reserved length changes
+    if (n > 0 && ev->router.watched() == std::vector<int>(numbers, numbers + n))  // the same controllers: only the reserved length changes
     {
       if (maxVectors <= ev->ctlCapacityVectors)  // the signals' pointers (mlgpu_events_controller_signal) are only ever replaced to grow
       {
@@ -1779,8 +1383,8 @@ extern "C"
       if (e->liveSequences > 0)
         return efail(ev, MLGPU_ERR_INVALID, "events_watch_controllers would move the controller signals that recorded sequences of this engine may read: destroy them first");
       DeviceBuffer<float> fresh;
-      if (allocate(fresh, 64 * maxVectors * ev->ctlLanes()) != hipSuccess) return efail(ev, MLGPU_ERR_OOM, "events_watch_controllers: controller signals");
-      hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * ev->ctlLanes(), e->stream);
+      if (allocate(fresh, 64 * maxVectors * ev->router.ctlLanes()) != hipSuccess) return efail(ev, MLGPU_ERR_OOM, "events_watch_controllers: controller signals");
+      hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * ev->router.ctlLanes(), e->stream);
       ev->d_ctlOut = std::move(fresh);
       ev->ctlMaxVectors = ev->ctlCapacityVectors = maxVectors;
       return MLGPU_OK;
@@ -1789,11 +1393,9 @@ extern "C"
       return efail(ev, MLGPU_ERR_INVALID, "events_watch_controllers would free controller signals that recorded sequences of this engine may read: destroy them first");
     freeControllers(ev);
     if (n == 0) return MLGPU_OK;
-    ev->watched.assign(numbers, numbers + n);
-    for (int i = 0; i < n; ++i) ev->slotOf[numbers[i]] = i;
+    ev->router.watch(numbers, n);
     ev->ctlMaxVectors = ev->ctlCapacityVectors = maxVectors;
-    const size_t lanes = ev->ctlLanes();
-    ev->ctlLaneRecs.resize(lanes);
+    const size_t lanes = ev->router.ctlLanes();
     hipError_t err = allocate(ev->d_ctlOut, 64 * maxVectors * lanes);
     if (err == hipSuccess) err = allocate(ev->d_ctlState, (size_t)kCtlWords * lanes);
     for (mlgpu_events::CtlStaging& st : ev->ctlStage)
@@ -1807,32 +1409,15 @@ extern "C"
       freeControllers(ev);
       return efail(ev, err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP, std::string("events_watch_controllers: ") + hipGetErrorString(err));
     }
-    // A smoother that starts being watched now starts settled on its controller's current value (the reference's has been
-    // running all along: the same thing 20 ms after the controller last moved); an instrument that has not seen an event yet
-    // is asleep and gives zeros (:386).
-    std::vector<uint32_t> st((size_t)kCtlWords * lanes, 0u);
-    auto W = [&](int word, size_t lane) -> uint32_t& { return st[(size_t)word * lanes + lane]; };
-    for (int sl = 0; sl < n; ++sl)
-      for (size_t i = 0; i < ev->nInstruments; ++i)
-      {
-        const size_t lane = (size_t)sl * ev->nInstruments + i;
-        const float v = ev->inst[i].ctlInput.empty() ? 0.f : ev->inst[i].ctlInput[(size_t)numbers[sl]];
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        W(C_AWAKE, lane) = ev->inst[i].awakeSent ? 1u : 0u;
-        W(C_INPUT, lane) = bits;
-        W(C_GLIDE + 0, lane) = bits;         // target
-        W(C_GLIDE + 2, lane) = 0xFFFFFFFFu;  // remaining = -1: holding (MLDSPGens.h:441)
-        W(C_GLIDE + 3, lane) = 1u;           // mCurrVec is one value
-        W(C_GLIDE + 4, lane) = bits;
-      }
+    std::vector<uint32_t> st;
+    ev->router.initialControllerState(st);
     return mlgpu_upload(e, ev->d_ctlState.get(), st.data(), st.size() * sizeof(uint32_t));
   }
   const float* mlgpu_events_controller_signal(mlgpu_events* ev, int slot)
   {
-    if (!ev || slot < 0 || (size_t)slot >= ev->watched.size()) return nullptr;
-    return ev->d_ctlOut.get() + (size_t)slot * 64 * ev->ctlCapacityVectors * ev->nInstruments;
+    if (!ev || slot < 0 || (size_t)slot >= ev->router.watched().size()) return nullptr;
+    return ev->d_ctlOut.get() + (size_t)slot * 64 * ev->ctlCapacityVectors * ev->router.instruments();
   }
-  int mlgpu_events_is_midi(mlgpu_events* ev) { return (ev && !ev->mpe) ? 1 : 0; }
+  int mlgpu_events_is_midi(mlgpu_events* ev) { return (ev && !ev->router.mpe()) ? 1 : 0; }
   mlgpu_engine* mlgpu_events_engine(mlgpu_events* ev) { return ev ? ev->e : nullptr; }
 }

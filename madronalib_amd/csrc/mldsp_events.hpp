@@ -1,51 +1,17 @@
 // mldsp_events.hpp — the device side of EventsToSignals (source/app/MLEventsToSignals.{h,cpp}) shared by the events kernel
 // (events.hip: all 8 rows into HBM) and the run-time fused graph kernels (graph.hip: pitch and gate as source nodes of a voice
-// graph, never written to memory): the record format the host router produces, the per-voice state layout, LinearGlide with
-// its 64 slots, note_frame - one frame of a vector that holds note records - and CtlVoice: the control records of
+// graph, never written to memory): the kernels' arguments (the record format and the state layout are mlev_format.hpp), LinearGlide
+// with its 64 slots, note_frame - one frame of a vector that holds note records - and CtlVoice: the control records of
 // e2s_ctl_kernel expanded to the pitch and gate rows inside a voice kernel, one quad of frames at a time.
 #pragma once
 #include "mlgpu_device_args.hpp"
 #include "mldsp_math.hpp"
 #include "mldsp_procs.hpp"  // Proc<MLGPU_PROC_SAMPLE_ACCURATE_LINEAR_GLIDE>: the pitch glide
+#include "mlev_format.hpp"  // the records, the state words: what the host router shares with this file
 
 namespace mlev
 {
 using namespace mldev;
-
-// ---- records ------------------------------------------------------------------------------------------------------
-enum RecType : uint32_t
-{
-  REC_AWAKE = 0,      // the instrument received its first event: processVector stops being a no-op (:383-386)
-  REC_NOTE_ON = 1,    // writeNoteEvent kNoteOn (:129-152):   v1 pitch, v2 velocity, flags bit0 doGlide bit1 doReset
-  REC_NOTE_RETRIG = 2,
-  REC_NOTE_OFF = 3,
-  REC_SET_BEND = 4,   // currentPitchBend = v1 (:700-731)
-  REC_SET_MOD = 5,
-  REC_SET_X = 6,
-  REC_SET_Y = 7,
-  REC_SET_Z = 8,
-  REC_SET_CHANNEL_PRESSURE = 9  // controllers[128].inputValue (MIDI mode, :620-626)
-};
-struct Rec
-{
-  uint32_t vec;    // DSPVector index inside this launch
-  uint32_t typeTimeFlags;  // type | time << 8 | flags << 16
-  float v1, v2;
-};
-
-// ---- device state layout (uint32 words per voice, SoA [word][lanes]) --------------------------------------------------
-enum : int
-{
-  S_AWAKE = 0, S_VELOCITY, S_PITCH, S_BEND, S_MOD, S_X, S_Y, S_Z, S_CHANPRESS, S_AGE, S_AGE_STEP, S_INHIBIT_GLIDE,
-  S_PG_CURR, S_PG_STEP, S_PG_TARGET, S_PG_REMAINING, S_PG_PER_GLIDE, S_PG_DY,
-  S_DRIFT_SEED, S_DRIFT_COUNTER, S_DRIFT_VALUE, S_DRIFT_NEXT,
-  S_RECALC,  // Voice::recalcNeeded (:45-54): set by setSampleRate / setPitchGlideInSeconds, consumed by the next beginProcess
-  S_GLIDES  // 7 glides follow: bend, mod, x, y, z, drift, channel pressure
-};
-constexpr int kNumGlides = 7;
-constexpr int kGlideWords = 5 + 64;  // target, step, remaining, isUniform, uniformValue, currVec[64]
-constexpr int kStateWords = S_GLIDES + kNumGlides * kGlideWords;
-
 
 struct E2SArgs
 {
@@ -332,9 +298,6 @@ MLD void note_frame(const Rec* recs, RecCache& cache, uint32_t& nc, uint32_t ven
     if (wantTime) vTime = (float)((double)age / srD);
   }
 }
-
-// flags of a note record (typeTimeFlags >> 16): bit 0 doGlide, bit 1 doReset, bit 2 REC_FLAG_REWIND
-constexpr uint32_t REC_FLAG_REWIND = 4u;
 
 // A vector that holds a note record flagged REC_FLAG_REWIND: a record on frame 0 for a voice whose earlier note records of the same
 // vector ended later than that. Events reach the reference sorted by time, so only an event it makes up itself can be such a record: the

@@ -1,5 +1,5 @@
 // tests/cpp/sanitize_host_test.cpp — the pure-host parts of the library (the DSPBuffer ring of dspbuffer.cpp, the
-// coefficient makers of coeffs.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, and the ring's single-producer /
+// coefficient makers of coeffs.cpp, the event router of events_router.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, and the ring's single-producer /
 // single-consumer contract under ThreadSanitizer (tests/test_host_cpp.py builds it three ways with g++ and runs it; no
 // GPU involved). Random operation sequences against a trivially correct model: a std::deque of floats.
 #include <atomic>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mlgpu.h"
+#include "../../madronalib_amd/csrc/events_router.hpp"
 
 static int failures = 0;
 #define REQUIRE(cond)                                                 \
@@ -143,6 +144,78 @@ static void coefficientMakers()
   }
 }
 
+
+// The event router (voice allocation and stealing, unison, pedal, MIDI / MPE channel rules) driven by random performances with
+// hostile event fields; every launch is packed into heap buffers of exactly the sizes the router announced. Only the absence of
+// sanitizer reports is asserted (what the records must be: tests/cpp/events_router_test.cpp).
+static void routerPerformance(unsigned seed)
+{
+  std::mt19937 rng(seed);
+  auto upTo = [&](unsigned n) { return (int)(rng() % n); };
+  const size_t nInst = 1 + (size_t)upTo(3);
+  mlev::EventRouter r(nInst, 1 + upTo(16));
+  if (upTo(3) == 0)
+  {
+    r.setProtocol(true);
+    r.clear();
+  }
+  r.setUnison(upTo(4) == 0);
+  r.setModCC(upTo(2) ? 16 : upTo(140));
+  const int times[] = {-2147483647 - 1, -100000, -65, -1, 2147483647, 2147483000, 100000};
+  const int numbers[] = {0, 1, 7, 16, 73, 74, 120, 123, 127, 128, 129, 300, 65535};
+  for (int block = 0; block < 12; ++block)
+  {
+    if (upTo(6) == 0)
+    {
+      int watch[4];
+      const int n = upTo(5);
+      for (int i = 0; i < n; ++i) watch[i] = (i == 0 && upTo(3) == 0) ? 128 : upTo(30) + 32 * i;  // (no number twice)
+      if (n) r.watch(watch, n);
+      else r.unwatch();
+    }
+    if (upTo(15) == 0) r.clear();
+    if (upTo(25) == 0)
+    {
+      r.setProtocol(upTo(2) != 0);
+      r.clear();
+    }
+    const size_t nVectors = 1 + (size_t)upTo(8);
+    const int frames = (int)nVectors * 64;
+    for (int i = upTo(40); i > 0; --i)
+    {
+      mlgpu_event e{};
+      const int kind = upTo(10);
+      e.type = (uint8_t)(kind < 3 ? MLGPU_EVENT_NOTE_ON : kind < 5 ? MLGPU_EVENT_NOTE_OFF : kind == 5 ? MLGPU_EVENT_SUSTAIN_PEDAL : kind == 6 ? MLGPU_EVENT_CONTROLLER : upTo(256));
+      e.channel = (uint8_t)(upTo(4) ? upTo(18) : upTo(256));
+      e.source_idx = (uint16_t)(e.type == MLGPU_EVENT_CONTROLLER ? numbers[upTo(13)] : upTo(5) ? 30 + upTo(60) : upTo(65536));
+      e.time = upTo(8) ? upTo(frames) : times[upTo(7)];
+      e.value1 = upTo(3) ? (float)upTo(1000) * 0.001f : (float)(upTo(3) - 1) * 1e30f;
+      e.value2 = (float)upTo(1000) * 0.001f;
+      r.addEvent((size_t)upTo((unsigned)nInst), e);
+    }
+    size_t done = 0;
+    while (done < nVectors)  // a block may be routed in several launches
+    {
+      const size_t n = 1 + (size_t)upTo((unsigned)(nVectors - done));
+      r.route(n, (int)done * 64);
+      std::vector<mlev::Rec> recs(r.recordCount());
+      std::vector<mlev::LaneRange> lanes(r.dirtyLaneCount());
+      r.pack(recs.data(), lanes.data());
+      REQUIRE(lanes.empty() ? recs.empty() : (lanes.back().last == recs.size() && lanes.back().lane < r.lanes()));
+      std::vector<mlev::CtlRec> ctl(r.ctlRecordCount());
+      std::vector<uint32_t> start(r.ctlLanes() + 1);
+      r.packControllers(ctl.data(), start.data());
+      REQUIRE(start.back() == ctl.size());
+      for (size_t i = 0; i < nInst; ++i) REQUIRE(r.newestVoice(i) <= r.polyphony());
+      done += n;
+    }
+    r.clearEvents();
+  }
+  std::vector<uint32_t> st;
+  r.initialVoiceState(st);
+  r.initialControllerState(st);
+}
+
 int main(int argc, char** argv)
 {
   const bool threadsOnly = argc > 1 && !strcmp(argv[1], "threads");
@@ -150,6 +223,7 @@ int main(int argc, char** argv)
   {
     for (unsigned s = 1; s <= 12; ++s) ringAgainstModel(s);
     coefficientMakers();
+    for (unsigned s = 1; s <= 200; ++s) routerPerformance(s);
   }
   ringTwoThreads();
   if (failures == 0) printf("All tests passed\n");

@@ -57,14 +57,14 @@ def test_multi_engine_program_passes():
 
 @pytest.mark.parametrize("sanitizer,mode", [("address,undefined", ""), ("thread", "threads")])
 def test_host_code_under_sanitizers(sanitizer, mode, tmp_path):
-    """SURVEY §5 (sanitizer builds): the pure-host translation units (the DSPBuffer ring, the coefficient makers) built with
+    """SURVEY §5 (sanitizer builds): the pure-host translation units (the DSPBuffer ring, the coefficient makers, the event router) built with
     g++ -fsanitize=address,undefined and -fsanitize=thread and driven by random operation sequences and a two-thread
     producer / consumer run (tests/cpp/sanitize_host_test.cpp). Any report aborts the program."""
     if not os.path.exists("/usr/bin/g++"):
         pytest.skip("no g++")
     exe = str(tmp_path / "sanitize_host_test")
     src = [os.path.join(ROOT, "tests", "cpp", "sanitize_host_test.cpp"), os.path.join(ROOT, "madronalib_amd", "csrc", "dspbuffer.cpp"),
-           os.path.join(ROOT, "madronalib_amd", "csrc", "coeffs.cpp")]
+           os.path.join(ROOT, "madronalib_amd", "csrc", "coeffs.cpp"), os.path.join(ROOT, "madronalib_amd", "csrc", "events_router.cpp")]
     cmd = ["g++", "-std=c++17", "-O1", "-g", f"-fsanitize={sanitizer}", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
            "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include")] + src + ["-o", exe, "-pthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -73,6 +73,22 @@ def test_host_code_under_sanitizers(sanitizer, mode, tmp_path):
     assert b.returncode == 0, b.stderr[-2000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=1")
     r = subprocess.run([exe] + ([mode] if mode else []), capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "All tests passed" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def test_event_router_routes_on_the_cpu(tmp_path):
+    """The host half of EventsToSignals (madronalib_amd/csrc/events_router.cpp: voice allocation and stealing, unison, the sustain
+    pedal, MIDI / MPE channel rules, watched controllers, initial states) is plain C++: built by g++ from that one file with no HIP
+    include path, and its packed records for tiny performances are the hand-written lists of tests/cpp/events_router_test.cpp."""
+    if not os.path.exists("/usr/bin/g++"):
+        pytest.skip("no g++")
+    exe = str(tmp_path / "events_router_test")
+    b = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", os.path.join(ROOT, "tests", "cpp", "events_router_test.cpp"),
+                        os.path.join(ROOT, "madronalib_amd", "csrc", "events_router.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-3000:]
+    used = subprocess.run(["g++", "-std=c++17", "-M", os.path.join(ROOT, "madronalib_amd", "csrc", "events_router.cpp")], capture_output=True, text=True, timeout=300).stdout
+    assert "hip/" not in used and "hip_runtime" not in used and "mlev_format.hpp" in used
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "All tests passed" in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 
