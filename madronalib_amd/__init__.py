@@ -803,9 +803,10 @@ class Resampler(_Handle):
         self.engine._check(self.L.mlgpu_resampler_process(self.h, int(n_vectors_in), ctypes.c_void_p(d_in.ptr), int(in_layout),
                                                          ctypes.c_void_p(d_out.ptr), int(out_layout)))
 
-    def process_host(self, x, layout=Layout.QUAD):
-        """x [V][64*Tin] numpy -> [V][64*Tout] numpy (conversion to / from `layout` on the device)."""
+    def process_host(self, x, layout=Layout.QUAD, out_layout=None):
+        """x [V][64*Tin] numpy -> [V][64*Tout] numpy (conversion to `layout` and from `out_layout`, by default the same, on the device)."""
         eng, V = self.engine, self.V
+        out_layout = layout if out_layout is None else out_layout
         x = np.ascontiguousarray(x, np.float32)
         Tin = x.shape[1] // 64
         Tout = Tin << self.octaves if self.up else Tin >> self.octaves
@@ -814,11 +815,11 @@ class Resampler(_Handle):
         if layout != Layout.VOICE_MAJOR:
             d_in = eng.alloc(x.nbytes)
             eng.layout_convert(d_vm, Layout.VOICE_MAJOR, d_in, layout, V, Tin)
-        self.process(Tin, d_in, d_out, layout, layout)
+        self.process(Tin, d_in, d_out, layout, out_layout)
         res = d_out
-        if layout != Layout.VOICE_MAJOR:
+        if out_layout != Layout.VOICE_MAJOR:
             res = eng.alloc(4 * V * 64 * Tout)
-            eng.layout_convert(d_out, layout, res, Layout.VOICE_MAJOR, V, Tout)
+            eng.layout_convert(d_out, out_layout, res, Layout.VOICE_MAJOR, V, Tout)
         return res.download(np.float32, V * 64 * Tout).reshape(V, 64 * Tout)
 
 

@@ -327,6 +327,31 @@ def delay_case(mk, name, V, T, seed=0):
     raise KeyError(name)
 
 
+def long_ring_case(mk, kind_name, V, T, max_delay, write_index, seed=0, write_index2=None):
+    """delay_case's "integer_var", "frac_var" or "pitchbend" (the same inputs: the delay-time signal stays within 0 .. 192 samples, so
+    every read lands on a row the run itself wrote, or on one it has not reached yet and both sides hold as zero) on a ring sized by
+    max_delay, with state word 0 - the write index - given per voice (a scalar or [V]). A PitchbendableDelay's second ring (word 5)
+    gets write_index2, by default the same index: the two rings in step, as the reference class keeps them."""
+    assert kind_name in ("integer_var", "frac_var", "pitchbend")
+    c = delay_case(mk, kind_name, V, T, seed)
+    c["max_delay"] = float(max_delay)
+    c["state0"][0] = np.broadcast_to(np.asarray(write_index, np.uint32), (V,))
+    if kind_name == "pitchbend":
+        c["state0"][5] = np.broadcast_to(np.asarray(write_index if write_index2 is None else write_index2, np.uint32), (V,))
+    return c
+
+
+def sparse_zeros(shape):
+    """A zeroed float32 array of which only the touched 4 KiB pages become resident (anonymous memory without transparent huge
+    pages): the oracle's [V][rings][len] ring memory for rings of megabytes, of which a run touches a few hundred samples each."""
+    import mmap
+    n = int(np.prod(shape)) * 4
+    mm = mmap.mmap(-1, n)
+    if hasattr(mmap, "MADV_NOHUGEPAGE"):
+        mm.madvise(mmap.MADV_NOHUGEPAGE)
+    return np.frombuffer(mm, np.float32).reshape(shape)
+
+
 def region_case(V, T, seed=0):
     """Inputs of the rate-region cases (Upsample2xFunction / Downsample2xFunction around one stateful fn): noise x, a slow
     modulator m, per-voice oscillator frequency, Lopass coefficients (omega 0.2, k 0.8 from the caller's makeCoeffs)."""

@@ -474,3 +474,152 @@ def test_ring_layouts_random_chains(eng):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     assert mod.run(14, 31, eng) == 0
+
+
+# ---- bank and ring sizes at which the ring addressing changes form ---------------------------------------------------------
+# 2374 voices = 9 * 256 + 70: a grid of 10 workgroups, 8 of them behind the XCD remap and 2 after it, a last wavefront of 6 voices.
+RAGGED_V = 9 * 256 + 70
+LONG_KINDS = ("integer_var", "frac_var", "pitchbend")
+
+
+def _oracle_two_launches(oracle, c, V, T):
+    """The oracle's outputs and state words after each of two launches of T vectors, on ring memory of the case's true length (freed on
+    return). At least half of the second launch's samples must be non-zero, so that no comparison passes on silence."""
+    from graph_oracle import ring_len
+    from inputs import sparse_zeros
+    rings = 2 if c["kind"] == Proc.PITCHBENDABLE_DELAY else 1
+    st, mem = c["state0"].copy(), sparse_zeros((V, rings, ring_len(c["max_delay"])))
+    wants, states = [], []
+    for call in range(2):
+        sl = slice(call * 64 * T, (call + 1) * 64 * T)
+        wants.append(oracle.delay_process(c["kind"], T, st, mem, [np.ascontiguousarray(a[:, sl]) for a in c["inputs"]]))
+        states.append(st.copy())
+    del mem
+    assert 2 * np.count_nonzero(wants[1]) >= wants[1].size, "the oracle's second launch is mostly silence"
+    return wants, states
+
+
+def _assert_delay_run(g, names, c, T, wants, states, what):
+    outs, gst = run_delay(g, names, c["state0"], c["inputs"], T, Layout.QUAD)
+    for call in range(2):
+        assert_bits_equal(outs[call], wants[call], True, f"{what} call {call}")
+        assert_bits_equal(gst[call], states[call], False, f"{what} state after call {call}")
+
+
+def _written_byte_offsets(c, V, L, samples):
+    """Ring layout 0: the byte offsets, from the ring's start, of the rows a run of `samples` samples writes - row i of voice v lies
+    at 4 V i + 4 v. [V][samples], int64."""
+    pos = (c["state0"][0].astype(np.int64)[:, None] + np.arange(samples, dtype=np.int64)[None, :]) % L
+    return pos * (4 * V) + 4 * np.arange(V, dtype=np.int64)[:, None]
+
+
+def _rows32(g):
+    """Whether the generated kernel addresses its ring rows through 32-bit offsets (VoiceMem's addr32 initialiser ends `, true}`)."""
+    return ", true}" in g.source
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("windows", WINDOWS)
+@pytest.mark.parametrize("name", LONG_KINDS)
+def test_delay_lines_ragged_many_workgroups(eng, oracle, name, windows):
+    """Every ring layout at 2374 voices - ten workgroups, eight behind the XCD remap and two after it, a last wavefront of six voices
+    (the transposed layout's spare lanes, the windowed layouts' padding to 2560 voices) - at the ring length of the 300-voice cases:
+    outputs and every state word after each of two launches against the oracle, then clear() and a vector of silence."""
+    from inputs import long_ring_case
+    V, T = RAGGED_V, 3
+    c = long_ring_case(oracle, name, V, 2 * T, 192.0, 0, seed=8)
+    wants, states = _oracle_two_launches(oracle, c, V, T)
+    g, names = delay_graph(eng, V, c["kind"], len(c["inputs"]), c["max_delay"], windows)
+    try:
+        _assert_delay_run(g, names, c, T, wants, states, f"{name}, {V} voices")
+        g.clear()
+        (y,) = g.process_host(1, {nm: np.zeros((V, 64), np.float32) for nm in names} | {names[1]: np.full((V, 64), 70.0, np.float32)}, Layout.QUAD)
+        assert (y == 0).all()
+    finally:
+        g.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", LONG_KINDS)
+def test_row_offsets_above_2_31(eng, oracle, monkeypatch, name):
+    """Ring layout 0 with rows behind 32-bit offsets (VoiceMem::ringPtr) in the upper half of their range: 2040 voices on rings of 2^19
+    samples, 4 278 190 080 bytes a ring. A third of the voices writes through the ring's end (offsets up to 2^32 - 8160 + 4 v), a third
+    through row 263 172, whose bytes straddle 2^31, a third anywhere. Against the oracle on rings of the true length, and the same
+    graph with the 64-bit rows (MLGPU_GRAPH_ROW_ADDR32=0); which form each kernel has is read from its source."""
+    from graph_oracle import ring_len
+    from inputs import long_ring_case
+    V, T, max_delay = 2040, 3, 500000.0
+    L = ring_len(max_delay)
+    assert L == 1 << 19 and 4 * V * L <= 1 << 32
+    rng = np.random.default_rng(19)
+    w = np.concatenate([np.full(680, L - 100), np.full(680, 263172 - 100), rng.integers(0, L, V - 1360)]).astype(np.uint32)
+    c = long_ring_case(oracle, name, V, 2 * T, max_delay, w, seed=12)
+    offs = _written_byte_offsets(c, V, L, 2 * 64 * T)
+    assert offs.max() >= 1 << 31 and offs.max() < 1 << 32
+    assert offs[:680].max() == 4 * V * (L - 1) + 4 * 679 and offs[:680].min() < 4 * V * 100      # through the ring's end
+    assert offs[680:1360].min() < 1 << 31 <= offs[680:1360].max()                                # across 2^31
+    wants, states = _oracle_two_launches(oracle, c, V, T)
+    for hook, want32 in ((None, True), ("0", False)):
+        if hook is not None:
+            monkeypatch.setenv("MLGPU_GRAPH_ROW_ADDR32", hook)
+        g, names = delay_graph(eng, V, c["kind"], len(c["inputs"]), max_delay, 0)
+        try:
+            assert _rows32(g) == want32, hook
+            _assert_delay_run(g, names, c, T, wants, states, f"{name}, rows32={want32}")
+        finally:
+            g.close()
+
+
+# (voices, max_delay, ring length): a ring of exactly 4 GiB; just above 4 GiB; a ring of 2^24 rows, one more than __umul24 takes
+GUARD_EDGES = [pytest.param(128, 8388544.0, 1 << 23, id="4GiB"), pytest.param(2100, 500000.0, 1 << 19, id="above4GiB"),
+               pytest.param(64, 16777152.0, 1 << 24, id="ring2^24")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,max_delay,L", GUARD_EDGES)
+@pytest.mark.parametrize("name", ["integer_var", "pitchbend"])
+def test_row_address_guards_at_their_edges(eng, oracle, name, V, max_delay, L):
+    """The three conditions under which the generated kernel takes the 32-bit row form - ring bytes over the bank <= 2^32, ring length
+    < 2^24, voices < 2^22 - each case on one side of one of them, the write index 100 samples under the ring's end so that the run
+    writes the ring's last row (the 4 GiB ring: byte offset 2^32 - 4) and wraps. The PitchbendableDelay's second ring, a whole ring
+    above the first, gets a write index of its own (8 further), which keeps the two rings apart in the kernel."""
+    from graph_oracle import ring_len
+    from inputs import long_ring_case
+    T = 3
+    assert ring_len(max_delay) == L
+    want32 = 4 * V * L <= 1 << 32 and L < 1 << 24 and V < 1 << 22
+    assert want32 == (L == 1 << 23)
+    c = long_ring_case(oracle, name, V, 2 * T, max_delay, L - 100, seed=5, write_index2=(L - 100 + 8) & (L - 1))
+    offs = _written_byte_offsets(c, V, L, 2 * 64 * T)
+    assert offs.max() == 4 * V * L - 4 and offs.min() == 0
+    if L == 1 << 23:
+        assert offs.max() == (1 << 32) - 4
+    wants, states = _oracle_two_launches(oracle, c, V, T)
+    g, names = delay_graph(eng, V, c["kind"], len(c["inputs"]), max_delay, 0)
+    try:
+        assert _rows32(g) == want32
+        _assert_delay_run(g, names, c, T, wants, states, f"{name}, {V} voices, ring {L}")
+    finally:
+        g.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_delay,L", [(500000.0, 1 << 19), (4194240.0, 1 << 22)])
+@pytest.mark.parametrize("windows", [w for w in WINDOWS if w.values[0]])
+@pytest.mark.parametrize("name", ["integer_var", "pitchbend"])
+def test_windowed_layouts_long_rings(eng, oracle, name, windows, max_delay, L):
+    """The three windowed layouts ([256-voice block][sample / 8][lane][8] and its transposed form) on rings of 2^19 and 2^22 samples:
+    a block's ring takes 512 MiB to 8 GiB, a PitchbendableDelay's second ring starts that far above the first. 300 voices (a second,
+    ragged block), every write index 128 samples under the ring's end - a multiple of 16, which keeps the layouts' fast forms - so that
+    the first launch runs through the ring's last chunk and wraps. No layout refuses these lengths: compile() succeeds for all."""
+    from graph_oracle import ring_len
+    from inputs import long_ring_case
+    V, T = 300, 3
+    assert ring_len(max_delay) == L
+    c = long_ring_case(oracle, name, V, 2 * T, max_delay, L - 128, seed=21)
+    wants, states = _oracle_two_launches(oracle, c, V, T)
+    g, names = delay_graph(eng, V, c["kind"], len(c["inputs"]), max_delay, windows)
+    try:
+        _assert_delay_run(g, names, c, T, wants, states, f"{name}, ring {L}")
+    finally:
+        g.close()

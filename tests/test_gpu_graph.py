@@ -83,6 +83,32 @@ def test_synth16_vs_oracle(eng, oracle, layout, vpl):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("V,vpl", [(9 * 256 + 70, 1), (9 * 512 + 70, 2)])
+def test_synth16_many_workgroups(eng, oracle, V, vpl):
+    """The generated graph kernel on a grid of ten workgroups - eight behind the XCD-aware workgroup -> voice remap, two tail blocks, the
+    last one with 70 voices (a block holds 256 voices, or 512 with two voices per lane): every voice of two launches, and every state
+    word, against the graph oracle."""
+    T = 3
+    params, coeffs = synth16_setup(oracle, V, seed=6)
+    seeds = np.arange(V, dtype=np.uint32) * np.uint32(2654435761)
+    g, desc, outs, states = build_synth16(eng, oracle, V, params, coeffs, seeds, vpl)
+    assert f"({vpl} voice" in g.source
+    gate = gate_signal(V, 64 * T * 2, seed=10)
+    gate[:, :40] = np.float32(0.8)     # (every voice sounds from the first launch on)
+    for call in range(2):
+        sig = {"gate": np.ascontiguousarray(gate[:, call * 64 * T:(call + 1) * 64 * T])}
+        (got,) = g.process_host(T, sig, Layout.QUAD)
+        (want,) = evaluate(oracle, desc, outs, V, T, sig, params, coeffs, states)
+        assert_bits_equal(got, want, True, f"synth16, {V} voices, call {call}")
+    for n in desc:
+        if n["type"] == "proc":
+            for i in range(g.num_state(n["name"])):
+                assert (g.get_state(n["name"], i) == states[n["name"]][i]).all(), (n["name"], i)
+    assert 2 * np.count_nonzero(want) >= want.size
+    g.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("vpl", [1, 2])
 def test_synth16full_golden_and_oracle(eng, oracle, vpl):
     """patches.synth16(full=True) = config 5 as SURVEY 8d lists it: Lopass(x, omega, k) with per-sample coefficients (device

@@ -220,7 +220,8 @@ def test_mixdown_groups_voice_order(eng, P, groups, layout):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("V,T", [(64, 1), (64 * 5, 3), (4096 + 64, 2), (65536 + 4096 + 192, 1),   # 1 / 5 / 65 / 1091 groups: one to three row passes
-                                 (1, 2), (100, 1), (4097, 3), (262144 + 77, 1)])                    # a last wavefront that is not full: its missing voices count as +0
+                                 (1, 2), (100, 1), (4097, 3), (262144 + 77, 1),                     # a last wavefront that is not full: its missing voices count as +0
+                                 (2374, 2)])                                                        # ... in a tail workgroup after the remapped eight
 @pytest.mark.parametrize("chain,signal", [((Proc.SAW_GEN, Proc.BANDPASS, Proc.GAIN), False), ((Proc.SAW_GEN, Proc.BANDPASS, Proc.GAIN), True),
                                           ((Proc.SINE_GEN, Proc.GAIN), False), ((Proc.PULSE_GEN, Proc.HIPASS, Proc.ONE_POLE), True)])
 def test_bank_process_mixdown_same_bits(eng, oracle, V, T, chain, signal):

@@ -20,7 +20,7 @@ def eng():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("octaves", [0, 1, 2, 3, 6])
+@pytest.mark.parametrize("octaves", [0, 1, 2, 3, 4, 5, 6])
 @pytest.mark.parametrize("up", [False, True])
 @pytest.mark.parametrize("layout", [Layout.QUAD, Layout.VOICE_MAJOR])
 def test_resampler_vs_oracle(eng, oracle, octaves, up, layout):
@@ -36,6 +36,26 @@ def test_resampler_vs_oracle(eng, oracle, octaves, up, layout):
         assert_bits_equal(r.get_state(), st, True, "HalfBandFilter state")
     r.clear()
     assert (r.get_state() == 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("octaves", [1, 3])
+@pytest.mark.parametrize("up", [False, True])
+@pytest.mark.parametrize("layout,out_layout", [(Layout.QUAD, Layout.ROWS), (Layout.VOICE_MAJOR, Layout.QUAD), (Layout.ROWS, Layout.VOICE_MAJOR)])
+def test_resampler_many_workgroups_mixed_layouts(eng, oracle, octaves, up, layout, out_layout):
+    """2374 voices - ten workgroups, eight behind the XCD remap and two after it, a last wavefront of six voices - reading one signal
+    layout and writing another: outputs and the filter state over two calls."""
+    import madronalib_amd as ml
+    V = 9 * 256 + 70
+    Tin = 2 * (1 << octaves) if not up else 2
+    x = lcg_noise(np.arange(V, dtype=np.uint32) + 23, 64 * Tin * 2)
+    r = ml.Resampler(eng, V, octaves, up)
+    st = np.zeros((octaves * 9, V), np.float32)
+    for call in range(2):
+        xs = np.ascontiguousarray(x[:, call * 64 * Tin:(call + 1) * 64 * Tin])
+        assert_bits_equal(r.process_host(xs, layout, out_layout), oracle.resample(octaves, up, st, xs), True, f"octaves {octaves} up {up} call {call}")
+        assert_bits_equal(r.get_state(), st, True, f"HalfBandFilter state after call {call}")
+    r.close()
 
 
 @pytest.mark.gpu

@@ -268,6 +268,30 @@ def test_delay_lines_match_reference(oracle, ref, name):
         assert_bits_equal(mem_o, mem_r, True, f"{name} ring contents after call {call}")
 
 
+def test_long_ring_delay_lines_match_reference(oracle, ref):
+    """The same at the ring length of the GPU suite's long-ring cases: 2^19 samples, the write index 100 under the ring's end (the
+    first call wraps), a PitchbendableDelay's second ring 8 samples ahead of its first. Validates the oracle the GPU is compared with
+    there: outputs, state and ring contents against the reference's own classes, two calls."""
+    from inputs import long_ring_case
+    V, T, max_delay = 5, 3, 500000.0
+    L = ring_len(max_delay)
+    assert L == 1 << 19
+    for name in ("integer_var", "frac_var", "pitchbend"):
+        c = long_ring_case(oracle, name, V, 2 * T, max_delay, L - 100, seed=3, write_index2=(L - 92) & (L - 1))
+        rings = 2 if c["kind"] == Proc.PITCHBENDABLE_DELAY else 1
+        st_o, st_r = c["state0"].copy(), c["state0"].copy()
+        mem_o, mem_r = np.zeros((V, rings, L), np.float32), np.zeros((V, rings, L), np.float32)
+        for call in range(2):
+            sl = slice(call * 64 * T, (call + 1) * 64 * T)
+            ins = [np.ascontiguousarray(a[:, sl]) for a in c["inputs"]]
+            want = ref.delay_process(c["kind"], T, st_r, mem_r, ins)
+            got = oracle.delay_process(c["kind"], T, st_o, mem_o, ins)
+            assert_bits_equal(got, want, True, f"{name} call {call}")
+            assert_bits_equal(st_o, st_r, False, f"{name} state after call {call}")
+            assert_bits_equal(mem_o, mem_r, True, f"{name} ring contents after call {call}")
+        assert st_o[0, 0] == (L - 100 + 2 * 64 * T) % L and 2 * np.count_nonzero(got) >= got.size
+
+
 def test_allpass1_and_delay_coefficients_match_reference(oracle, ref):
     for d in (0.0, 0.3, 0.618, 0.9999, 1.0, 1.618, 5.5, 63.99, 64.0, 100.617, 1234.25):
         assert oracle.allpass1_coeffs(d) == ref.allpass1_coeffs(d)
