@@ -490,6 +490,25 @@ int mlgpu_bank_set_input_const(mlgpu_bank* b, const float* h_per_voice);
  * processor through the bank's HBM scratch signal (still on the GPU). */
 int mlgpu_bank_process(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout,
                        float* d_out, int out_layout);
+/* mlgpu_bank_process with the voices in GROUPS of adjacent voices: instruments of P voices that want one mixed channel each
+ * (Synth::processVector's voice sum, source/app/MLSynth.h:43-57), or filter banks that want one excitation row fanned out to P filters
+ * and their sum back (Bank<Bandpass, N> followed by addRows). One launch; the voices' own signals never reach memory.
+ *   in_group   1, 2, 4, 8 or 16: voice v reads row v / in_group of d_in, a signal of n_voices / in_group rows in `in_layout` (any
+ *              layout; MLGPU_LAYOUT_BROADCAST only with in_group 1). d_in NULL (the per-voice input constant): in_group must be 1.
+ *   out_group  1, 2, 4, 8 or 16: channel c of d_out is ((0 + y[c*G]) + y[c*G + 1]) + ... + y[c*G + G - 1], in voice order - the bits
+ *              mlgpu_mixdown_groups gives for mlgpu_bank_process's output. d_out is a signal of n_voices / out_group channels in
+ *              `out_layout` (64 * n_vectors * n_voices / out_group floats), written once. 1: the voices' signals as they are.
+ *   d_gains    per-voice gains [n_voices], or NULL: voice v's samples are multiplied by d_gains[v] (one float multiply) before the sum.
+ *              NULL is no multiply at all, not a multiply by one.
+ * n_voices must be a multiple of both groups (not of 64). State and coefficients as after mlgpu_bank_process; any split into launches
+ * gives the bits of one launch. Never allocates; can be recorded into a sequence.
+ * MLGPU_ERR_INVALID: a group size outside {1, 2, 4, 8, 16} (other sizes: mlgpu_mixdown_groups), voices that are not whole groups, an
+ * input group without d_in or with a broadcast input, a null or misaligned signal, a bad layout. MLGPU_ERR_UNSUPPORTED, with nothing launched and the state
+ * untouched: the bank is not one of the ahead-of-time chain kernels - it runs processor by processor (mlgpu_bank_is_fused() == 0), as
+ * an SVF cascade form, or as a kernel generated at run time. Such a bank takes the two steps (mlgpu_bank_process, then
+ * mlgpu_mixdown_groups), or is built as a graph (mlgpu_graph_set_input_group / mlgpu_graph_set_output_group_sum). */
+int mlgpu_bank_process_groups(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
+                              const float* d_gains, int out_group, float* d_out, int out_layout);
 /* 1 if the chain maps to a single fused kernel, 0 if it runs processor by processor. */
 int mlgpu_bank_is_fused(mlgpu_bank* b);
 /* Name of the device kernel that dominates mlgpu_bank_process (for profile lookup). */

@@ -642,6 +642,20 @@ class VoiceBank
     eng_.check(mlgpu_bank_process_mixdown_shard(b_, vectors, nullptr, MLGPU_LAYOUT_QUAD, gains, rows));
   }
 
+  // ... and when the voices belong together in groups of adjacent voices (mlgpu_bank_process_groups; groups of 1, 2, 4, 8, 16):
+  // `in` (or nullptr: the per-voice constant input, inGroup 1) has one row per inGroup voices - a filter bank's shared excitation -
+  // and `out` one channel per outGroup voices, their sum in voice order (Synth::processVector's `outputs += voice` per instrument,
+  // Bank<Bandpass, N> + addRows), the bits mlgpu_mixdown_groups gives. gains: per-voice, on the device, or none.
+  void processGroups(const DeviceSignal* in, int inGroup, const float* gains, int outGroup, DeviceSignal& out)
+  {
+    if (inGroup < 1 || outGroup < 1 || out.voices() * (size_t)outGroup != voices_ ||
+        (in && (in->voices() * (size_t)inGroup != voices_ || in->vectors() != out.vectors())))
+      throw Error(MLGPU_ERR_INVALID, "VoiceBank: signal shape mismatch");
+    commit();
+    eng_.check(mlgpu_bank_process_groups(b_, out.vectors(), in ? in->data() : nullptr, in ? in->layout() : MLGPU_LAYOUT_QUAD, inGroup, gains, outGroup,
+                                         out.data(), out.layout()));
+  }
+
   // raw state (checkpoint / resume)
   std::vector<uint32_t> state(int proc, int idx) const
   {

@@ -938,6 +938,40 @@ class Bank(_Handle):
         pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
         self.engine._check(self.L.mlgpu_bank_process_mixdown_shard(self.h, int(n_vectors), pin, int(in_layout), pg, pout))
 
+    def process_groups(self, n_vectors, d_out, out_group, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, in_group=1, d_gains=None):
+        """process with the voices in groups of adjacent voices (1, 2, 4, 8 or 16), in one launch (mlgpu_bank_process_groups): d_in
+        has one row per in_group voices, d_out one channel per out_group voices - ((0 + y0) + y1) + ... in voice order, the bits
+        Engine.mixdown_groups gives for process's output - and d_gains [V] scales each voice before the sum. The voices' own signals
+        are never written. Status.ERR_UNSUPPORTED for a bank that is not one of the ahead-of-time chain kernels."""
+        pin = None if d_in is None else ctypes.c_void_p(d_in.ptr if hasattr(d_in, "ptr") else int(d_in))
+        pout = ctypes.c_void_p(d_out.ptr if hasattr(d_out, "ptr") else int(d_out))
+        pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
+        self.engine._check(self.L.mlgpu_bank_process_groups(self.h, int(n_vectors), pin, int(in_layout), int(in_group), pg, int(out_group), pout,
+                                                            int(out_layout)))
+
+    def process_groups_host(self, n_vectors, out_group, in_signal=None, in_group=1, gains=None, layout=Layout.QUAD, in_layout=None):
+        """Test convenience beside process_host: in_signal [V / in_group][64T] and the result [V / out_group][64T] are VOICE_MAJOR
+        numpy, gains [V] numpy or None; the kernel writes `layout` and reads `in_layout` (default: the same)."""
+        eng, V, T = self.engine, self.V, int(n_vectors)
+        in_layout = layout if in_layout is None else in_layout
+        d_in = None
+        if in_signal is not None:
+            x = np.ascontiguousarray(in_signal, np.float32)
+            rows = V // int(in_group)
+            assert x.shape == (rows, 64 * T)
+            d_in = eng.to_device(x)
+            if in_layout != Layout.VOICE_MAJOR:
+                d_vm, d_in = d_in, eng.alloc(rows * T * 64 * 4)
+                eng.layout_convert(d_vm, Layout.VOICE_MAJOR, d_in, in_layout, rows, T)
+        d_gains = None if gains is None else eng.to_device(np.ascontiguousarray(gains, np.float32))
+        chans = V // int(out_group)
+        res = eng.alloc(chans * T * 64 * 4)
+        self.process_groups(T, res, out_group, layout, d_in, in_layout, in_group, d_gains)
+        if layout != Layout.VOICE_MAJOR:
+            d_out, res = res, eng.alloc(chans * T * 64 * 4)
+            eng.layout_convert(d_out, layout, res, Layout.VOICE_MAJOR, chans, T)
+        return res.download(np.float32, chans * T * 64).reshape(chans, 64 * T)
+
     def process_host(self, n_vectors, in_signal=None, layout=Layout.QUAD):
         """Test convenience: in_signal/out are VOICE_MAJOR [V][64T] numpy; the kernel runs in `layout`
         (conversion done by the device layout kernel)."""

@@ -41,6 +41,23 @@ hipError_t launchChainMix(const ChainArgs& a, hipStream_t stream, int /*cuCount*
   return hipGetLastError();
 }
 
+// the group form (mlgpu_bank_process_groups): outGroup picks the instantiation, a.inGroupShift and a.mixGains travel as arguments
+template <bool HAS_SIGNAL, int... KS>
+hipError_t launchChainGroups(const ChainArgs& a, int outGroup, hipStream_t stream)
+{
+  const dim3 blocks((unsigned)((a.V + kChainBlock - 1) / kChainBlock)), block(kChainBlock);
+  switch (outGroup)
+  {
+    case 1: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 1>), blocks, block, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 2>), blocks, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 4>), blocks, block, 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 8>), blocks, block, 0, stream, a); break;
+    case 16: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 16>), blocks, block, 0, stream, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 // How many wavefront lanes share one channel of a head-less SVF cascade (cascade_lanes_kernel). One lane per channel is the
 // cheapest per sample, but a bank needs ~49 000 channels before its wavefronts (two per SIMD at ~190 VGPRs) fill the chip;
 // smaller banks are spread over 2 or 4 lanes per channel (4 or 6 wavefronts per SIMD). Thresholds from
@@ -137,6 +154,8 @@ ChainEntry makeEntry(const char* name)
   e.kinds = {KS...};
   e.launchSignal = &launchChain<true, KS...>;
   e.launchConst = &launchChain<false, KS...>;
+  e.launchGroupsSignal = &launchChainGroups<true, KS...>;
+  e.launchGroupsConst = &launchChainGroups<false, KS...>;
   // what a profiler prints for this kernel: "chain_kernel<mldev::Chain<2, 18, 48>, false>(ChainArgs)";
   // `name` is the human-readable alias used in logs.
   static const std::string profName = [] {

@@ -127,12 +127,93 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
   }
 }
 
-template <class CH, bool HAS_SIGNAL, bool MIX = false>
+// ---- groups of adjacent voices inside the voice kernel (chain_group_kernel) ----
+// A bank of instruments (OUT_G voices each, one mixed channel per instrument: Synth::processVector's voice sum, source/app/MLSynth.h:43-57)
+// or of filter banks (one excitation row for every a.inGroup voices, their sum back). Voice v reads the streamed input at row
+// v >> a.inGroupShift; channel c of the output is ((0 + y[c G]) + y[c G + 1]) + ... + y[c G + G - 1], the bits mlgpu_mixdown_groups
+// gives, written once - the voices' own signals never reach memory. G = 2, 4, 8: the lane-shift chain, the group's last lane stores
+// the quad. G = 16: the LDS strip of mldsp_math.hpp, lane (g, s) stores one float per four quads. G = 1: the plain store (an input
+// group alone). A group never leaves its wavefront (G divides 64) and the bank's voices are whole groups, so the lanes past the last
+// voice are whole groups that have no channel: they leave the kernel like chain_kernel's, before the loop, and neither the lane
+// shifts nor the strip's sums ever look at them (the strip's barrier orders one wavefront's own LDS operations; it is not a
+// rendezvous of lanes).
+template <int OUT_G>
+struct GroupStrips
+{
+  static __device__ __forceinline__ float* mine() { return nullptr; }
+};
+template <>
+struct GroupStrips<16>
+{
+  static __device__ __forceinline__ float* mine()
+  {
+    __shared__ __attribute__((aligned(16))) float lds[(256 / 64) * kGroup16Strip];
+    return lds + (threadIdx.x >> 6) * kGroup16Strip;
+  }
+};
+
+// run_voice with the group forms of input and output (GAINS: a.mixGains scales the voice before the sum - a loop of its own, so that
+// a launch without gains has no multiply at all)
+template <class CH, bool HAS_SIGNAL, bool FAST_HEAD, int OUT_G, bool GAINS>
+__device__ __forceinline__ void run_voice_groups(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip)
+{
+  static_assert(OUT_G == 1 || OUT_G == 2 || OUT_G == 4 || OUT_G == 8 || OUT_G == 16, "group_sum_in_order's sizes, or none");
+  const float gain = GAINS ? a.mixGains[v] : 1.f;
+  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (v >> a.inGroupShift) * a.in.strideV : nullptr;
+  f32x4* pout = (f32x4*)a.out.base + (v / OUT_G) * a.out.strideV;  // (OUT_G == 16: lane (g, s)'s own channel is the group g it adds up)
+  const bool lastOfGroup = (threadIdx.x & (OUT_G - 1)) == OUT_G - 1;
+  const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
+  const uint32_t slot = wave_slot();
+  for (size_t t = 0; t < a.T; ++t)
+  {
+    const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
+    f32x4* po = pout + t * a.out.strideT;
+#pragma unroll 4
+    for (int q = 0; q < 16; ++q)
+    {
+      if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
+      f32x4 x = {xc, xc, xc, xc};
+      if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
+      f32x4 y;
+      y.x = ch.template next_head<FAST_HEAD>(x.x);
+      y.y = ch.template next_head<FAST_HEAD>(x.y);
+      y.z = ch.template next_head<FAST_HEAD>(x.z);
+      y.w = ch.template next_head<FAST_HEAD>(x.w);
+      if constexpr (GAINS)
+      {
+        y.x *= gain;
+        y.y *= gain;
+        y.z *= gain;
+        y.w *= gain;
+      }
+      if constexpr (OUT_G == 1)
+        __builtin_nontemporal_store(y, po + q * outQ);
+      else if constexpr (OUT_G == 16)
+      {
+        group16_park(strip, q & 3, y);
+        if ((q & 3) == 3) group16_sum_store(strip, po + (size_t)(q - 3) * outQ, outQ);
+      }
+      else
+      {
+        y.x = group_sum_in_order<OUT_G>(y.x);
+        y.y = group_sum_in_order<OUT_G>(y.y);
+        y.z = group_sum_in_order<OUT_G>(y.z);
+        y.w = group_sum_in_order<OUT_G>(y.w);
+        if (lastOfGroup) __builtin_nontemporal_store(y, po + q * outQ);
+      }
+    }
+    ch.end_vector();
+  }
+}
+
+// OUT_G != 0: the group form (chain_group_kernel)
+template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0>
 __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
 {
+  static_assert(!(MIX && OUT_G), "one summing form at a time");
   apply_fp_mode(a.flags);
   __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
-  float* const strip = MixStrips<MIX>::mine();
+  float* const strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
   if constexpr (CH::kHasImpulse)
   {
     if (threadIdx.x < Proc<MLGPU_PROC_IMPULSE_GEN>::kTableSize) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];
@@ -169,7 +250,21 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   // range test: decide once per wavefront which loop body to run.
   bool fastHead = false;
   if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(CH::head_input_is_odd(xc)) == 0);
-  if constexpr (MIX)
+  if constexpr (OUT_G != 0)
+  {
+    if (a.mixGains != nullptr)  // (the same in all lanes: a kernel argument)
+    {
+      if (fastHead)
+        run_voice_groups<CH, HAS_SIGNAL, true, OUT_G, true>(ch, a, v, xc, strip);
+      else
+        run_voice_groups<CH, HAS_SIGNAL, false, OUT_G, true>(ch, a, v, xc, strip);
+    }
+    else if (fastHead)
+      run_voice_groups<CH, HAS_SIGNAL, true, OUT_G, false>(ch, a, v, xc, strip);
+    else
+      run_voice_groups<CH, HAS_SIGNAL, false, OUT_G, false>(ch, a, v, xc, strip);
+  }
+  else if constexpr (MIX)
   {
     const bool scaled = a.mixGains != nullptr || __builtin_amdgcn_ballot_w64(!live) != 0;  // (the same in all lanes)
     if (scaled)
@@ -203,6 +298,14 @@ template <class CH, bool HAS_SIGNAL>
 __global__ __launch_bounds__(kChainBlock) void chain_mix_kernel(const ChainArgs a)
 {
   chain_kernel_body<CH, HAS_SIGNAL, true>(a);
+}
+
+// the same voices in groups: input row v >> a.inGroupShift, one output channel per OUT_G adjacent voices (see run_voice_groups);
+// state as chain_kernel leaves it.
+template <class CH, bool HAS_SIGNAL, int OUT_G>
+__global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, false, OUT_G>(a);
 }
 
 // ---------------------------------------------------------------------------------------------

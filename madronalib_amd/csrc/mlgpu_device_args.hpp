@@ -38,6 +38,9 @@ struct ChainArgs
   uint32_t flags;  // MLGPU_KFLAG_*
   float* mix;      // chain_mix_kernel: the rows of 64-voice group sums, [(group * T + t) * 64 + sample] (mlgpu_mixdown's first stage); else unused
   const float* mixGains;  // ... and the per-voice gains the voices are scaled by before (mlgpu_mixdown's d_gains), or nullptr
+  // chain_group_kernel (which scales by mixGains too, before its group sums): voice v reads row v >> inGroupShift of `in`, and
+  // `out` is a signal of V / OUT_G channels; else unused
+  uint32_t inGroupShift = 0;
 };
 
 // EventsToSignals settings the device needs (events.hip, mldsp_events.hpp)

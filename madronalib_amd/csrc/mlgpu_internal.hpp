@@ -131,6 +131,7 @@ inline SignalView makeView(const float* p, int layout, size_t V, size_t T)
 }
 
 typedef hipError_t (*ChainLauncher)(const ChainArgs& a, hipStream_t stream, int cuCount);
+typedef hipError_t (*ChainGroupLauncher)(const ChainArgs& a, int outGroup, hipStream_t stream);
 
 struct ChainEntry
 {
@@ -138,6 +139,7 @@ struct ChainEntry
   ChainLauncher launchSignal;  // streamed input
   ChainLauncher launchConst;   // per-voice constant (or no) input
   ChainLauncher launchMixSignal{nullptr}, launchMixConst{nullptr};  // chain_mix_kernel (the voices' sum instead of their signals), where instantiated
+  ChainGroupLauncher launchGroupsSignal{nullptr}, launchGroupsConst{nullptr};  // chain_group_kernel (voices in groups of 1, 2, 4, 8, 16): the chain kernels, not the cascades
   const char* kernelName;  // prefix of the name a profiler shows for the device kernel
   const char* (*kernelNameFor)(size_t V, uint32_t flags){nullptr};  // where the kernel depends on the bank's size (SVF cascades)
   const char* alias;       // e.g. "chain_kernel<SawGen,Bandpass,Gain>"
