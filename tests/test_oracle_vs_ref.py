@@ -215,6 +215,35 @@ def test_pulse_gen_absurd_widths_match_reference(oracle, ref):
         assert_bits_equal(st_o, st_r, False, "state")
 
 
+def test_stream_osc_census_matches_reference(oracle, ref):
+    """SawGen and PulseGen on a frequency that moves every sample, in the combinations tests/stream_osc_cases.py drives the device with:
+    hostile frequencies (2^65 and negative zero among them) next to edge widths, absurd and mildly odd widths on a time-varying frequency,
+    the width as PulseGen's second input and as its coefficient, the frequency made of exp2Approx(pitch) * base with NaN / infinite /
+    +-200 pitches; two launches, outputs and counters. Pins the oracle where tests/test_gpu_stream_osc.py takes it as the authority."""
+    import stream_osc_cases as sc
+    data = sc.census_data()
+    V, T = sc.V0, sc.T0
+    cf = sc.structural_cases(data)["computed_freq"]
+    w = np.ascontiguousarray(data["w"][None, :])
+    none = np.zeros((0, V), np.float32)
+    for what, f in (("census", data["f"]), ("computed", sc.freq_of(oracle, cf))):
+        if what == "computed":
+            assert_bits_equal(f, sc.freq_of(ref, cf), True, "exp2Approx(pitch) * base")
+        st = {(c, k): np.ascontiguousarray(data["phases"][None, :].copy()) for c in "or" for k in ("saw", "p2", "pc")}
+        for call in range(2):
+            part = np.ascontiguousarray(f[:, call * 64 * T:(call + 1) * 64 * T])
+            ws = np.ascontiguousarray(np.repeat(data["w"][:, None], 64 * T, 1))
+            res = {}
+            for c, chk in (("o", oracle), ("r", ref)):
+                res[c] = [chk.chain_process([Proc.SAW_GEN], T, none, st[c, "saw"], part, None),
+                          chk.proc_multi(Proc.PULSE_GEN, T, w, st[c, "p2"], [part, ws]),
+                          chk.chain_process([Proc.PULSE_GEN], T, w, st[c, "pc"], part, None)]
+            for i, nm in enumerate(("saw", "pulse(f, w)", "pulse(f), width coefficient")):
+                assert_bits_equal(res["o"][i], res["r"][i], True, f"{what} frequency, {nm}, launch {call}")
+            for k in ("saw", "p2", "pc"):
+                assert_bits_equal(st["o", k], st["r", k], False, f"{what} frequency, counters of {k} after launch {call}")
+
+
 @pytest.mark.parametrize("vop", [Vop.COLUMN_INDEX, Vop.RANGE_OPEN, Vop.RANGE_CLOSED, Vop.INTERPOLATE_LINEAR])
 def test_vector_generators_match_reference(oracle, ref, vop):
     V, T = 9, 17

@@ -3,7 +3,9 @@
 1 .. 4 delay nodes of all three kinds (delay times per voice, made of an audio node, or the node's state) in a random ring layout, plus
 0 .. 2 feedback nodes - on the device against the oracle's vector-by-vector evaluator (tests/graph_oracle.py: evaluate_stream), every
 output of two launches bit for bit. The delay tests pin the delay nodes in small fixed graphs; this puts them next to everything else
-the generator emits (node order, the reads issued ahead, LDS of several features in one kernel).
+the generator emits (node order, the reads issued ahead, LDS of several features in one kernel). The wide graphs (every second one) also
+get a PulseGen and / or a SawGen on an audio-rate frequency, each an output of the graph: the per-sample forms, and in a quarter of them
+the stream-locked pair - its locked branch only, since every counter starts from clear() (unequal counters: tests/test_gpu_stream_osc.py).
     python tools/graph_stream_fuzz.py [cases] [first seed]"""
 import os
 import sys
@@ -64,6 +66,21 @@ def widen(rng, orc, V, desc, params, coeffs):
             if co is not None and np.size(co):
                 coeffs[name] = np.ascontiguousarray(co, np.float32)
         audio.append(name)
+    # a PulseGen and a SawGen on an AUDIO-RATE frequency (|signal| * small, as random_graph makes its generators'), each in every second
+    # wide graph: alone the per-sample forms (next_sw / next), together on one frequency node the pair of planStreamLocks (step_locked_stream)
+    fsrc = None
+    for kind, name in ((Proc.PULSE_GEN, "wsp"), (Proc.SAW_GEN, "wss")):
+        if rng.random() >= 0.5:
+            continue
+        if fsrc is None:
+            fsrc = "wsf"
+            desc.append(dict(name="wsa", type="op", kind=Op.ABS, inputs=[str(rng.choice(audio))]))
+            desc.append(dict(name=fsrc, type="op", kind=Op.MULTIPLY, inputs=["wsa", "small"]))
+        desc.append(dict(name=name, type="proc", kind=kind, inputs=[fsrc]))
+        co = proc_default_coeffs(orc, kind, V, seed=int(rng.integers(0, 1000)))
+        if co is not None and np.size(co):
+            coeffs[name] = np.ascontiguousarray(co, np.float32)
+        audio.append(name)
     return audio
 
 
@@ -119,7 +136,8 @@ def build(rng, orc, V, wide=False):
                 desc.insert(k, mix)
                 d["inputs"] = [f"fx{j}"] + d["inputs"][1:]
                 break
-    outs = list(dict.fromkeys([audio[-1], outs[0]]))
+    # (the wide graphs' oscillators on an audio-rate frequency are outputs themselves: compared in every graph that holds them)
+    outs = list(dict.fromkeys([audio[-1], outs[0]] + [d["name"] for d in desc if d["name"] in ("wsp", "wss")]))
     return desc, outs, params, coeffs, rings
 
 
