@@ -745,6 +745,56 @@ int mlgpu_graph_set_input_layout(mlgpu_graph* g, int input_index, int layout);
 int mlgpu_graph_process_ctl(mlgpu_graph* g, size_t n_vectors, const float* const* d_inputs, int in_layout,
                             const float* const* d_controls, float* const* d_outputs, int out_layout);
 
+/* ---- Sparse, stream-ordered updates of per-voice params, coefficients and state ----------------------------------------------
+ * The whole-row setters above (and the bank's) take all n_voices values and wait for the device. A live instrument bank changes a
+ * few voices per block: a list of update records, applied by one small kernel on the engine's stream, ordered between the process
+ * calls around it. The call never waits for the device (except for its own call before last), and after a reserve never allocates.
+ *
+ * A record writes `bits` (a float's bit pattern, or a state word, exactly as given) to voices [first_voice, first_voice + n_voices)
+ * of one table row. After mlgpu_*_apply_updates(recs, n) the tables hold exactly what the records applied one at a time, in list
+ * order, would leave - what the equivalent whole-row setters leave. Where two records of one call cover the same word the later
+ * one wins: overlaps are found on the host and the list is cut into several launches there (a list without overlaps is one launch).
+ *
+ * MLGPU_UPDATE_CLEAR is T::clear() for those voices only: expanded on the host into one device record per state word clear()
+ * resets (mlgpu_graph_clear_proc's words; a feedback node's stored vector becomes zeros). A node with delay rings is refused with
+ * MLGPU_ERR_UNSUPPORTED (node = -1 in a graph that has one, too). The graph's DSPVector count that pairs the vectors of
+ * DOWNSAMPLE_2X regions is per graph, not per voice: mlgpu_graph_clear resets it, a CLEAR record does not.
+ *
+ * Everything is validated before anything is enqueued; a refused list changes no table word and the error text names the record's
+ * position. MLGPU_ERR_INVALID: a node of the wrong type, n_voices == 0, an unknown target, INPUT_CONST on a graph, PARAM on a bank,
+ * a graph that is not compiled, a call while recording a sequence (it reads host memory; between the launches of a recorded
+ * sequence it works - the sequence has the tables' addresses). MLGPU_ERR_RANGE: a node, an index or a voice range out of range, and
+ * a list that needs more device records than were reserved. MLGPU_ERR_BUSY: a compile job owns the graph. n == 0: MLGPU_OK.
+ *
+ * mlgpu_*_reserve_updates(max_device_records) is setup (it allocates and waits): from then on apply_updates never allocates and
+ * refuses a list that costs more (mlgpu_graph_update_device_records says what a list costs: one per record, a CLEAR one per cleared
+ * state word; 0 for a list that would be refused). Without a reserve the buffers grow inside the call: a setup convenience that
+ * allocates and may wait. One list holds at most 2^25 device records, reserved or not (MLGPU_ERR_INVALID / MLGPU_ERR_RANGE). */
+typedef enum mlgpu_update_target
+{
+  MLGPU_UPDATE_PARAM = 0,       /* graph: node = a param node; index ignored */
+  MLGPU_UPDATE_COEFF = 1,       /* graph: node = a proc node, index = coefficient slot; bank: node = processor index */
+  MLGPU_UPDATE_STATE = 2,       /* graph: proc / feedback node, index = state word; bank: processor index; bits as given */
+  MLGPU_UPDATE_INPUT_CONST = 3, /* bank only: the table of mlgpu_bank_set_input_const; node and index ignored */
+  MLGPU_UPDATE_CLEAR = 4        /* T::clear() of node (node = -1: every processor and feedback node) for these voices only */
+} mlgpu_update_target;
+typedef struct mlgpu_update
+{
+  int32_t node;
+  uint16_t target; /* mlgpu_update_target */
+  uint16_t index;
+  uint32_t first_voice, n_voices;
+  uint32_t bits;
+} mlgpu_update;
+int mlgpu_graph_reserve_updates(mlgpu_graph* g, size_t max_device_records);
+int mlgpu_graph_apply_updates(mlgpu_graph* g, const mlgpu_update* recs, size_t n);
+size_t mlgpu_graph_update_device_records(mlgpu_graph* g, const mlgpu_update* recs, size_t n);
+int mlgpu_bank_reserve_updates(mlgpu_bank* b, size_t max_device_records);
+int mlgpu_bank_apply_updates(mlgpu_bank* b, const mlgpu_update* recs, size_t n);
+/* read-backs beside mlgpu_graph_get_state (they wait for the device, like it) */
+int mlgpu_graph_get_param(mlgpu_graph* g, int param_node, float* h_per_voice);
+int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h_per_voice);
+
 /* Chains without an ahead-of-time kernel are fused with hiprtc when their bank is created
  * (default on). With jit off they run processor by processor through HBM scratch signals. */
 int mlgpu_engine_set_jit(mlgpu_engine* e, int enabled);

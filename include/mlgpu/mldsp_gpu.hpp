@@ -665,6 +665,29 @@ class VoiceBank
   }
   void setState(int proc, int idx, const std::vector<uint32_t>& s) { eng_.check(mlgpu_bank_set_state(b_, proc, idx, s.data())); }
   void setStateAll(int proc, int idx, uint32_t v) { eng_.check(mlgpu_bank_set_state_uniform(b_, proc, idx, v)); }
+
+  // A knob turned on some of the voices while the bank runs (mlgpu_bank_apply_updates): records {processor, target, index, first
+  // voice, voices, bits} applied on the engine's stream between the process calls around them, without waiting for the device.
+  // reserveUpdates at setup makes the call allocation-free. What coeffs() / input() staged goes first - through commit(), whose
+  // whole-row uploads WAIT for the device: on an audio thread, stage nothing between process calls and use records alone. The
+  // host copies follow the records, so a later commit() uploads what the device already holds.
+  void reserveUpdates(size_t maxDeviceRecords) { eng_.check(mlgpu_bank_reserve_updates(b_, maxDeviceRecords)); }
+  void applyUpdates(const mlgpu_update* recs, size_t n)
+  {
+    commit();
+    eng_.check(mlgpu_bank_apply_updates(b_, recs, n));
+    for (size_t r = 0; r < n; ++r)
+    {
+      const mlgpu_update& u = recs[r];
+      float f;
+      std::memcpy(&f, &u.bits, 4);
+      if (u.target == MLGPU_UPDATE_COEFF)
+        std::fill_n(hostCoeffs_[(size_t)u.node].begin() + (size_t)u.index * voices_ + u.first_voice, u.n_voices, f);
+      else if (u.target == MLGPU_UPDATE_INPUT_CONST)
+        std::fill_n(hostInput_.begin() + u.first_voice, u.n_voices, f);
+    }
+  }
+  void applyUpdates(const std::vector<mlgpu_update>& recs) { applyUpdates(recs.data(), recs.size()); }
 };
 
 }  // namespace gpu

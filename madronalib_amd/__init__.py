@@ -13,9 +13,9 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .constants import FLOATS_PER_DSPVECTOR, Layout, Op, Proc, Region, Route, RowOp, RowsRule, Status, Vop
+from .constants import FLOATS_PER_DSPVECTOR, Layout, Op, Proc, Region, Route, RowOp, RowsRule, Status, UpdateTarget, Vop
 
-__all__ = ["Engine", "Bank", "Graph", "DSPBuffer", "ProcessBuffer", "Resampler", "Events", "Event", "EventType", "jit_selftest", "DeviceBuffer", "MlgpuError", "Layout", "Op", "Proc", "RowOp", "Status", "Vop", "Route", "RowsRule", "Allpass1", "FractionalDelay", "LinearGlide", "SampleAccurateLinearGlide",
+__all__ = ["Engine", "Bank", "Graph", "Update", "UpdateTarget", "DSPBuffer", "ProcessBuffer", "Resampler", "Events", "Event", "EventType", "jit_selftest", "DeviceBuffer", "MlgpuError", "Layout", "Op", "Proc", "RowOp", "Status", "Vop", "Route", "RowsRule", "Allpass1", "FractionalDelay", "LinearGlide", "SampleAccurateLinearGlide",
            "Lopass", "Hipass", "Bandpass", "LoShelf", "HiShelf", "Bell", "OnePole", "DCBlocker", "ADSR",
            "dBToGain", "device_count", "FLOATS_PER_DSPVECTOR"]
 
@@ -823,6 +823,47 @@ class Resampler(_Handle):
         return res.download(np.float32, V * 64 * Tout).reshape(V, 64 * Tout)
 
 
+class Update(ctypes.Structure):  # mlgpu_update
+    """One record of Graph.apply_updates / Bank.apply_updates: `bits` to voices [first_voice, first_voice + n_voices) of one table
+    row. The constructors take a float (param, coeff, input_const) or a state word; `node` is a graph's node id (Graph.ids) or a
+    bank's processor index."""
+    _fields_ = [("node", ctypes.c_int32), ("target", ctypes.c_uint16), ("index", ctypes.c_uint16), ("first_voice", ctypes.c_uint32),
+                ("n_voices", ctypes.c_uint32), ("bits", ctypes.c_uint32)]
+
+    @staticmethod
+    def _float_bits(value):
+        return int(np.float32(value).view(np.uint32))
+
+    @classmethod
+    def param(cls, node, first_voice, n_voices, value):
+        return cls(int(node), UpdateTarget.PARAM, 0, int(first_voice), int(n_voices), cls._float_bits(value))
+
+    @classmethod
+    def coeff(cls, node, index, first_voice, n_voices, value):
+        return cls(int(node), UpdateTarget.COEFF, int(index), int(first_voice), int(n_voices), cls._float_bits(value))
+
+    @classmethod
+    def state(cls, node, index, first_voice, n_voices, bits):
+        return cls(int(node), UpdateTarget.STATE, int(index), int(first_voice), int(n_voices), int(bits) & 0xFFFFFFFF)
+
+    @classmethod
+    def input_const(cls, first_voice, n_voices, value):
+        return cls(0, UpdateTarget.INPUT_CONST, 0, int(first_voice), int(n_voices), cls._float_bits(value))
+
+    @classmethod
+    def clear(cls, node, first_voice, n_voices):
+        """T::clear() of `node` (-1: every processor and feedback node) for these voices only."""
+        return cls(int(node), UpdateTarget.CLEAR, 0, int(first_voice), int(n_voices), 0)
+
+
+def _update_array(records):
+    """records: a ctypes array of Update (used as it is) or a sequence of Update."""
+    if isinstance(records, ctypes.Array) and records._type_ is Update:
+        return records, len(records)
+    records = list(records)
+    return (Update * max(1, len(records)))(*records), len(records)
+
+
 class Bank(_Handle):
     """Runtime-sized Bank<T,ROWS> (reference MLDSPFunctional.h:321-360): V voices of one chain."""
     _destroy = "mlgpu_bank_destroy"
@@ -910,6 +951,16 @@ class Bank(_Handle):
         v = np.ascontiguousarray(per_voice, np.float32)
         assert v.shape == (self.V,)
         self.engine._check(self.L.mlgpu_bank_set_input_const(self.h, _np_ptr(v)))
+
+    def reserve_updates(self, max_device_records):
+        """Setup: from now on apply_updates never allocates, and refuses (Status.ERR_RANGE) a list that needs more device records."""
+        self.engine._check(self.L.mlgpu_bank_reserve_updates(self.h, int(max_device_records)))
+
+    def apply_updates(self, records):
+        """Enqueue a list of Update records (COEFF, STATE, INPUT_CONST, CLEAR; node = processor index) on the engine's stream, ordered
+        between the process calls around it; does not wait for the device (mlgpu_bank_apply_updates)."""
+        arr, n = _update_array(records)
+        self.engine._check(self.L.mlgpu_bank_apply_updates(self.h, arr, n))
 
     def process(self, n_vectors, d_out, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD):
         """Enqueue n_vectors DSPVectors for every voice. d_in/d_out: DeviceBuffer or raw int pointer."""
@@ -1264,6 +1315,32 @@ class Graph(_Handle):
     def set_state(self, node, idx, value):
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(value, np.uint32), (self.V,)))
         self.engine._check(self.L.mlgpu_graph_set_state(self.h, self._id(node), idx, _np_ptr(v)))
+
+    def get_param(self, node):
+        out = np.empty(self.V, np.float32)
+        self._check(self.L.mlgpu_graph_get_param(self.h, self._id(node), _np_ptr(out)))
+        return out
+
+    def get_coeff(self, node, idx):
+        out = np.empty(self.V, np.float32)
+        self._check(self.L.mlgpu_graph_get_coeff(self.h, self._id(node), int(idx), _np_ptr(out)))
+        return out
+
+    def reserve_updates(self, max_device_records):
+        """Setup: from now on apply_updates never allocates, and refuses (Status.ERR_RANGE) a list that needs more device records
+        (update_device_records says what a list costs)."""
+        self._check(self.L.mlgpu_graph_reserve_updates(self.h, int(max_device_records)))
+
+    def update_device_records(self, records):
+        arr, n = _update_array(records)
+        return int(self.L.mlgpu_graph_update_device_records(self.h, arr, n))
+
+    def apply_updates(self, records):
+        """Enqueue a list of Update records (PARAM, COEFF, STATE, CLEAR; node = node id) on the engine's stream, ordered between the
+        process calls around it; does not wait for the device (mlgpu_graph_apply_updates). Where records of one list overlap the
+        later one wins."""
+        arr, n = _update_array(records)
+        self._check(self.L.mlgpu_graph_apply_updates(self.h, arr, n))
 
     def set_input_layout(self, input_index, layout):
         self.engine._check(self.L.mlgpu_graph_set_input_layout(self.h, int(input_index), int(layout)))

@@ -314,6 +314,13 @@ def _declare(L):
     sig("mlgpu_graph_get_state", i, [vp, i, i, vp])
     sig("mlgpu_graph_set_state", i, [vp, i, i, vp])
     sig("mlgpu_graph_process", i, [vp, sz, pp, i, pp, i])
+    sig("mlgpu_graph_get_param", i, [vp, i, vp])
+    sig("mlgpu_graph_get_coeff", i, [vp, i, i, vp])
+    sig("mlgpu_graph_reserve_updates", i, [vp, sz])
+    sig("mlgpu_graph_apply_updates", i, [vp, vp, sz])
+    sig("mlgpu_graph_update_device_records", sz, [vp, vp, sz])
+    sig("mlgpu_bank_reserve_updates", i, [vp, sz])
+    sig("mlgpu_bank_apply_updates", i, [vp, vp, sz])
     sig("mlgpu_lopass_make_coeffs", None, [f, f, fp])
     sig("mlgpu_hipass_make_coeffs", None, [f, f, fp])
     sig("mlgpu_bandpass_make_coeffs", None, [f, f, fp])

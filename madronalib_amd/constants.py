@@ -23,6 +23,14 @@ class Layout:
     BROADCAST = 3    # [S] one voice's stream read by every voice (inputs only)
 
 
+class UpdateTarget:   # mlgpu_update_target: what a record of Graph.apply_updates / Bank.apply_updates writes
+    PARAM = 0
+    COEFF = 1
+    STATE = 2
+    INPUT_CONST = 3
+    CLEAR = 4
+
+
 class Op:
     SQRT = 0
     SQRT_APPROX = 1

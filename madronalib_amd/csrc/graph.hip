@@ -97,6 +97,7 @@ struct mlgpu_graph
   std::vector<Variant> variants;
   OwnedEvent tuneEv0, tuneEv1;
   int inLayoutOverride[MLGPU_GRAPH_MAX_INPUTS];  // -1: none
+  mlgpu_updater updates;         // mlgpu_graph_apply_updates: the planner, the tables' description, the staging sets
   mlgpu_graph()
   {
     for (int& x : inLayoutOverride) x = -1;
@@ -988,6 +989,94 @@ extern "C"
     if (idx < 0 || idx >= g->desc.nodes[node].ns) return gfail(g, MLGPU_ERR_RANGE, "state index out of range");
     return mlgpu_upload(g->e, g->d_state.get() + (size_t)(g->desc.nodes[node].sOff + idx) * g->desc.V, h, sizeof(uint32_t) * g->desc.V);
   }
+
+  int mlgpu_graph_get_param(mlgpu_graph* g, int node, float* h)
+  {
+    int st = checkNode(g, node, NODE_PARAM);
+    if (st) return st;
+    if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_get_param: compile first / null");
+    return mlgpu_download(g->e, h, g->d_params.get() + (size_t)g->desc.nodes[node].slot * g->desc.V, sizeof(float) * g->desc.V);
+  }
+  int mlgpu_graph_get_coeff(mlgpu_graph* g, int node, int idx, float* h)
+  {
+    int st = checkNode(g, node, NODE_PROC);
+    if (st) return st;
+    if (!g->compiled || !h) return gfail(g, MLGPU_ERR_INVALID, "graph_get_coeff: compile first / null");
+    if (idx < 0 || idx >= g->desc.nodes[node].nc) return gfail(g, MLGPU_ERR_RANGE, "coefficient index out of range");
+    return mlgpu_download(g->e, h, g->d_coeffs.get() + (size_t)(g->desc.nodes[node].cOff + idx) * g->desc.V, sizeof(float) * g->desc.V);
+  }
+
+  // ---- sparse, stream-ordered updates (param_updates.hpp plans, updates.hip applies) ----
+  // The compiled graph's tables as the planner sees them: which rows each node owns, and what clearNode() writes to a node's state
+  static int updatesReady(mlgpu_graph* g, const char* who)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": compile first");
+    mlgpu_updater& u = g->updates;
+    if (u.described) return MLGPU_OK;
+    u.desc.bank = false;
+    u.desc.V = g->desc.V;
+    u.desc.nodes.assign(g->desc.nodes.size(), mlupd::NodeDesc());
+    for (size_t i = 0; i < g->desc.nodes.size(); ++i)
+    {
+      const Node& n = g->desc.nodes[i];
+      mlupd::NodeDesc& nd = u.desc.nodes[i];
+      if (n.type == NODE_PARAM)
+      {
+        nd.kind = mlupd::NodeDesc::PARAM;
+        nd.paramRow = n.slot;
+      }
+      else if (n.type == NODE_FEEDBACK)
+      {
+        nd.kind = mlupd::NodeDesc::FEEDBACK;
+        nd.sOff = n.sOff;
+        nd.ns = n.ns;
+        nd.clearWords.assign((size_t)n.ns, 0u);
+        nd.clearMask.assign((size_t)n.ns, 1);
+      }
+      else if (n.type == NODE_PROC)
+      {
+        nd.kind = mlupd::NodeDesc::PROC;
+        nd.cOff = n.cOff;
+        nd.nc = n.nc;
+        nd.sOff = n.sOff;
+        nd.ns = n.ns;
+        nd.rings = n.ringLen != 0 || mlgpu_proc_rings(n.kind) > 0;
+        uint32_t words[MLGPU_MAX_PROC_STATE];
+        mlgpu_proc_clear_state(n.kind, words, true);
+        const uint64_t mask = mlgpu_proc_clear_mask(n.kind);
+        nd.clearWords.assign(words, words + n.ns);
+        nd.clearMask.resize((size_t)n.ns);
+        for (int w = 0; w < n.ns; ++w) nd.clearMask[(size_t)w] = (uint8_t)((mask >> (w < 64 ? w : 63)) & 1);
+      }
+    }
+    u.described = true;
+    return MLGPU_OK;
+  }
+  int mlgpu_graph_reserve_updates(mlgpu_graph* g, size_t maxDeviceRecords)
+  {
+    if (const int st = updatesReady(g, "graph_reserve_updates")) return st;
+    std::string err;
+    const int st = mlgpu_updater_reserve(g->e, g->updates, maxDeviceRecords, err);
+    return st == MLGPU_OK ? st : gfail(g, st, "graph_" + err);
+  }
+  size_t mlgpu_graph_update_device_records(mlgpu_graph* g, const mlgpu_update* recs, size_t n)
+  {
+    if (updatesReady(g, "graph_update_device_records")) return 0;
+    return mlgpu_updater_device_records(g->updates, recs, n);
+  }
+  int mlgpu_graph_apply_updates(mlgpu_graph* g, const mlgpu_update* recs, size_t n)
+  {
+    if (const int st = updatesReady(g, "graph_apply_updates")) return st;
+    uint32_t* const tables[mlupd::kTables] = {(uint32_t*)g->d_params.get(), (uint32_t*)g->d_coeffs.get(), g->d_state.get(), nullptr};
+    std::string err;
+    const int st = mlgpu_updater_apply(g->e, g->updates, tables, recs, n, err);
+    return st == MLGPU_OK ? st : gfail(g, st, "graph_" + err);
+  }
+  // Not in mlgpu.h: the tests' view of the staging sets (their four buffer addresses, the capacity in records), to see that
+  // apply_updates after a reserve leaves them alone
+  size_t mlgpu_graph_update_staging(mlgpu_graph* g, const void** four) { return (g && !g->job && four) ? mlgpu_updater_staging(g->updates, four) : 0; }
 
   int mlgpu_graph_set_delay_layout(mlgpu_graph* g, int windowed)
   {

@@ -12,6 +12,7 @@
 
 #include "../../include/mlgpu.h"
 #include "mlgpu_device_args.hpp"
+#include "param_updates.hpp"
 
 // Owning device memory, pinned host memory and HIP events: every handle frees what it holds by deleting its members
 struct DeviceFree
@@ -197,6 +198,31 @@ bool mlgpu_jit_compile_only(const std::string& source, std::string& log);  // hi
 hipFunction_t mlgpu_jit_function(int device, const std::string& source, const char* name, std::string& log, bool* loaded = nullptr);
 hipError_t mlgpu_jit_launch(hipFunction_t fn, void* args, size_t argBytes, size_t V, hipStream_t stream);  // blocks of 256 lanes over V
 bool mlgpu_jit_code_number(const std::vector<char>& code, const char* key, long& value);  // a number of the kernel's metadata note
+
+// updates.hip — sparse per-voice table updates (mlgpu_graph_apply_updates, mlgpu_bank_apply_updates): what a graph or a bank keeps
+// for them. `desc` describes the owner's tables to the host planner and is made by the owner (once: the tables' shape is fixed
+// when a graph is compiled / a bank created); the two staging sets take turns.
+struct mlgpu_updater
+{
+  mlupd::UpdatePlanner planner;
+  mlupd::TableDesc desc;
+  bool described{false};
+  struct Staging
+  {
+    PinnedBuffer<mlupd::DevRec> h_recs;
+    DeviceBuffer<mlupd::DevRec> d_recs;
+    size_t capacity{0};
+    OwnedEvent done;
+    bool pending{false};
+  } stage[2];
+  int idx{0};
+  size_t reserved{0};  // reserve_updates: device records per call (0: no reserve, the buffers grow inside apply)
+};
+int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRecords, std::string& err);
+size_t mlgpu_updater_device_records(mlgpu_updater& u, const mlgpu_update* recs, size_t n);
+// tables[mlupd::kTables]: the device rows of params, coefficients, state and input constants (null where the owner has none)
+int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, const mlgpu_update* recs, size_t n, std::string& err);
+size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four);  // (test hook: buffer addresses and capacity)
 
 // coeffs.cpp
 void mlgpu_build_impulse_table(float* out17);

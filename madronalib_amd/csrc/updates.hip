@@ -1,0 +1,137 @@
+// updates.hip — the DEVICE half of sparse per-voice table updates, and the staging both callers share (graph.hip, capi.hip).
+//
+// param_updates.cpp turns a list of mlgpu_update records into batches of 16-byte device records none of which writes a word twice;
+// here a batch is one launch of apply_updates_kernel on the engine's stream, behind the asynchronous upload of its records from one
+// of two pinned staging sets (as mlgpu_events::Staging): the host packs into the set that is free and waits only if the call
+// before last has not finished.
+#include <string.h>
+
+#include <string>
+
+#include "mlgpu_internal.hpp"
+
+using mlupd::DevRec;
+
+namespace
+{
+struct UpdateArgs
+{
+  const uint4* recs;
+  uint32_t* tables[mlupd::kTables];  // params, coefficients, state, input constants: rows of V words each (null: the object has none)
+  size_t V;
+  uint32_t n;
+};
+
+// One wavefront per record, its lanes striding the record's voices in coalesced dword stores: the same launch serves very many
+// short ranges (100 000 instruments of 16 voices: a quarter of a wavefront's lanes each) and a few long ones (a whole row of 2^20
+// voices: 16 384 trips of one wavefront). The kernel moves a few MB at most and is bound by latency, not bandwidth. A record is
+// the same for every lane: its index goes through readfirstlane so that the record and the table's base are scalar loads.
+__global__ __launch_bounds__(256) void apply_updates_kernel(const UpdateArgs a)
+{
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (w >= a.n) return;
+  const uint4 r = a.recs[w];
+  uint32_t* __restrict__ row = a.tables[r.x >> mlupd::kRowBits] + (size_t)(r.x & mlupd::kRowMask) * a.V + r.y;
+  for (uint32_t i = threadIdx.x & 63u; i < r.z; i += 64u) row[i] = r.w;
+}
+}  // namespace
+
+static int ufail(std::string& err, int status, const std::string& what)
+{
+  err = what;
+  return status;
+}
+
+// One batch is one launch of a 1-D grid of a wavefront per record, and a grid holds fewer than 2^32 threads: lists are held to what a
+// single launch can take, at reserve and before anything of a list is enqueued
+static constexpr size_t kMaxDeviceRecords = (size_t)1 << 25;
+
+static bool growStage(mlgpu_updater::Staging& sg, size_t need)
+{
+  if (need <= sg.capacity) return true;
+  sg.capacity = 0;
+  if (allocate(sg.d_recs, need) != hipSuccess || allocate(sg.h_recs, need) != hipSuccess) return false;
+  sg.capacity = need;
+  return true;
+}
+
+int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRecords, std::string& err)
+{
+  if (e->recording) return ufail(err, MLGPU_ERR_INVALID, "reserve_updates allocates: not while recording a sequence");
+  if (maxDeviceRecords == 0 || maxDeviceRecords > kMaxDeviceRecords) return ufail(err, MLGPU_ERR_INVALID, "reserve_updates: 1 .. 2^25 device records");
+  if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
+  // (launches that read the old buffers may be in flight)
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipStreamSynchronize");
+  for (mlgpu_updater::Staging& sg : u.stage)
+  {
+    sg.pending = false;
+    if (!sg.done && allocate(sg.done, hipEventDisableTiming) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipEventCreate");
+    if (!growStage(sg, maxDeviceRecords)) return ufail(err, MLGPU_ERR_OOM, "reserve_updates: record buffers");
+  }
+  u.planner.reserve(maxDeviceRecords);
+  u.reserved = maxDeviceRecords;
+  return MLGPU_OK;
+}
+
+size_t mlgpu_updater_device_records(mlgpu_updater& u, const mlgpu_update* recs, size_t n)
+{
+  if (!recs || !n) return 0;
+  return u.planner.validate(u.desc, recs, n) == MLGPU_OK ? u.planner.deviceRecords() : 0;
+}
+
+int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, const mlgpu_update* recs, size_t n, std::string& err)
+{
+  if (n == 0) return MLGPU_OK;
+  if (!recs) return ufail(err, MLGPU_ERR_INVALID, "apply_updates: null record list");
+  if (e->recording) return ufail(err, MLGPU_ERR_INVALID, "apply_updates reads host memory: not while recording a sequence (apply between the sequence's launches)");
+  // everything that can be refused is refused before anything is enqueued
+  const int vst = u.planner.validate(u.desc, recs, n);
+  if (vst != MLGPU_OK) return ufail(err, vst, std::string("apply_updates: ") + u.planner.error());
+  const size_t nDev = u.planner.deviceRecords();
+  if (nDev == 0) return MLGPU_OK;  // (a CLEAR of nodes without state words that clear() resets)
+  if (u.reserved && nDev > u.reserved)
+    return ufail(err, MLGPU_ERR_RANGE, "apply_updates: the list needs " + std::to_string(nDev) + " device records, reserve_updates reserved " + std::to_string(u.reserved));
+  if (nDev > kMaxDeviceRecords) return ufail(err, MLGPU_ERR_RANGE, "apply_updates: more than 2^25 device records in one list");
+  if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
+  mlgpu_updater::Staging& sg = u.stage[u.idx];
+  u.idx ^= 1;
+  if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "apply_updates: waiting for the call before last");
+  sg.pending = false;
+  if (!sg.done && allocate(sg.done, hipEventDisableTiming) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "apply_updates: hipEventCreate");
+  // after a reserve both sets hold `reserved` records and nothing is allocated here, ever; without one the buffers grow here, a
+  // setup convenience that allocates and may wait (nothing of this set is in flight: see the wait above)
+  if (!u.reserved && nDev > sg.capacity && !growStage(sg, std::max<size_t>(1024, 2 * nDev))) return ufail(err, MLGPU_ERR_OOM, "apply_updates: record buffers");
+  u.planner.pack(u.desc, recs, n, sg.h_recs.get());
+  hipError_t herr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(DevRec) * nDev, hipMemcpyHostToDevice, e->stream);
+  UpdateArgs a;
+  for (uint32_t t = 0; t < mlupd::kTables; ++t) a.tables[t] = tables[t];
+  a.V = u.desc.V;
+  size_t begin = 0;
+  for (size_t b = 0; b < u.planner.batches() && herr == hipSuccess; ++b)
+  {
+    const size_t end = u.planner.batchEnd(b);
+    a.recs = (const uint4*)(sg.d_recs.get() + begin);
+    a.n = (uint32_t)(end - begin);
+    hipLaunchKernelGGL(apply_updates_kernel, dim3(a.n / 4u + (a.n % 4u ? 1u : 0u)), dim3(256), 0, e->stream, a);
+    herr = hipGetLastError();
+    begin = end;
+  }
+  // (whatever was enqueued reads this set: the event goes in even after a failed launch)
+  if (hipEventRecord(sg.done.get(), e->stream) == hipSuccess)
+    sg.pending = true;
+  else
+    hipStreamSynchronize(e->stream);
+  if (herr != hipSuccess) return ufail(err, MLGPU_ERR_HIP, std::string("apply_updates: ") + hipGetErrorString(herr));
+  return MLGPU_OK;
+}
+
+// what the tests look at: the staging buffers' addresses {host 0, device 0, host 1, device 1} and the smaller capacity, in records
+size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four)
+{
+  for (int i = 0; i < 2; ++i)
+  {
+    four[2 * i] = u.stage[i].h_recs.get();
+    four[2 * i + 1] = u.stage[i].d_recs.get();
+  }
+  return std::min(u.stage[0].capacity, u.stage[1].capacity);
+}
