@@ -757,8 +757,15 @@ int mlgpu_graph_process_ctl(mlgpu_graph* g, size_t n_vectors, const float* const
  *
  * MLGPU_UPDATE_CLEAR is T::clear() for those voices only: expanded on the host into one device record per state word clear()
  * resets (mlgpu_graph_clear_proc's words; a feedback node's stored vector becomes zeros). A node with delay rings is refused with
- * MLGPU_ERR_UNSUPPORTED (node = -1 in a graph that has one, too). The graph's DSPVector count that pairs the vectors of
+ * MLGPU_ERR_UNSUPPORTED (node = -1 in a graph that has one, too): its rings cost their length, not a few words, and are cleared
+ * only where the host asks for that - MLGPU_UPDATE_CLEAR_RINGS. The graph's DSPVector count that pairs the vectors of
  * DOWNSAMPLE_2X regions is per graph, not per voice: mlgpu_graph_clear resets it, a CLEAR record does not.
+ *
+ * MLGPU_UPDATE_CLEAR_RINGS is CLEAR plus zeros to every delay ring of the node for those voices - IntegerDelay::clear()'s
+ * std::fill of one voice's buffer, what a stolen voice of a plucked-string or reverb bank needs (node = -1: every processor and
+ * feedback node, rings included). The write index and every other word clear() leaves alone stay. The zeros are written by a
+ * second small kernel (at most one launch per call, from the same record upload), whose work is the ring length: one second of
+ * delay is 256 KiB per voice. On a node without rings, and on a bank (banks have none), it is exactly CLEAR.
  *
  * Everything is validated before anything is enqueued; a refused list changes no table word and the error text names the record's
  * position. MLGPU_ERR_INVALID: a node of the wrong type, n_voices == 0, an unknown target, INPUT_CONST on a graph, PARAM on a bank,
@@ -768,7 +775,8 @@ int mlgpu_graph_process_ctl(mlgpu_graph* g, size_t n_vectors, const float* const
  *
  * mlgpu_*_reserve_updates(max_device_records) is setup (it allocates and waits): from then on apply_updates never allocates and
  * refuses a list that costs more (mlgpu_graph_update_device_records says what a list costs: one per record, a CLEAR one per cleared
- * state word; 0 for a list that would be refused). Without a reserve the buffers grow inside the call: a setup convenience that
+ * state word, a CLEAR_RINGS those plus two per ring node and segment of the voice range - one segment in delay layout 0, one per
+ * 256-voice block the range touches in the others; 0 for a list that would be refused). Without a reserve the buffers grow inside the call: a setup convenience that
  * allocates and may wait. One list holds at most 2^25 device records, reserved or not (MLGPU_ERR_INVALID / MLGPU_ERR_RANGE). */
 typedef enum mlgpu_update_target
 {
@@ -776,7 +784,8 @@ typedef enum mlgpu_update_target
   MLGPU_UPDATE_COEFF = 1,       /* graph: node = a proc node, index = coefficient slot; bank: node = processor index */
   MLGPU_UPDATE_STATE = 2,       /* graph: proc / feedback node, index = state word; bank: processor index; bits as given */
   MLGPU_UPDATE_INPUT_CONST = 3, /* bank only: the table of mlgpu_bank_set_input_const; node and index ignored */
-  MLGPU_UPDATE_CLEAR = 4        /* T::clear() of node (node = -1: every processor and feedback node) for these voices only */
+  MLGPU_UPDATE_CLEAR = 4,       /* T::clear() of node (node = -1: every processor and feedback node) for these voices only */
+  MLGPU_UPDATE_CLEAR_RINGS = MLGPU_UPDATE_CLEAR + 1 /* 5: CLEAR, and zeros to every delay ring of the node for these voices; index and bits ignored */
 } mlgpu_update_target;
 typedef struct mlgpu_update
 {

@@ -855,6 +855,12 @@ class Update(ctypes.Structure):  # mlgpu_update
         """T::clear() of `node` (-1: every processor and feedback node) for these voices only."""
         return cls(int(node), UpdateTarget.CLEAR, 0, int(first_voice), int(n_voices), 0)
 
+    @classmethod
+    def clear_rings(cls, node, first_voice, n_voices):
+        """clear(), and zeros to every delay ring of `node` for these voices: the work is the ring length per voice. A node without
+        rings, and a bank's processor: exactly clear()."""
+        return cls(int(node), UpdateTarget.CLEAR_RINGS, 0, int(first_voice), int(n_voices), 0)
+
 
 def _update_array(records):
     """records: a ctypes array of Update (used as it is) or a sequence of Update."""

@@ -23,8 +23,12 @@ class Layout:
     BROADCAST = 3    # [S] one voice's stream read by every voice (inputs only)
 
 
-class UpdateTarget:   # mlgpu_update_target: what a record of Graph.apply_updates / Bank.apply_updates writes
-    PARAM = 0
+class _RingTargets:   # the targets of mlgpu_update_target that write delay-ring memory beside the tables
+    CLEAR_RINGS = 5   # MLGPU_UPDATE_CLEAR + 1
+
+
+class UpdateTarget(_RingTargets):   # mlgpu_update_target: what a record of Graph.apply_updates / Bank.apply_updates writes
+    PARAM = 0         # (its own attributes are the five targets that write table words only)
     COEFF = 1
     STATE = 2
     INPUT_CONST = 3

@@ -1017,6 +1017,11 @@ extern "C"
     if (u.described) return MLGPU_OK;
     u.desc.bank = false;
     u.desc.V = g->desc.V;
+    // where a voice's ring words lie (MLGPU_UPDATE_CLEAR_RINGS): the layout's granule, and the spare lanes of ring layout 2
+    const GraphPlan& plan = g->build->plan;
+    u.desc.ringGranule = plan.rings == RingLayout::ROWS ? 1u : plan.rings == RingLayout::TRANSPOSED ? 16u : 8u;
+    u.desc.memVoices = plan.memVoices;
+    u.desc.spareLanes = plan.rings == RingLayout::TRANSPOSED && plan.totalRings && (g->desc.V % 64) != 0;
     u.desc.nodes.assign(g->desc.nodes.size(), mlupd::NodeDesc());
     for (size_t i = 0; i < g->desc.nodes.size(); ++i)
     {
@@ -1043,6 +1048,8 @@ extern "C"
         nd.sOff = n.sOff;
         nd.ns = n.ns;
         nd.rings = n.ringLen != 0 || mlgpu_proc_rings(n.kind) > 0;
+        nd.memOff = plan.nodes[i].memOff;
+        nd.ringWords = (uint64_t)n.ringLen * (uint64_t)mlgpu_proc_rings(n.kind);
         uint32_t words[MLGPU_MAX_PROC_STATE];
         mlgpu_proc_clear_state(n.kind, words, true);
         const uint64_t mask = mlgpu_proc_clear_mask(n.kind);
@@ -1071,7 +1078,7 @@ extern "C"
     if (const int st = updatesReady(g, "graph_apply_updates")) return st;
     uint32_t* const tables[mlupd::kTables] = {(uint32_t*)g->d_params.get(), (uint32_t*)g->d_coeffs.get(), g->d_state.get(), nullptr};
     std::string err;
-    const int st = mlgpu_updater_apply(g->e, g->updates, tables, recs, n, err);
+    const int st = mlgpu_updater_apply(g->e, g->updates, tables, (uint32_t*)g->d_mem.get(), g->build->plan.memVoices * g->build->plan.memFloatsPerVoice, recs, n, err);
     return st == MLGPU_OK ? st : gfail(g, st, "graph_" + err);
   }
   // Not in mlgpu.h: the tests' view of the staging sets (their four buffer addresses, the capacity in records), to see that

@@ -220,8 +220,10 @@ struct mlgpu_updater
 };
 int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRecords, std::string& err);
 size_t mlgpu_updater_device_records(mlgpu_updater& u, const mlgpu_update* recs, size_t n);
-// tables[mlupd::kTables]: the device rows of params, coefficients, state and input constants (null where the owner has none)
-int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, const mlgpu_update* recs, size_t n, std::string& err);
+// tables[mlupd::kTables]: the device rows of params, coefficients, state and input constants (null where the owner has none);
+// ringMem[ringMemWords]: a graph's delay-ring memory (null: none, and desc says so)
+int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, uint32_t* ringMem, size_t ringMemWords, const mlgpu_update* recs, size_t n,
+                        std::string& err);
 size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four);  // (test hook: buffer addresses and capacity)
 
 // coeffs.cpp

@@ -3,14 +3,17 @@
 // param_updates.cpp turns a list of mlgpu_update records into batches of 16-byte device records none of which writes a word twice;
 // here a batch is one launch of apply_updates_kernel on the engine's stream, behind the asynchronous upload of its records from one
 // of two pinned staging sets (as mlgpu_events::Staging): the host packs into the set that is free and waits only if the call
-// before last has not finished.
+// before last has not finished. The ring records of MLGPU_UPDATE_CLEAR_RINGS lie behind the table records in the same upload and
+// are one launch of clear_rings_kernel.
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 
 #include "mlgpu_internal.hpp"
 
 using mlupd::DevRec;
+using mlupd::RingRec;
 
 namespace
 {
@@ -33,6 +36,62 @@ __global__ __launch_bounds__(256) void apply_updates_kernel(const UpdateArgs a)
   const uint4 r = a.recs[w];
   uint32_t* __restrict__ row = a.tables[r.x >> mlupd::kRowBits] + (size_t)(r.x & mlupd::kRowMask) * a.V + r.y;
   for (uint32_t i = threadIdx.x & 63u; i < r.z; i += 64u) row[i] = r.w;
+}
+
+struct RingClearArgs
+{
+  const uint4* recs;  // two per record (mlupd::RingRec)
+  uint32_t* mem;      // the graph's ring memory ...
+  uint64_t memWords;  // ... and its size: nothing is stored beyond it
+  uint32_t wide;      // the ring layout's granule is 8 words or more: spans are 16-byte aligned multiples of 16 bytes
+};
+
+// Zeros to the strided spans of one ring record: `rows` spans of `span` words, `stride` words apart. The lanes of a wavefront go
+// over the flattened (row, place in the span) space, so that one voice's clear - spans of 8 words in ring layout 4, of 1 word in
+// layout 0 - keeps all 64 busy; a lane's store is W words (16 bytes where the layout's granule allows, a dword in layout 0). A
+// record is cut into slabs of 16 KiB of stores, one per wavefront at a time: grid.x is the record, grid.y * 4 wavefronts stride
+// its slabs, and a wavefront with no slab left (a short record next to a long one) leaves - every test on the way is wave-uniform.
+// Offsets are 64-bit: a graph's ring memory can exceed 4 GiB.
+constexpr uint32_t kSlabWords = 4096;
+
+template <int W>
+__device__ __forceinline__ void clear_ring_slabs(const RingClearArgs& a, uint64_t offset, uint32_t span, uint32_t stride, uint32_t rows, uint32_t wave)
+{
+  constexpr uint32_t kSlab = kSlabWords / W;  // stores per slab
+  const uint32_t perSpan = span / W;
+  if (!perSpan) return;
+  const uint64_t stores = (uint64_t)rows * perSpan;
+  const uint64_t nSlabs = (stores + kSlab - 1) / kSlab;
+  for (uint64_t slab = (uint64_t)blockIdx.y * 4u + wave; slab < nSlabs; slab += (uint64_t)gridDim.y * 4u)
+  {
+    // the slab's first store: its row once per slab in 64 bits, every store's row from there in 32 (perSpan + kSlab fits easily)
+    const uint64_t s0 = slab * kSlab, row0 = s0 / perSpan;
+    const uint32_t rem0 = (uint32_t)(s0 - row0 * perSpan);
+    const uint32_t count = (uint32_t)(stores - s0 < kSlab ? stores - s0 : kSlab);
+    const uint64_t base = offset + row0 * stride;
+    for (uint32_t j = threadIdx.x & 63u; j < count; j += 64u)
+    {
+      const uint32_t t = rem0 + j, r = t / perSpan, p = t - r * perSpan;
+      const uint64_t at = base + (uint64_t)r * stride + (uint64_t)p * W;
+      if (at + W > a.memWords) continue;
+      if (W == 4)
+        *(uint4*)(a.mem + at) = make_uint4(0u, 0u, 0u, 0u);
+      else
+        a.mem[at] = 0u;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void clear_rings_kernel(const RingClearArgs a)
+{
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t rec = (uint32_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x);
+  const uint4 lo = a.recs[2u * rec], hi = a.recs[2u * rec + 1u];  // {offset lo, offset hi, span, stride}, {rows, -, -, -}
+  const uint64_t offset = ((uint64_t)lo.y << 32) | lo.x;
+  if (a.wide)
+    clear_ring_slabs<4>(a, offset, lo.z, lo.w, hi.x, wave);
+  else
+    clear_ring_slabs<1>(a, offset, lo.z, lo.w, hi.x, wave);
 }
 }  // namespace
 
@@ -79,7 +138,8 @@ size_t mlgpu_updater_device_records(mlgpu_updater& u, const mlgpu_update* recs, 
   return u.planner.validate(u.desc, recs, n) == MLGPU_OK ? u.planner.deviceRecords() : 0;
 }
 
-int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, const mlgpu_update* recs, size_t n, std::string& err)
+int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, uint32_t* ringMem, size_t ringMemWords, const mlgpu_update* recs, size_t n,
+                        std::string& err)
 {
   if (n == 0) return MLGPU_OK;
   if (!recs) return ufail(err, MLGPU_ERR_INVALID, "apply_updates: null record list");
@@ -87,11 +147,12 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
   // everything that can be refused is refused before anything is enqueued
   const int vst = u.planner.validate(u.desc, recs, n);
   if (vst != MLGPU_OK) return ufail(err, vst, std::string("apply_updates: ") + u.planner.error());
-  const size_t nDev = u.planner.deviceRecords();
+  const size_t nDev = u.planner.deviceRecords(), nTable = u.planner.tableRecords(), nRing = u.planner.ringRecords();
+  if (nRing && !ringMem) return ufail(err, MLGPU_ERR_INVALID, "apply_updates: ring records without ring memory");
   if (nDev == 0) return MLGPU_OK;  // (a CLEAR of nodes without state words that clear() resets)
   if (u.reserved && nDev > u.reserved)
     return ufail(err, MLGPU_ERR_RANGE, "apply_updates: the list needs " + std::to_string(nDev) + " device records, reserve_updates reserved " + std::to_string(u.reserved));
-  if (nDev > kMaxDeviceRecords) return ufail(err, MLGPU_ERR_RANGE, "apply_updates: more than 2^25 device records in one list");
+  if (nDev > kMaxDeviceRecords || nRing >= kMaxDeviceRecords / 2) return ufail(err, MLGPU_ERR_RANGE, "apply_updates: more than 2^25 device records in one list");
   if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
   mlgpu_updater::Staging& sg = u.stage[u.idx];
   u.idx ^= 1;
@@ -115,6 +176,26 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
     hipLaunchKernelGGL(apply_updates_kernel, dim3(a.n / 4u + (a.n % 4u ? 1u : 0u)), dim3(256), 0, e->stream, a);
     herr = hipGetLastError();
     begin = end;
+  }
+  if (nRing && herr == hipSuccess)
+  {
+    // grid.y: enough wavefronts for the longest record's slabs, within a million workgroups in all (the rest is the kernel's loop)
+    const uint32_t wordsPerStore = u.desc.ringGranule >= 8 ? 4u : 1u, slab = kSlabWords / wordsPerStore;
+    uint64_t slabs = 1;
+    for (size_t i = 0; i < nRing; ++i)
+    {
+      RingRec rr;
+      memcpy(&rr, sg.h_recs.get() + nTable + 2 * i, sizeof(rr));
+      slabs = std::max<uint64_t>(slabs, ((uint64_t)rr.rows * (rr.span / wordsPerStore) + slab - 1) / slab);
+    }
+    const uint64_t y = std::max<uint64_t>(1, std::min<uint64_t>({(slabs + 3) / 4, (uint64_t)65535, ((uint64_t)1 << 20) / nRing}));
+    RingClearArgs ra;
+    ra.recs = (const uint4*)(sg.d_recs.get() + nTable);
+    ra.mem = ringMem;
+    ra.memWords = ringMemWords;
+    ra.wide = wordsPerStore == 4u;
+    hipLaunchKernelGGL(clear_rings_kernel, dim3((uint32_t)nRing, (uint32_t)y), dim3(256), 0, e->stream, ra);
+    herr = hipGetLastError();
   }
   // (whatever was enqueued reads this set: the event goes in even after a failed launch)
   if (hipEventRecord(sg.done.get(), e->stream) == hipSuccess)
