@@ -481,6 +481,8 @@ int mlgpu_bank_set_state_uniform(mlgpu_bank* b, int proc_idx, int state_idx, uin
 /* Bank input when no signal is streamed: voice v's processor 0 sees DSPVector(h[v])
  * (the implicit float->DSPVector broadcast, MLDSPOps.h:157), e.g. a per-voice freq. */
 int mlgpu_bank_set_input_const(mlgpu_bank* b, const float* h_per_voice);
+/* ... and read back (it changes under mlgpu_bank_apply_updates' MLGPU_UPDATE_INPUT_CONST records); waits for the stream. */
+int mlgpu_bank_get_input_const(mlgpu_bank* b, float* h_per_voice);
 
 /* Process n_vectors DSPVectors for every voice.
  *   d_in   input signal in `in_layout`, or NULL to use the per-voice input constant.
@@ -509,6 +511,51 @@ int mlgpu_bank_process(mlgpu_bank* b, size_t n_vectors, const float* d_in, int i
  * mlgpu_mixdown_groups), or is built as a graph (mlgpu_graph_set_input_group / mlgpu_graph_set_output_group_sum). */
 int mlgpu_bank_process_groups(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
                               const float* d_gains, int out_group, float* d_out, int out_layout);
+/* VOICE LISTS: run only the listed voices of a bank - the sounding voices of an instrument bank most of whose slots are idle. The cost
+ * of a listed call goes with the list's length, not with the bank's size.
+ * One rule: with the list L[0 .. K) - voice indices, strictly ascending, all below n_voices - a listed process call behaves exactly as
+ * a bank of K voices made of voices L[0] ... L[K-1], in that order.
+ *   What belongs to a voice is addressed by its voice index L[i]: coefficient and state rows, the input constant, the streamed input
+ *   d_in - still a signal of n_voices rows in `in_layout` as mlgpu_bank_process takes it, lane i reads row L[i]
+ *   (MLGPU_LAYOUT_BROADCAST as there) - and the per-voice gains d_gains[n_voices].
+ *   What the call produces is addressed by list position i: d_out is a signal of K rows in `out_layout` (64 * n_vectors * K floats);
+ *   the mixdown tree is that of a K-voice bank (pairwise inside 64 consecutive list positions, then mlgpu_mixdown's later stages over
+ *   ceil(K / 64) rows); the peaks are d_peak[K].
+ *   Unlisted voices are neither read nor written: every coefficient, state and input-constant word of theirs holds the same bits after
+ *   the call, and no time passes for them (phases and envelopes stay where they are).
+ *   Any split of n_vectors into several listed launches with the same list gives the bits of one launch.
+ * The list must be ascending because lane i gathers its voice's table words and input quads at index L[i]: ascending indices keep a
+ * wavefront's 4-byte table loads and 16-byte input loads nearly coalesced.
+ *
+ * mlgpu_bank_set_voice_list takes HOST memory and follows the discipline of mlgpu_bank_apply_updates: the list is validated completely
+ * before anything is enqueued (a refused list leaves the previous one in force), copied to the device on the engine's stream - ordered
+ * between the process calls and apply_updates calls around it - and the call never waits for the device except for its own call before
+ * last (two pinned staging sets take turns). After mlgpu_bank_reserve_voice_list(max_listed) it never allocates; without a reserve the
+ * buffers grow inside the call, a setup convenience that allocates and may wait. n == 0 is a valid, empty list; a new bank has the
+ * empty list. MLGPU_ERR_INVALID: not strictly ascending (the message names the position), a null list, a call while recording a
+ * sequence (it reads host memory). MLGPU_ERR_RANGE: an index >= n_voices (with its position), more entries than reserved.
+ * mlgpu_bank_voice_list_size: the length of the list set last.
+ *
+ * mlgpu_bank_process_listed / _listed_mixdown: mlgpu_bank_process / mlgpu_bank_process_mixdown of the listed voices. They never
+ * allocate and can be recorded into a sequence: a recorded launch reads whichever list is on the device when it runs, but its K is
+ * fixed when it is recorded, so the list must keep its length between replays (its contents may change). _listed_mixdown needs the
+ * same mlgpu_mixdown_reserve as mlgpu_bank_process_mixdown, for K voices (MLGPU_ERR_INVALID without). With an empty list
+ * _process_listed launches nothing and _listed_mixdown writes +0.0 to the 64 * n_vectors floats of d_out.
+ *   d_peak  NULL, or K words: d_peak[i] = the maximum over all samples of the launch of (bits(y) & 0x7fffffff) as an unsigned integer,
+ *           y voice L[i]'s own output sample - the float mlgpu_bank_process_listed stores, before any gain in the mixdown form. An
+ *           integer maximum is exact and the same in both floating-point modes, and a NaN anywhere in the launch shows as a value
+ *           above 0x7f800000. Written once per launch, not accumulated across launches: a released voice whose peak stays below a
+ *           threshold has died away and can leave the list.
+ * MLGPU_ERR_UNSUPPORTED, with nothing launched and the state untouched, as mlgpu_bank_process_groups: a bank that is not one of the
+ * ahead-of-time chain kernels (processor by processor, an SVF cascade form, generated at run time); for _listed_mixdown also a chain
+ * without an ahead-of-time summing form. */
+int mlgpu_bank_reserve_voice_list(mlgpu_bank* b, size_t max_listed);
+int mlgpu_bank_set_voice_list(mlgpu_bank* b, const uint32_t* h_voices, size_t n);
+size_t mlgpu_bank_voice_list_size(mlgpu_bank* b);
+int mlgpu_bank_process_listed(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout,
+                              float* d_out, int out_layout, uint32_t* d_peak);
+int mlgpu_bank_process_listed_mixdown(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout,
+                                      const float* d_gains, float* d_out, uint32_t* d_peak);
 /* 1 if the chain maps to a single fused kernel, 0 if it runs processor by processor. */
 int mlgpu_bank_is_fused(mlgpu_bank* b);
 /* Name of the device kernel that dominates mlgpu_bank_process (for profile lookup). */

@@ -958,6 +958,11 @@ class Bank(_Handle):
         assert v.shape == (self.V,)
         self.engine._check(self.L.mlgpu_bank_set_input_const(self.h, _np_ptr(v)))
 
+    def get_input_const(self):
+        out = np.empty(self.V, np.float32)
+        self.engine._check(self.L.mlgpu_bank_get_input_const(self.h, _np_ptr(out)))
+        return out
+
     def reserve_updates(self, max_device_records):
         """Setup: from now on apply_updates never allocates, and refuses (Status.ERR_RANGE) a list that needs more device records."""
         self.engine._check(self.L.mlgpu_bank_reserve_updates(self.h, int(max_device_records)))
@@ -1005,6 +1010,39 @@ class Bank(_Handle):
         pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
         self.engine._check(self.L.mlgpu_bank_process_groups(self.h, int(n_vectors), pin, int(in_layout), int(in_group), pg, int(out_group), pout,
                                                             int(out_layout)))
+
+    def reserve_voice_list(self, max_listed):
+        """Setup: from now on set_voice_list never allocates, and refuses (Status.ERR_RANGE) a longer list."""
+        self.engine._check(self.L.mlgpu_bank_reserve_voice_list(self.h, int(max_listed)))
+
+    def set_voice_list(self, indices):
+        """The voices the listed process calls run: strictly ascending indices below V (empty: none). Copied to the device on the
+        engine's stream, ordered between the calls around it; does not wait for the device (mlgpu_bank_set_voice_list)."""
+        v = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self.engine._check(self.L.mlgpu_bank_set_voice_list(self.h, _np_ptr(v) if v.size else None, v.size))
+
+    @property
+    def voice_list_size(self):
+        return int(self.L.mlgpu_bank_voice_list_size(self.h))
+
+    def process_listed(self, n_vectors, d_out, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, d_peak=None):
+        """process of the listed voices only, as a bank of K = voice_list_size voices in list order: d_out has K rows, d_in (if any)
+        still V rows of which lane i reads row list[i], d_peak (if any) gets K uint32 words, the largest bits(y) & 0x7fffffff of each
+        voice in this launch. Unlisted voices are neither read nor written (mlgpu_bank_process_listed)."""
+        pin = None if d_in is None else ctypes.c_void_p(d_in.ptr if hasattr(d_in, "ptr") else int(d_in))
+        pout = ctypes.c_void_p(d_out.ptr if hasattr(d_out, "ptr") else int(d_out))
+        pp = None if d_peak is None else ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
+        self.engine._check(self.L.mlgpu_bank_process_listed(self.h, int(n_vectors), pin, int(in_layout), pout, int(out_layout), pp))
+
+    def process_listed_mixdown(self, n_vectors, d_out, d_in=None, in_layout=Layout.QUAD, d_gains=None, d_peak=None):
+        """process_mixdown of the listed voices only: d_out gets the 64 * n_vectors samples of the K-voice mixdown tree over the list
+        positions, d_gains [V] is indexed by voice, d_peak [K] by list position and taken before the gain
+        (mlgpu_bank_process_listed_mixdown)."""
+        pin = None if d_in is None else ctypes.c_void_p(d_in.ptr if hasattr(d_in, "ptr") else int(d_in))
+        pout = ctypes.c_void_p(d_out.ptr if hasattr(d_out, "ptr") else int(d_out))
+        pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
+        pp = None if d_peak is None else ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
+        self.engine._check(self.L.mlgpu_bank_process_listed_mixdown(self.h, int(n_vectors), pin, int(in_layout), pg, pout, pp))
 
     def process_groups_host(self, n_vectors, out_group, in_signal=None, in_group=1, gains=None, layout=Layout.QUAD, in_layout=None):
         """Test convenience beside process_host: in_signal [V / in_group][64T] and the result [V / out_group][64T] are VOICE_MAJOR

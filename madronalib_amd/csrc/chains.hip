@@ -41,6 +41,23 @@ hipError_t launchChainMix(const ChainArgs& a, hipStream_t stream, int /*cuCount*
   return hipGetLastError();
 }
 
+// the voice-list forms (mlgpu_bank_process_listed, _listed_mixdown): a.V is the list's length
+template <bool HAS_SIGNAL, int... KS>
+hipError_t launchChainListed(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
+{
+  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
+  hipLaunchKernelGGL((chain_listed_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
+  return hipGetLastError();
+}
+
+template <bool HAS_SIGNAL, int... KS>
+hipError_t launchChainListedMix(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
+{
+  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
+  hipLaunchKernelGGL((chain_listed_mix_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
+  return hipGetLastError();
+}
+
 // the group form (mlgpu_bank_process_groups): outGroup picks the instantiation, a.inGroupShift and a.mixGains travel as arguments
 template <bool HAS_SIGNAL, int... KS>
 hipError_t launchChainGroups(const ChainArgs& a, int outGroup, hipStream_t stream)
@@ -156,6 +173,8 @@ ChainEntry makeEntry(const char* name)
   e.launchConst = &launchChain<false, KS...>;
   e.launchGroupsSignal = &launchChainGroups<true, KS...>;
   e.launchGroupsConst = &launchChainGroups<false, KS...>;
+  e.launchListedSignal = &launchChainListed<true, KS...>;
+  e.launchListedConst = &launchChainListed<false, KS...>;
   // what a profiler prints for this kernel: "chain_kernel<mldev::Chain<2, 18, 48>, false>(ChainArgs)";
   // `name` is the human-readable alias used in logs.
   static const std::string profName = [] {
@@ -178,6 +197,8 @@ ChainEntry makeMixEntry(const char* name)
   ChainEntry e = makeEntry<KS...>(name);
   e.launchMixSignal = &launchChainMix<true, KS...>;
   e.launchMixConst = &launchChainMix<false, KS...>;
+  e.launchListedMixSignal = &launchChainListedMix<true, KS...>;
+  e.launchListedMixConst = &launchChainListedMix<false, KS...>;
   return e;
 }
 

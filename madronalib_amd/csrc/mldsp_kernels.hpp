@@ -81,11 +81,16 @@ struct MixStrips<true>
 // the streaming loop of one voice: T DSPVectors, 16 quads each, one 16-byte access per quad
 // (SCALED: the summing form with per-voice gains and / or spare lanes in the wavefront - a loop of its own, so that the plain one
 // pays nothing for them)
-template <class CH, bool HAS_SIGNAL, bool FAST_HEAD, bool MIX = false, bool SCALED = false>
-__device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip = nullptr, bool live = true)
+// (LISTED: the voice-list forms - what belongs to the voice, its gain and its input row, is at voice vs, what the launch produces at
+// the lane's list position v; *peak gets the largest bits(y) & 0x7fffffff of the launch, y before any gain, kept in a register)
+template <class CH, bool HAS_SIGNAL, bool FAST_HEAD, bool MIX = false, bool SCALED = false, bool LISTED = false>
+__device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip = nullptr, bool live = true, size_t vs = 0,
+                                          uint32_t* peak = nullptr)
 {
-  const float mixGain = (SCALED && a.mixGains) ? a.mixGains[v] : 1.f;
-  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + v * a.in.strideV : nullptr;
+  const size_t vin = LISTED ? vs : v;
+  uint32_t pk = 0;
+  const float mixGain = (SCALED && a.mixGains) ? a.mixGains[vin] : 1.f;
+  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + vin * a.in.strideV : nullptr;
   f32x4* pout = MIX ? nullptr : (f32x4*)a.out.base + v * a.out.strideV;
   const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
   const uint32_t slot = wave_slot();
@@ -104,6 +109,12 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
       y.y = ch.template next_head<FAST_HEAD>(x.y);
       y.z = ch.template next_head<FAST_HEAD>(x.z);
       y.w = ch.template next_head<FAST_HEAD>(x.w);
+      if constexpr (LISTED)
+      {
+        const uint32_t m0 = f2u(y.x) & 0x7fffffffu, m1 = f2u(y.y) & 0x7fffffffu, m2 = f2u(y.z) & 0x7fffffffu, m3 = f2u(y.w) & 0x7fffffffu;
+        const uint32_t m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3, m = m01 > m23 ? m01 : m23;
+        pk = pk > m ? pk : m;
+      }
       if constexpr (MIX)
       {
         if constexpr (SCALED)
@@ -125,6 +136,7 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
     }
     ch.end_vector();
   }
+  if constexpr (LISTED) *peak = pk;
 }
 
 // ---- groups of adjacent voices inside the voice kernel (chain_group_kernel) ----
@@ -207,10 +219,16 @@ __device__ __forceinline__ void run_voice_groups(CH& ch, const ChainArgs& a, siz
 }
 
 // OUT_G != 0: the group form (chain_group_kernel)
-template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0>
+// LISTED: the voice-list forms (chain_listed_kernel, chain_listed_mix_kernel). The launch is a bank of a.V lanes: lane i - its place
+// from block and thread exactly as below, XCD remap included - runs voice vs = a.voiceList[i] of a bank of a.tableStride voices.
+// Coefficients, state, the input constant, the gain and the streamed input row are the voice's (vs); the output row, the mix row and
+// the peak are the lane's (i). The list is ascending, which is what keeps the gathered 4-byte table loads and 16-byte input loads
+// of a wavefront nearly coalesced: 64 ascending voices touch at most as many cache lines as they span, each once.
+template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0, bool LISTED = false>
 __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
 {
   static_assert(!(MIX && OUT_G), "one summing form at a time");
+  static_assert(!(LISTED && OUT_G), "no group form of a voice list");
   apply_fp_mode(a.flags);
   __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
   float* const strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
@@ -239,12 +257,21 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   else if (v >= a.V)
     return;
 
+  // (a spare lane of the listed mix form has taken the list's last position above: it runs the list's last voice again)
+  size_t vs = v, stride = a.V;
+  if constexpr (LISTED)
+  {
+    vs = a.voiceList[v];
+    stride = a.tableStride;
+  }
+  uint32_t pk = 0;
+
   CH ch;
-  const VoiceMem mem{a.coeffs + v, a.state + v, a.V};
+  const VoiceMem mem{a.coeffs + vs, a.state + vs, stride};
   const KernelTables tables{ldsTable};
   ch.load(mem, tables);
 
-  const float xc = (!HAS_SIGNAL && a.inConst) ? a.inConst[v] : 0.f;
+  const float xc = (!HAS_SIGNAL && a.inConst) ? a.inConst[vs] : 0.f;
 
   // A launch-constant input lets the head processor (SawGen / PulseGen) skip its per-sample
   // range test: decide once per wavefront which loop body to run.
@@ -270,20 +297,27 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
     if (scaled)
     {
       if (fastHead)
-        run_voice<CH, HAS_SIGNAL, true, true, true>(ch, a, v, xc, strip, live);
+        run_voice<CH, HAS_SIGNAL, true, true, true, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
       else
-        run_voice<CH, HAS_SIGNAL, false, true, true>(ch, a, v, xc, strip, live);
+        run_voice<CH, HAS_SIGNAL, false, true, true, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
     }
     else if (fastHead)
-      run_voice<CH, HAS_SIGNAL, true, true>(ch, a, v, xc, strip, live);
+      run_voice<CH, HAS_SIGNAL, true, true, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
     else
-      run_voice<CH, HAS_SIGNAL, false, true>(ch, a, v, xc, strip, live);
+      run_voice<CH, HAS_SIGNAL, false, true, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
   }
   else if (fastHead)
-    run_voice<CH, HAS_SIGNAL, true, MIX>(ch, a, v, xc, strip, live);
+    run_voice<CH, HAS_SIGNAL, true, MIX, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
   else
-    run_voice<CH, HAS_SIGNAL, false, MIX>(ch, a, v, xc, strip, live);
+    run_voice<CH, HAS_SIGNAL, false, MIX, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
   ch.store(mem);
+  if constexpr (LISTED)
+  {
+    if (a.peaks != nullptr)  // (the same in all lanes: a kernel argument)
+    {
+      if (live) a.peaks[v] = pk;  // (a spare lane has no place in the list)
+    }
+  }
 }
 
 template <class CH, bool HAS_SIGNAL>
@@ -298,6 +332,18 @@ template <class CH, bool HAS_SIGNAL>
 __global__ __launch_bounds__(kChainBlock) void chain_mix_kernel(const ChainArgs a)
 {
   chain_kernel_body<CH, HAS_SIGNAL, true>(a);
+}
+
+// the voices of a list instead of all of them (mlgpu_bank_process_listed, _listed_mixdown): see chain_kernel_body's LISTED
+template <class CH, bool HAS_SIGNAL>
+__global__ __launch_bounds__(kChainBlock) void chain_listed_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, false, 0, true>(a);
+}
+template <class CH, bool HAS_SIGNAL>
+__global__ __launch_bounds__(kChainBlock) void chain_listed_mix_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, true, 0, true>(a);
 }
 
 // the same voices in groups: input row v >> a.inGroupShift, one output channel per OUT_G adjacent voices (see run_voice_groups);

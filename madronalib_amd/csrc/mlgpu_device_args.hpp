@@ -41,6 +41,12 @@ struct ChainArgs
   // chain_group_kernel (which scales by mixGains too, before its group sums): voice v reads row v >> inGroupShift of `in`, and
   // `out` is a signal of V / OUT_G channels; else unused
   uint32_t inGroupShift = 0;
+  // chain_listed_kernel / chain_listed_mix_kernel (mlgpu_bank_process_listed): lane i of the launch runs voice voiceList[i] of a
+  // bank of tableStride voices - V is then the list's length, coeffs / state / inConst / in / mixGains are read at the voice, out /
+  // mix / peaks written at i; peaks[i] (or nullptr) gets the largest |sample| bit pattern of the launch. Else unused.
+  const uint32_t* voiceList = nullptr;
+  size_t tableStride = 0;
+  uint32_t* peaks = nullptr;
 };
 
 // EventsToSignals settings the device needs (events.hip, mldsp_events.hpp)

@@ -141,6 +141,8 @@ struct ChainEntry
   ChainLauncher launchConst;   // per-voice constant (or no) input
   ChainLauncher launchMixSignal{nullptr}, launchMixConst{nullptr};  // chain_mix_kernel (the voices' sum instead of their signals), where instantiated
   ChainGroupLauncher launchGroupsSignal{nullptr}, launchGroupsConst{nullptr};  // chain_group_kernel (voices in groups of 1, 2, 4, 8, 16): the chain kernels, not the cascades
+  // chain_listed_kernel / chain_listed_mix_kernel (the voices of a list): where chain_group_kernel / chain_mix_kernel are
+  ChainLauncher launchListedSignal{nullptr}, launchListedConst{nullptr}, launchListedMixSignal{nullptr}, launchListedMixConst{nullptr};
   const char* kernelName;  // prefix of the name a profiler shows for the device kernel
   const char* (*kernelNameFor)(size_t V, uint32_t flags){nullptr};  // where the kernel depends on the bank's size (SVF cascades)
   const char* alias;       // e.g. "chain_kernel<SawGen,Bandpass,Gain>"
