@@ -891,9 +891,9 @@ struct mlgpu_events
   // launch (a few hundred of 262 144: the list goes up in kilobytes where a start offset per lane was a megabyte over PCIe
   // every block), and a kernel that consumed a lane's records puts the {0, 0} back.
   DeviceBuffer<uint2> d_recRange;
-  // Two sets of upload buffers (pinned host + device): the records of launch k + 1 are routed and copied while the kernel of
-  // launch k still runs; a set is reused only after the launch that read it has finished (its event).
-  struct Staging
+  // Two sets of upload buffers (pinned host + device) that take turns ("Staging turns"): the records of launch
+  // k + 1 are routed and copied while the kernel of launch k still runs.
+  struct StagingSet
   {
     PinnedBuffer<Rec> h_recs;
     DeviceBuffer<Rec> d_recs;
@@ -901,15 +901,14 @@ struct mlgpu_events
     DeviceBuffer<LaneRange> d_dirty;
     size_t recCapacity{0}, dirtyCapacity{0};
     size_t nDirtySet{0};       // lanes whose range set_rec_ranges_kernel has set for the block in flight and no kernel has consumed yet
-    OwnedEvent done;
-    bool pending{false};
-  } stage[2];
-  int stageIdx{0};
+  };
+  StagingTurns<StagingSet> stage;
+  using Staging = StagingTurns<StagingSet>::Slot;  // a set and its turn
   // watched controllers (mlgpu_events_watch_controllers): lane = slot * nInstruments + instrument
   size_t ctlMaxVectors{0}, ctlCapacityVectors{0};  // longest launch allowed / what d_ctlOut was allocated for
   DeviceBuffer<float> d_ctlOut;
   DeviceBuffer<uint32_t> d_ctlState;
-  struct CtlStaging
+  struct CtlStaging  // ctlStage[i] rides on the turn of stage.set[i]: it has no event of its own
   {
     PinnedBuffer<CtlRec> h_recs;
     DeviceBuffer<CtlRec> d_recs;
@@ -933,17 +932,6 @@ int efail(mlgpu_events* ev, int st, const std::string& what)
 {
   if (ev && ev->e) ev->e->lastError = what;
   return st;
-}
-
-// a pinned + device pair of upload buffers, replaced by a larger one (twice the need, `least` at least) when `need` elements do not fit
-template <class T>
-bool growPair(PinnedBuffer<T>& host, DeviceBuffer<T>& dev, size_t& capacity, size_t need, size_t least)
-{
-  if (need <= capacity) return true;
-  capacity = std::max(least, 2 * need);
-  if (allocate(dev, capacity) == hipSuccess && allocate(host, capacity) == hipSuccess) return true;
-  capacity = 0;
-  return false;
 }
 
 // the settings the kernels need, from the object's
@@ -1006,11 +994,11 @@ extern "C"
     if (!ev) return MLGPU_ERR_INVALID;
     return ev->e->release(ev, "events_destroy", [](mlgpu_events* ev) {
       mlgpu_graph_forget_events(ev);  // graphs bound to this object (mlgpu_graph_bind_events) go back to "no events object"
-      for (mlgpu_events::Staging& st : ev->stage)
+      for (mlgpu_events::Staging& st : ev->stage.set)
       {
         st.h_recs.reset();
         st.h_dirty.reset();
-        st.done.reset();
+        st.turn.reset();
       }
       for (mlgpu_events::CtlStaging& st : ev->ctlStage)
       {
@@ -1049,8 +1037,8 @@ extern "C"
     if (err == hipSuccess) err = allocate(ev->d_state, (size_t)kStateWords * maxLanes);
     if (err == hipSuccess) err = allocate(ev->d_recRange, maxLanes);
     if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * maxLanes, e->stream);
-    for (mlgpu_events::Staging& st : ev->stage)
-      if (err == hipSuccess) err = allocate(st.done, hipEventDisableTiming);
+    for (mlgpu_events::Staging& st : ev->stage.set)
+      if (err == hipSuccess) err = createTurn(st.turn);
     if (err != hipSuccess)
     {
       e->lastError = std::string("events_create: ") + hipGetErrorString(err);
@@ -1122,16 +1110,15 @@ extern "C"
     return MLGPU_OK;
   }
 
-  // The controller lanes of one launch: their records uploaded into the staging set of this launch (free once the launch
-  // before last has finished, which prepare() has just waited for), then ctl_kernel on the engine's stream - ahead of the
-  // kernel that reads the signals.
+  // The controller lanes of one launch: their records uploaded into the staging set of this launch (the one that goes with the set
+  // prepare() has just taken), then ctl_kernel on the engine's stream - ahead of the kernel that reads the signals.
   static int processControllers(mlgpu_events* ev, size_t nVectors, int stageIdx, const E2SSettings& s)
   {
     mlgpu_engine* e = ev->e;
     const EventRouter& router = ev->router;
     mlgpu_events::CtlStaging& sg = ev->ctlStage[stageIdx];
     const size_t lanes = router.ctlLanes(), nRecs = router.ctlRecordCount();
-    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, 1024)) return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
+    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, std::max<size_t>(1024, 2 * (nRecs + 1)))) return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
     router.packControllers(sg.h_recs.get(), sg.h_recStart.get());
     hipError_t err = hipMemcpyAsync(sg.d_recStart.get(), sg.h_recStart.get(), sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream);
     if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream);
@@ -1155,15 +1142,17 @@ extern "C"
 
   // The per-lane record ranges are device state: set from the block's lane list, cleared by the kernel that consumes them. A block that
   // fails after they were set and before that kernel ran would leave them pointing into a staging buffer the NEXT block does not
-  // use: put them back to "no records" (stream-ordered, the list is still in sg.d_dirty).
+  // use: put them back to "no records" (stream-ordered, the list is still in sg.d_dirty). This is the way out of every block that
+  // fails once its set was taken: whatever was enqueued - uploads, the clearing pass - reads the set, so the turn is submitted.
   static void abandonRanges(mlgpu_events* ev, mlgpu_events::Staging& sg)
   {
-    if (!sg.nDirtySet) return;
-    hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream, (const uint4*)sg.d_dirty.get(), sg.nDirtySet, ev->d_recRange.get());
-    (void)hipGetLastError();
-    sg.nDirtySet = 0;
-    // (the list must outlive the clearing pass: the next use of this staging buffer waits for `done`)
-    if (hipEventRecord(sg.done.get(), ev->e->stream) == hipSuccess) sg.pending = true;
+    if (sg.nDirtySet)
+    {
+      hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream, (const uint4*)sg.d_dirty.get(), sg.nDirtySet, ev->d_recRange.get());
+      (void)hipGetLastError();
+      sg.nDirtySet = 0;
+    }
+    sg.turn.submitted(ev->e->stream);
   }
 
   // One block of nVectors DSPVectors starting at frame startOffset of the event times, up to the kernel that consumes it: the block's
@@ -1178,14 +1167,16 @@ extern "C"
       return efail(ev, MLGPU_ERR_RANGE, "events_process: more DSPVectors than events_watch_controllers reserved the controller signals for");
     router.route(nVectors, startOffset);  // (before the wait below: block k + 1 is routed while block k runs)
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    mlgpu_events::Staging& sg = ev->stage[ev->stageIdx];
-    sgOut = &sg;
-    ev->stageIdx ^= 1;
-    if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
-    sg.pending = false;
+    sgOut = ev->stage.take();
+    if (!sgOut) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
+    mlgpu_events::Staging& sg = *sgOut;
+    const auto giveUp = [&](int st, const std::string& what) {
+      abandonRanges(ev, sg);
+      return efail(ev, st, what);
+    };
     const size_t nRecs = router.recordCount(), nDirty = router.dirtyLaneCount();
-    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, 4096)) return efail(ev, MLGPU_ERR_OOM, "events_process: record buffer");
-    if (!growPair(sg.h_dirty, sg.d_dirty, sg.dirtyCapacity, nDirty, 1024)) return efail(ev, MLGPU_ERR_OOM, "events_process: lane list");
+    if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, std::max<size_t>(4096, 2 * (nRecs + 1)))) return giveUp(MLGPU_ERR_OOM, "events_process: record buffer");
+    if (!growPair(sg.h_dirty, sg.d_dirty, sg.dirtyCapacity, nDirty, std::max<size_t>(1024, 2 * nDirty))) return giveUp(MLGPU_ERR_OOM, "events_process: lane list");
     router.pack(sg.h_recs.get(), sg.h_dirty.get());
     hipError_t cerr = hipSuccess;
     if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(LaneRange) * nDirty, hipMemcpyHostToDevice, e->stream);
@@ -1196,10 +1187,10 @@ extern "C"
       cerr = hipGetLastError();
       if (cerr == hipSuccess) sg.nDirtySet = nDirty;
     }
-    if (cerr != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process upload: ") + hipGetErrorString(cerr));
+    if (cerr != hipSuccess) return giveUp(MLGPU_ERR_HIP, std::string("events_process upload: ") + hipGetErrorString(cerr));
 
     dev.s = deviceSettings(ev);
-    const int cst = router.watched().empty() ? MLGPU_OK : processControllers(ev, nVectors, ev->stageIdx ^ 1, dev.s);
+    const int cst = router.watched().empty() ? MLGPU_OK : processControllers(ev, nVectors, (int)(&sg - ev->stage.set), dev.s);
     if (cst != MLGPU_OK)
     {
       abandonRanges(ev, sg);
@@ -1216,8 +1207,7 @@ extern "C"
   static int launched(mlgpu_events* ev, mlgpu_events::Staging& sg)
   {
     sg.nDirtySet = 0;  // (the consuming kernel clears the ranges it read)
-    if (hipEventRecord(sg.done.get(), ev->e->stream) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "events_process: event");
-    sg.pending = true;  // no wait here: the host goes on routing the next block while this one runs
+    sg.turn.submitted(ev->e->stream);  // no wait here: the host goes on routing the next block while this one runs
     return MLGPU_OK;
   }
 

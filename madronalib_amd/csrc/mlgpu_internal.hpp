@@ -13,6 +13,7 @@
 #include "../../include/mlgpu.h"
 #include "mlgpu_device_args.hpp"
 #include "param_updates.hpp"
+#include "staging_turns.hpp"
 
 // Owning device memory, pinned host memory and HIP events: every handle frees what it holds by deleting its members
 struct DeviceFree
@@ -49,6 +50,38 @@ inline hipError_t allocate(OwnedEvent& out, unsigned flags = hipEventDefault)
   const hipError_t err = hipEventCreateWithFlags(&ev, flags);
   out.reset(err == hipSuccess ? ev : nullptr);
   return err;
+}
+
+// a pinned + device pair of upload buffers replaced by one of `fresh` elements - the caller's growth policy - when `need` do not fit
+// (the old contents go; capacity 0 if that fails)
+template <class T>
+bool growPair(PinnedBuffer<T>& host, DeviceBuffer<T>& dev, size_t& capacity, size_t need, size_t fresh)
+{
+  if (need <= capacity) return true;
+  capacity = 0;
+  if (allocate(dev, fresh) != hipSuccess || allocate(host, fresh) != hipSuccess) return false;
+  capacity = fresh;
+  return true;
+}
+
+// The staging sets of host uploads take turns by mlstage's rule (staging_turns.hpp; DESIGN.md §3.7, "Staging turns") on HIP events
+struct HipStagingApi
+{
+  using Event = hipEvent_t;
+  using Stream = hipStream_t;
+  static bool create(Event& ev) { return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess; }
+  static void destroy(Event ev) { hipEventDestroy(ev); }
+  static bool wait(Event ev) { return hipEventSynchronize(ev) == hipSuccess; }
+  static bool record(Event ev, Stream stream) { return hipEventRecord(ev, stream) == hipSuccess; }
+  static void drain(Stream stream) { hipStreamSynchronize(stream); }
+};
+using StagingTurn = mlstage::Turn<HipStagingApi>;
+template <class Set> using StagingTurns = mlstage::Turns<HipStagingApi, Set>;
+inline hipError_t createTurn(StagingTurn& turn)  // (for the create functions, which report a hipError_t)
+{
+  if (turn.create()) return hipSuccess;
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? err : hipErrorUnknown;
 }
 
 struct mlgpu_engine
@@ -209,15 +242,13 @@ struct mlgpu_updater
   mlupd::UpdatePlanner planner;
   mlupd::TableDesc desc;
   bool described{false};
-  struct Staging
+  struct Set
   {
     PinnedBuffer<mlupd::DevRec> h_recs;
     DeviceBuffer<mlupd::DevRec> d_recs;
     size_t capacity{0};
-    OwnedEvent done;
-    bool pending{false};
-  } stage[2];
-  int idx{0};
+  };
+  StagingTurns<Set> stage;
   size_t reserved{0};  // reserve_updates: device records per call (0: no reserve, the buffers grow inside apply)
 };
 int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRecords, std::string& err);

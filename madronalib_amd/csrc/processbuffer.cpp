@@ -36,13 +36,15 @@ struct mlgpu_process_buffer
   std::vector<mlgpu_dspbuffer*> in, out;
   size_t maxFrames{0}, maxVectors{0};
   // two sets of staging buffers: pinned host and device, each [(nIn + nOut)][maxVectors * 64]. The synchronous mode uses
-  // set 0 only; the pipelined mode alternates, so block k + 1 is gathered and uploaded while block k is still on the device
+  // set 0 only; the pipelined mode alternates, so block k + 1 is gathered and uploaded while block k is still on the device.
+  // A set's data makes a round trip, so the alternation is this object's own (`cur`); the event and the pending flag of a set are
+  // a turn's ("Staging turns")
   struct Stage
   {
     PinnedBuffer<float> h;
     DeviceBuffer<float> d;
-    OwnedEvent done;
-    size_t K{0};          // vectors in flight in this set (0: nothing pending)
+    StagingTurn turn;
+    size_t K{0};          // vectors of a whole block submitted in this set and not yet moved into the rings
   } stage[2];
   int cur{0};
   bool pipelined{false};
@@ -59,11 +61,11 @@ struct mlgpu_process_buffer
 
 namespace
 {
-// what was submitted in stage `sg` has come back: move it into the output rings, one DSPVector at a time as the reference
+// stage `sg` is free again: whatever was submitted in it has finished, and a whole block that came back is moved into the output
+// rings, one DSPVector at a time as the reference
 int retire(mlgpu_process_buffer* p, mlgpu_process_buffer::Stage& sg)
 {
-  if (!sg.K) return MLGPU_OK;
-  if (hipEventSynchronize(sg.done.get()) != hipSuccess)
+  if (!sg.turn.wait())
   {
     p->e->lastError = "process_buffer_process: waiting for a block";
     return MLGPU_ERR_HIP;
@@ -120,7 +122,7 @@ extern "C"
     {
       if (err == hipSuccess) err = allocate(sg.h, floats + 4);
       if (err == hipSuccess) err = allocate(sg.d, floats + 4);
-      if (err == hipSuccess) err = allocate(sg.done, hipEventDisableTiming);
+      if (err == hipSuccess) err = createTurn(sg.turn);
     }
     if (err != hipSuccess)
     {
@@ -198,24 +200,26 @@ extern "C"
       for (size_t c = 0; c < nIn; ++c)
         for (size_t k = 0; k < K; ++k)  // one DSPVector at a time: zeros when the ring runs dry (DSPBuffer::read(), :257)
           mlgpu_dspbuffer_read_vector(p->in[c], sg.h.get() + c * chan + k * MLGPU_FLOATS_PER_DSPVECTOR);
+      const char* step = "H2D";
       hipError_t err = hipSetDevice(e->device);
+      const bool deviceSet = err == hipSuccess;  // from here on the stream may hold work that uses the set: one way out, through submitted()
       if (err == hipSuccess && nIn) err = hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(float) * nIn * chan, hipMemcpyHostToDevice, e->stream);
+      int st = MLGPU_OK;
+      if (err == hipSuccess)
+      {
+        for (size_t c = 0; c < nIn; ++c) p->d_in[c] = sg.d.get() + c * chan;
+        for (size_t c = 0; c < nOut; ++c) p->d_out[c] = sg.d.get() + (nIn + c) * chan;
+        st = fn(user, K, p->d_in.data(), p->d_out.data());
+        step = "D2H";
+        if (st == MLGPU_OK) err = hipMemcpyAsync(sg.h.get() + nIn * chan, sg.d.get() + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream);
+      }
+      if (deviceSet) sg.turn.submitted(e->stream);
       if (err != hipSuccess)
       {
-        e->lastError = std::string("process_buffer_process (H2D): ") + hipGetErrorString(err);
+        e->lastError = std::string("process_buffer_process (") + step + "): " + hipGetErrorString(err);
         return MLGPU_ERR_HIP;
       }
-      for (size_t c = 0; c < nIn; ++c) p->d_in[c] = sg.d.get() + c * chan;
-      for (size_t c = 0; c < nOut; ++c) p->d_out[c] = sg.d.get() + (nIn + c) * chan;
-      const int st = fn(user, K, p->d_in.data(), p->d_out.data());
-      if (st != MLGPU_OK) return st;
-      err = hipMemcpyAsync(sg.h.get() + nIn * chan, sg.d.get() + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream);
-      if (err == hipSuccess) err = hipEventRecord(sg.done.get(), e->stream);
-      if (err != hipSuccess)
-      {
-        e->lastError = std::string("process_buffer_process (D2H): ") + hipGetErrorString(err);
-        return MLGPU_ERR_HIP;
-      }
+      if (st != MLGPU_OK) return st;  // (K stays 0: the block is lost, the set is safe)
       sg.K = K;
     }
     if (p->pipelined)

@@ -79,14 +79,12 @@ struct mlgpu_transport
   DeviceBuffer<float> d_omega;
   DeviceBuffer<double> d_dpdt;
   DeviceBuffer<float> d_out;
-  struct Staging
+  struct Set
   {
     PinnedBuffer<Update> h;
     DeviceBuffer<Update> d;
-    OwnedEvent done;
-    bool pending{false};
-  } stage[2];
-  int stageIdx{0};
+  };
+  StagingTurns<Set> stage;  // the reports' upload: two sets that take turns ("Staging turns")
 };
 
 namespace
@@ -180,11 +178,11 @@ extern "C"
     if (err == hipSuccess) err = allocate(t->d_omega, n);
     if (err == hipSuccess) err = allocate(t->d_dpdt, n);
     if (err == hipSuccess) err = allocate(t->d_out, 64 * maxVectors * n);
-    for (mlgpu_transport::Staging& s : t->stage)
+    for (auto& s : t->stage.set)
     {
       if (err == hipSuccess) err = allocate(s.d, n);
       if (err == hipSuccess) err = allocate(s.h, n);
-      if (err == hipSuccess) err = allocate(s.done, hipEventDisableTiming);
+      if (err == hipSuccess) err = createTurn(s.turn);
     }
     if (err == hipSuccess) err = hipMemsetAsync(t->d_omega.get(), 0, sizeof(float) * n, e->stream);  // omega_{0}, dpdt_{0}
     if (err == hipSuccess) err = hipMemsetAsync(t->d_dpdt.get(), 0, sizeof(double) * n, e->stream);
@@ -259,22 +257,21 @@ extern "C"
     if (hipSetDevice(e->device) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "hipSetDevice");
     if (!t->dirty.empty())
     {
-      mlgpu_transport::Staging& sg = t->stage[t->stageIdx];
-      t->stageIdx ^= 1;
-      if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: waiting for the launch before last");
-      sg.pending = false;
+      auto* const sg = t->stage.take();
+      if (!sg) return tfail(t, MLGPU_ERR_HIP, "transport_process: waiting for the launch before last");
       size_t n = 0;
       for (uint32_t i : t->dirty)
       {
         TimeState& s = t->st[i];
-        sg.h[n++] = Update{i, s.setOmega ? 1u : 0u, s.omega, 0.f, s.dpdt};
+        sg->h[n++] = Update{i, s.setOmega ? 1u : 0u, s.omega, 0.f, s.dpdt};
         s.dirty = s.setOmega = false;
       }
       t->dirty.clear();
-      if (hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(Update) * n, hipMemcpyHostToDevice, e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: upload");
-      hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, sg.d.get(), n, t->d_omega.get(), t->d_dpdt.get());
-      if (hipEventRecord(sg.done.get(), e->stream) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "transport_process: event");
-      sg.pending = true;
+      const bool uploaded = hipMemcpyAsync(sg->d.get(), sg->h.get(), sizeof(Update) * n, hipMemcpyHostToDevice, e->stream) == hipSuccess;
+      if (uploaded)
+        hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, sg->d.get(), n, t->d_omega.get(), t->d_dpdt.get());
+      sg->turn.submitted(e->stream);  // (after a failed copy too)
+      if (!uploaded) return tfail(t, MLGPU_ERR_HIP, "transport_process: upload");
     }
     hipLaunchKernelGGL(transport_kernel, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, e->stream, t->d_omega.get(), t->d_dpdt.get(), t->d_out.get(), t->n, nVectors);
     const hipError_t err = hipGetLastError();

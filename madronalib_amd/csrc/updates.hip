@@ -2,8 +2,7 @@
 //
 // param_updates.cpp turns a list of mlgpu_update records into batches of 16-byte device records none of which writes a word twice;
 // here a batch is one launch of apply_updates_kernel on the engine's stream, behind the asynchronous upload of its records from one
-// of two pinned staging sets (as mlgpu_events::Staging): the host packs into the set that is free and waits only if the call
-// before last has not finished. The ring records of MLGPU_UPDATE_CLEAR_RINGS lie behind the table records in the same upload and
+// of two pinned staging sets that take turns ("Staging turns"). The ring records of MLGPU_UPDATE_CLEAR_RINGS lie behind the table records in the same upload and
 // are one launch of clear_rings_kernel.
 #include <string.h>
 
@@ -105,15 +104,6 @@ static int ufail(std::string& err, int status, const std::string& what)
 // single launch can take, at reserve and before anything of a list is enqueued
 static constexpr size_t kMaxDeviceRecords = (size_t)1 << 25;
 
-static bool growStage(mlgpu_updater::Staging& sg, size_t need)
-{
-  if (need <= sg.capacity) return true;
-  sg.capacity = 0;
-  if (allocate(sg.d_recs, need) != hipSuccess || allocate(sg.h_recs, need) != hipSuccess) return false;
-  sg.capacity = need;
-  return true;
-}
-
 int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRecords, std::string& err)
 {
   if (e->recording) return ufail(err, MLGPU_ERR_INVALID, "reserve_updates allocates: not while recording a sequence");
@@ -121,12 +111,10 @@ int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRec
   if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
   // (launches that read the old buffers may be in flight)
   if (hipStreamSynchronize(e->stream) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipStreamSynchronize");
-  for (mlgpu_updater::Staging& sg : u.stage)
-  {
-    sg.pending = false;
-    if (!sg.done && allocate(sg.done, hipEventDisableTiming) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipEventCreate");
-    if (!growStage(sg, maxDeviceRecords)) return ufail(err, MLGPU_ERR_OOM, "reserve_updates: record buffers");
-  }
+  u.stage.drained();
+  if (!u.stage.create()) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipEventCreate");
+  for (mlgpu_updater::Set& sg : u.stage.set)
+    if (!growPair(sg.h_recs, sg.d_recs, sg.capacity, maxDeviceRecords, maxDeviceRecords)) return ufail(err, MLGPU_ERR_OOM, "reserve_updates: record buffers");
   u.planner.reserve(maxDeviceRecords);
   u.reserved = maxDeviceRecords;
   return MLGPU_OK;
@@ -154,14 +142,13 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
     return ufail(err, MLGPU_ERR_RANGE, "apply_updates: the list needs " + std::to_string(nDev) + " device records, reserve_updates reserved " + std::to_string(u.reserved));
   if (nDev > kMaxDeviceRecords || nRing >= kMaxDeviceRecords / 2) return ufail(err, MLGPU_ERR_RANGE, "apply_updates: more than 2^25 device records in one list");
   if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
-  mlgpu_updater::Staging& sg = u.stage[u.idx];
-  u.idx ^= 1;
-  if (sg.pending && hipEventSynchronize(sg.done.get()) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "apply_updates: waiting for the call before last");
-  sg.pending = false;
-  if (!sg.done && allocate(sg.done, hipEventDisableTiming) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "apply_updates: hipEventCreate");
+  auto* const taken = u.stage.take();
+  if (!taken) return ufail(err, MLGPU_ERR_HIP, "apply_updates: waiting for the call before last");
+  auto& sg = *taken;
+  if (!sg.turn.create()) return ufail(err, MLGPU_ERR_HIP, "apply_updates: hipEventCreate");  // (no reserve: the event is made here)
   // after a reserve both sets hold `reserved` records and nothing is allocated here, ever; without one the buffers grow here, a
-  // setup convenience that allocates and may wait (nothing of this set is in flight: see the wait above)
-  if (!u.reserved && nDev > sg.capacity && !growStage(sg, std::max<size_t>(1024, 2 * nDev))) return ufail(err, MLGPU_ERR_OOM, "apply_updates: record buffers");
+  // setup convenience that allocates and may wait (nothing of this set is in flight: it was taken)
+  if (!u.reserved && !growPair(sg.h_recs, sg.d_recs, sg.capacity, nDev, std::max<size_t>(1024, 2 * nDev))) return ufail(err, MLGPU_ERR_OOM, "apply_updates: record buffers");
   u.planner.pack(u.desc, recs, n, sg.h_recs.get());
   hipError_t herr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(DevRec) * nDev, hipMemcpyHostToDevice, e->stream);
   UpdateArgs a;
@@ -197,11 +184,7 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
     hipLaunchKernelGGL(clear_rings_kernel, dim3((uint32_t)nRing, (uint32_t)y), dim3(256), 0, e->stream, ra);
     herr = hipGetLastError();
   }
-  // (whatever was enqueued reads this set: the event goes in even after a failed launch)
-  if (hipEventRecord(sg.done.get(), e->stream) == hipSuccess)
-    sg.pending = true;
-  else
-    hipStreamSynchronize(e->stream);
+  sg.turn.submitted(e->stream);  // (after a failed copy or launch too)
   if (herr != hipSuccess) return ufail(err, MLGPU_ERR_HIP, std::string("apply_updates: ") + hipGetErrorString(herr));
   return MLGPU_OK;
 }
@@ -211,8 +194,8 @@ size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four)
 {
   for (int i = 0; i < 2; ++i)
   {
-    four[2 * i] = u.stage[i].h_recs.get();
-    four[2 * i + 1] = u.stage[i].d_recs.get();
+    four[2 * i] = u.stage.set[i].h_recs.get();
+    four[2 * i + 1] = u.stage.set[i].d_recs.get();
   }
-  return std::min(u.stage[0].capacity, u.stage[1].capacity);
+  return std::min(u.stage.set[0].capacity, u.stage.set[1].capacity);
 }
