@@ -83,10 +83,17 @@ struct MixStrips<true>
 // pays nothing for them)
 // (LISTED: the voice-list forms - what belongs to the voice, its gain and its input row, is at voice vs, what the launch produces at
 // the lane's list position v; *peak gets the largest bits(y) & 0x7fffffff of the launch, y before any gain, kept in a register)
-template <class CH, bool HAS_SIGNAL, bool FAST_HEAD, bool MIX = false, bool SCALED = false, bool LISTED = false>
+// HEAD: how the head processor takes a launch-constant input, decided once per wavefront (chain_kernel_body) - kHeadGeneral: per
+// sample, range test included; kHeadFast: per sample, the range test done; kHeadTrip: 8 samples (two quads) at a time, the polyBLEP
+// corrections once per zone per trip (Chain::next_head_trip) - same bits, about a third fewer instructions.
+constexpr int kHeadGeneral = 0, kHeadFast = 1, kHeadTrip = 2;
+constexpr int kHeadTripSamples = 8;
+
+template <class CH, bool HAS_SIGNAL, int HEAD, bool MIX = false, bool SCALED = false, bool LISTED = false>
 __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip = nullptr, bool live = true, size_t vs = 0,
                                           uint32_t* peak = nullptr)
 {
+  static_assert(HEAD != kHeadTrip || (!HAS_SIGNAL && CH::kHeadHasTrip), "trips want a launch-constant input and a head that has them");
   const size_t vin = LISTED ? vs : v;
   uint32_t pk = 0;
   const float mixGain = (SCALED && a.mixGains) ? a.mixGains[vin] : 1.f;
@@ -98,17 +105,27 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
   {
     const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
     f32x4* po = MIX ? nullptr : pout + t * a.out.strideT;
+    float s[kHeadTripSamples];  // (kHeadTrip: the trip the quad belongs to)
 #pragma unroll 4
     for (int q = 0; q < 16; ++q)
     {
       if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
-      f32x4 x = {xc, xc, xc, xc};
-      if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
       f32x4 y;
-      y.x = ch.template next_head<FAST_HEAD>(x.x);
-      y.y = ch.template next_head<FAST_HEAD>(x.y);
-      y.z = ch.template next_head<FAST_HEAD>(x.z);
-      y.w = ch.template next_head<FAST_HEAD>(x.w);
+      if constexpr (HEAD == kHeadTrip)
+      {
+        static_assert(kHeadTripSamples == 8, "a trip is two quads");
+        if ((q & 1) == 0) ch.template next_head_trip<kHeadTripSamples>(xc, s);
+        y = (q & 1) ? f32x4{s[4], s[5], s[6], s[7]} : f32x4{s[0], s[1], s[2], s[3]};
+      }
+      else
+      {
+        f32x4 x = {xc, xc, xc, xc};
+        if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
+        y.x = ch.template next_head<HEAD == kHeadFast>(x.x);
+        y.y = ch.template next_head<HEAD == kHeadFast>(x.y);
+        y.z = ch.template next_head<HEAD == kHeadFast>(x.z);
+        y.w = ch.template next_head<HEAD == kHeadFast>(x.w);
+      }
       if constexpr (LISTED)
       {
         const uint32_t m0 = f2u(y.x) & 0x7fffffffu, m1 = f2u(y.y) & 0x7fffffffu, m2 = f2u(y.z) & 0x7fffffffu, m3 = f2u(y.w) & 0x7fffffffu;
@@ -137,6 +154,24 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
     ch.end_vector();
   }
   if constexpr (LISTED) *peak = pk;
+}
+
+// run_voice in the head mode the wavefront has chosen (the same in all lanes)
+template <class CH, bool HAS_SIGNAL, bool MIX, bool SCALED, bool LISTED>
+__device__ __forceinline__ void run_voice_as(int head, CH& ch, const ChainArgs& a, size_t v, float xc, float* strip, bool live, size_t vs, uint32_t* peak)
+{
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  {
+    if (head == kHeadTrip)
+    {
+      run_voice<CH, HAS_SIGNAL, kHeadTrip, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
+      return;
+    }
+  }
+  if (head != kHeadGeneral)
+    run_voice<CH, HAS_SIGNAL, kHeadFast, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
+  else
+    run_voice<CH, HAS_SIGNAL, kHeadGeneral, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
 }
 
 // ---- groups of adjacent voices inside the voice kernel (chain_group_kernel) ----
@@ -277,6 +312,12 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   // range test: decide once per wavefront which loop body to run.
   bool fastHead = false;
   if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(CH::head_input_is_odd(xc)) == 0);
+  // ... and a SawGen head whose frequencies also allow it (0 < f <= 1/16 in every lane) makes its samples in trips of 8
+  int head = fastHead ? kHeadFast : kHeadGeneral;
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  {
+    if (fastHead && __builtin_amdgcn_ballot_w64(trip_freq_is_dense(xc, kHeadTripSamples)) == 0) head = kHeadTrip;
+  }
   if constexpr (OUT_G != 0)
   {
     if (a.mixGains != nullptr)  // (the same in all lanes: a kernel argument)
@@ -295,21 +336,12 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   {
     const bool scaled = a.mixGains != nullptr || __builtin_amdgcn_ballot_w64(!live) != 0;  // (the same in all lanes)
     if (scaled)
-    {
-      if (fastHead)
-        run_voice<CH, HAS_SIGNAL, true, true, true, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
-      else
-        run_voice<CH, HAS_SIGNAL, false, true, true, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
-    }
-    else if (fastHead)
-      run_voice<CH, HAS_SIGNAL, true, true, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
+      run_voice_as<CH, HAS_SIGNAL, true, true, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
     else
-      run_voice<CH, HAS_SIGNAL, false, true, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
+      run_voice_as<CH, HAS_SIGNAL, true, false, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
   }
-  else if (fastHead)
-    run_voice<CH, HAS_SIGNAL, true, MIX, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
   else
-    run_voice<CH, HAS_SIGNAL, false, MIX, false, LISTED>(ch, a, v, xc, strip, live, vs, &pk);
+    run_voice_as<CH, HAS_SIGNAL, false, false, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
   ch.store(mem);
   if constexpr (LISTED)
   {

@@ -2619,6 +2619,7 @@ struct Chain<>
   MLD float next(float x) { return x; }
   MLD void end_vector() {}
   static constexpr bool kHeadHasFastPath = false;
+  static constexpr bool kHeadHasTrip = false;
   static MLD bool head_input_is_odd(float) { return false; }
   template <bool FAST>
   MLD float next_head(float x)
@@ -2666,6 +2667,19 @@ struct Chain<K0, KS...>
       return tail.next(head.next_fast(x));
     else
       return tail.next(head.next(x));
+  }
+  // TRIP: the caller has also checked !trip_freq_is_dense(x, N) on every lane - a launch-constant frequency in (0, 1 / 2N]: the head makes
+  // N samples at once, its polyBLEP corrections once per zone (Proc<SAW_GEN>::trip_u), the tail takes them in sample order. SawGen
+  // only: PulseGen's `odd` would have to cover the width's range.
+  static constexpr bool kHeadHasTrip = kHeadHasFastPath && (K0 == MLGPU_PROC_SAW_GEN);
+  template <int N>
+  MLD void next_head_trip(float x, float (&y)[N])
+  {
+    static_assert(kHeadHasTrip, "a head with a trip form");
+    float s[N];
+    head.template trip_u<N>(x, /*odd*/ false, /*dense*/ false, s);
+#pragma unroll
+    for (int i = 0; i < N; ++i) y[i] = tail.next(s[i]);
   }
   MLD void end_vector()
   {
