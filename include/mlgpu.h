@@ -851,6 +851,58 @@ int mlgpu_bank_apply_updates(mlgpu_bank* b, const mlgpu_update* recs, size_t n);
 int mlgpu_graph_get_param(mlgpu_graph* g, int param_node, float* h_per_voice);
 int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h_per_voice);
 
+/* VOICE LISTS FOR GRAPHS: run only the listed voices of a graph, with the bank's rule and call discipline (VOICE LISTS above). With the
+ * list L[0 .. K) - voice indices, strictly ascending, all below n_voices - a listed process call behaves exactly as a graph of K voices
+ * with the same description, made of voices L[0] ... L[K-1] in that order.
+ *   What belongs to a voice is addressed by its voice index L[i]: coefficient, state and param rows, feedback vectors, delay rings, the
+ *   voice's row of every streamed input - inputs are still signals of n_voices rows; with mlgpu_graph_set_input_group(.., P) the row
+ *   is L[i] / P; a MLGPU_LAYOUT_BROADCAST input is the one row, as in mlgpu_graph_process - and the voice's column of every control
+ *   signal [n_vectors][n_voices].
+ *   What the call produces is addressed by list position i: every plain output is a signal of K rows in `out_layout`; an output set to
+ *   the mixdown of all voices (mlgpu_graph_set_output_mixdown(.., 1)) is the mixdown tree of a K-voice graph - mlgpu_mixdown's order
+ *   and bits over the K listed signals - in 64 * n_vectors floats; the peaks are d_peak[K].
+ *   Unlisted voices are neither read nor written: every coefficient, state, param, feedback and ring word of theirs holds the same
+ *   bits after the call, and no time passes for them.
+ *   Any split of n_vectors into several listed launches with the same list gives the bits of one launch.
+ *
+ * mlgpu_graph_enable_voice_lists(g, 1) is a build call (before compile; it drops what an earlier mlgpu_graph_emit made): the listed
+ * form is a second generated kernel, and a cold hiprtc compile takes seconds and must never happen inside a process call. With it on,
+ * mlgpu_graph_compile, _compile_async / _poll and mlgpu_graph_emit make both kernels, and compile loads both; the memory cache, the
+ * disk cache and mlgpu_jit_cache_export / _import carry the listed kernel like any other (it is found by its source). The kernel of
+ * mlgpu_graph_process is the same with it on or off. On a graph made without it the calls below answer MLGPU_ERR_INVALID and say so.
+ * mlgpu_graph_compile / mlgpu_graph_emit refuse (MLGPU_ERR_UNSUPPORTED, the message names the reason, nothing is built) a graph with
+ * voice lists enabled that the listed form does not serve:
+ *   delay ring layouts 1, 2 and 4 - also where layout 3 resolves to one of them: their LDS windows and 64-byte pieces are made by a
+ *   wavefront's neighbouring voices of one 256-voice block (layout 0, the rows, is served: mlgpu_graph_set_delay_layout(g, 0));
+ *   an output group sum (mlgpu_graph_set_output_group_sum); the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2));
+ *   event rows (mlgpu_graph_add_event_row: the events object goes by lane); a MLGPU_REGION_DOWNSAMPLE_2X region (it pairs DSPVectors
+ *   2k and 2k + 1 by the graph's count, not by a voice's).
+ * Input groups, UPSAMPLE_2X regions, feedback nodes, controls, live constants, const vectors, routes and impulse tables are served.
+ *
+ * mlgpu_graph_reserve_voice_list / _set_voice_list / _voice_list_size: as mlgpu_bank_reserve_voice_list / _set_voice_list /
+ * _voice_list_size, to the letter - HOST memory, validated completely before anything is enqueued (a refused list leaves the previous
+ * one in force), copied on the engine's stream between the process and apply_updates calls around it, waiting only for its own call
+ * before last, never allocating after a reserve, not while recording a sequence; the same statuses.
+ *
+ * mlgpu_graph_process_listed: mlgpu_graph_process_ctl of the listed voices (d_controls NULL for a graph without controls). It never
+ * allocates - with a mixed-down output it needs mlgpu_graph_reserve_mixdown, as mlgpu_graph_process does - and can be recorded into a
+ * sequence with the bank's caveat: K is fixed when it is recorded, the list's contents may change between replays. It does not
+ * advance the graph's DSPVector count. It always runs one voice per lane: mlgpu_graph_set_autotune and
+ * mlgpu_graph_set_voices_per_lane(2) do not apply to it, and it leaves their state alone. With an empty list it launches nothing for
+ * plain outputs and writes +0.0 to the 64 * n_vectors floats of a mixed-down output.
+ *   d_peak  NULL, or K words: d_peak[i] = the maximum of (bits(y) & 0x7fffffff), as an unsigned integer, over every sample of every
+ *           output node of voice L[i] in this launch, before any mixdown. The same in both floating-point modes; above 0x7f800000 if
+ *           a NaN went by. Written once per launch, not accumulated across launches.
+ * mlgpu_graph_listed_source / mlgpu_graph_emit_listed: mlgpu_graph_source / mlgpu_graph_emit for the listed kernel (no device). */
+int mlgpu_graph_enable_voice_lists(mlgpu_graph* g, int on);
+int mlgpu_graph_reserve_voice_list(mlgpu_graph* g, size_t max_listed);
+int mlgpu_graph_set_voice_list(mlgpu_graph* g, const uint32_t* h_voices, size_t n);
+size_t mlgpu_graph_voice_list_size(mlgpu_graph* g);
+int mlgpu_graph_process_listed(mlgpu_graph* g, size_t n_vectors, const float* const* d_inputs, int in_layout,
+                               const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
+const char* mlgpu_graph_listed_source(mlgpu_graph* g);
+int mlgpu_graph_emit_listed(mlgpu_graph* g, const void** code, size_t* code_size);
+
 /* Chains without an ahead-of-time kernel are fused with hiprtc when their bank is created
  * (default on). With jit off they run processor by processor through HBM scratch signals. */
 int mlgpu_engine_set_jit(mlgpu_engine* e, int enabled);

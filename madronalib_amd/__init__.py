@@ -1116,7 +1116,7 @@ class Graph(_Handle):
     _destroy = "mlgpu_graph_destroy"
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
-                 live_constants=False, output_groups=None, input_groups=None, compile_now=True):
+                 live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1135,6 +1135,8 @@ class Graph(_Handle):
             engine._check(self.L.mlgpu_graph_set_autotune(self.h, 1))
         if live_constants:
             self._check(self.L.mlgpu_graph_set_live_constants(self.h, 1))
+        if voice_lists:   # compile makes the listed form of the kernel too: set_voice_list / process_listed
+            self.enable_voice_lists()
         if description is not None:
             for n in description:
                 self.add(**n)
@@ -1176,6 +1178,46 @@ class Graph(_Handle):
         code, size = ctypes.c_void_p(), ctypes.c_size_t()
         self._check(self.L.mlgpu_graph_emit(self.h, ctypes.byref(code), ctypes.byref(size)))
         return self.source, ctypes.string_at(code, size.value)
+
+    def enable_voice_lists(self, on=True):
+        """Before compile: the graph gets the listed form of its kernel too (mlgpu_graph_enable_voice_lists)."""
+        self._check(self.L.mlgpu_graph_enable_voice_lists(self.h, 1 if on else 0))
+
+    def listed_source(self):
+        """The source of the listed kernel ("" before emit / compile, or without voice lists)."""
+        return self.L.mlgpu_graph_listed_source(self.h).decode()
+
+    def emit_listed(self):
+        """(listed kernel source, gfx950 code object bytes) without a device (mlgpu_graph_emit_listed)."""
+        code, size = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self.L.mlgpu_graph_emit_listed(self.h, ctypes.byref(code), ctypes.byref(size)))
+        return self.listed_source(), ctypes.string_at(code, size.value)
+
+    def reserve_voice_list(self, max_listed):
+        """Setup: from now on set_voice_list never allocates, and refuses (Status.ERR_RANGE) a longer list."""
+        self._check(self.L.mlgpu_graph_reserve_voice_list(self.h, int(max_listed)))
+
+    def set_voice_list(self, indices):
+        """The voices process_listed runs: strictly ascending indices below V (empty: none). Copied to the device on the engine's
+        stream, ordered between the calls around it; does not wait for the device (mlgpu_graph_set_voice_list)."""
+        v = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self.L.mlgpu_graph_set_voice_list(self.h, _np_ptr(v) if v.size else None, v.size))
+
+    @property
+    def voice_list_size(self):
+        return int(self.L.mlgpu_graph_voice_list_size(self.h))
+
+    def process_listed(self, n_vectors, d_inputs, d_outputs, in_layout=Layout.QUAD, out_layout=Layout.QUAD, d_controls=(), d_peak=None):
+        """process() of the listed voices only, as a graph of K = voice_list_size voices in list order: inputs and controls keep
+        their V rows / columns (lane i reads the ones of voice list[i]), plain outputs have K rows, a mixed-down output is the K-voice
+        tree, d_peak (if any) gets K uint32 words - the largest bits(y) & 0x7fffffff over the voice's outputs in this launch. Unlisted
+        voices are neither read nor written (mlgpu_graph_process_listed)."""
+        raw = lambda b: b.ptr if hasattr(b, "ptr") else int(b)  # noqa: E731
+        pi = (ctypes.c_void_p * max(1, len(d_inputs)))(*[raw(b) for b in d_inputs])
+        po = (ctypes.c_void_p * max(1, len(d_outputs)))(*[raw(b) for b in d_outputs])
+        pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
+        pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
+        self._check(self.L.mlgpu_graph_process_listed(self.h, int(n_vectors), pi, int(in_layout), pc, po, int(out_layout), pp))
 
     def _id(self, ref):
         return self.ids[ref] if isinstance(ref, str) else int(ref)

@@ -44,7 +44,17 @@ struct GraphBuild
   GraphPlan plan;
   std::string source, log;
   std::vector<char> code;
+  // the listed form (GraphDesc::voiceLists; else empty): the second kernel of the same plan
+  std::string listedSource, listedLog;
+  std::vector<char> listedCode;
 };
+// the listed kernel's form: one voice per lane, the plan's quads per trip (autotune and voices per lane do not apply to it)
+KernelForm listedForm(const GraphPlan& p)
+{
+  KernelForm f{1, p.form.quadsPerTrip, 0};
+  f.listed = true;
+  return f;
+}
 }  // namespace
 
 struct mlgpu_graph
@@ -54,6 +64,8 @@ struct mlgpu_graph
   std::unique_ptr<GraphBuild> build;  // made of `desc` by the first mlgpu_graph_emit / _compile after an edit
   bool compiled{false};
   hipFunction_t fn{nullptr};
+  hipFunction_t fnListed{nullptr};  // the listed form's kernel (mlgpu_graph_enable_voice_lists), loaded by the same compile
+  mlgpu_voice_list list;            // mlgpu_graph_set_voice_list
   KernelForm activeForm;         // of the kernel in `fn`: the plan's default form, or the one autotune found faster
   DeviceBuffer<float> d_coeffs;
   DeviceBuffer<uint32_t> d_state;
@@ -70,7 +82,7 @@ struct mlgpu_graph
   struct CompileResult
   {
     std::unique_ptr<GraphBuild> build;  // (empty: the graph's own build was there already, or planning failed)
-    hipFunction_t fn{nullptr};
+    hipFunction_t fn{nullptr}, fnListed{nullptr};
     int status{MLGPU_OK};
     std::string error;
   };
@@ -717,9 +729,15 @@ extern "C"
     GraphBuild& b = *r.build;
     r.status = planGraph(d, readTestHooks(), b.plan, r.error);
     if (r.status != MLGPU_OK) return r.build.reset();
-    if (generateBudgeted(d, b.plan, b.plan.form, b.source, b.code, b.log)) return;
-    r.status = MLGPU_ERR_UNSUPPORTED;  // (the build stays, for mlgpu_graph_source)
-    r.error = "graph_compile (hiprtc): " + b.log;
+    if (!generateBudgeted(d, b.plan, b.plan.form, b.source, b.code, b.log))
+    {
+      r.status = MLGPU_ERR_UNSUPPORTED;  // (the build stays, for mlgpu_graph_source)
+      r.error = "graph_compile (hiprtc): " + b.log;
+      return;
+    }
+    if (!d.voiceLists || generateBudgeted(d, b.plan, listedForm(b.plan), b.listedSource, b.listedCode, b.listedLog)) return;
+    r.status = MLGPU_ERR_UNSUPPORTED;
+    r.error = "graph_compile (hiprtc, the listed form): " + b.listedLog;
   }
   // Everything a compile does that needs no stream: that (unless the graph has it since an mlgpu_graph_emit), then the module on the
   // engine's device. Reads the graph, writes `r`: a compile job runs it on its thread.
@@ -736,12 +754,18 @@ extern "C"
     r.fn = mlgpu_jit_function(e->device, (g->build ? g->build : r.build)->source, "mlgpu_graph_kernel", log, &loaded);
     if (!loaded) return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc): " + log);
     if (!r.fn) return fail(MLGPU_ERR_HIP, log);
+    if (!g->desc.voiceLists) return;
+    loaded = false;
+    r.fnListed = mlgpu_jit_function(e->device, (g->build ? g->build : r.build)->listedSource, "mlgpu_graph_listed_kernel", log, &loaded);
+    if (!loaded) return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile (hiprtc, the listed form): " + log);
+    if (!r.fnListed) return fail(MLGPU_ERR_HIP, log);
   }
   // ... and its result taken over by the graph, on the caller's thread
   static int compileInstall(mlgpu_graph* g, mlgpu_graph::CompileResult& r)
   {
     if (r.build) g->build = std::move(r.build);
     g->fn = r.fn;
+    g->fnListed = r.fnListed;
     return r.status == MLGPU_OK ? MLGPU_OK : gfail(g, r.status, r.error);
   }
   static int compileFinish(mlgpu_graph* g);
@@ -759,6 +783,19 @@ extern "C"
     if (g->build->code.empty()) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_emit (hiprtc): " + g->build->log);
     if (code) *code = g->build->code.data();
     if (codeSize) *codeSize = g->build->code.size();
+    return MLGPU_OK;
+  }
+
+  const char* mlgpu_graph_listed_source(mlgpu_graph* g) { return (g && !g->job && g->build) ? g->build->listedSource.c_str() : ""; }
+  int mlgpu_graph_emit_listed(mlgpu_graph* g, const void** code, size_t* codeSize)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->desc.voiceLists) return gfail(g, MLGPU_ERR_INVALID, "graph_emit_listed: the graph has no listed form (mlgpu_graph_enable_voice_lists before compile / emit)");
+    if (const int st = mlgpu_graph_emit(g, nullptr, nullptr)) return st;
+    if (g->build->listedCode.empty()) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_emit_listed (hiprtc): " + g->build->listedLog);
+    if (code) *code = g->build->listedCode.data();
+    if (codeSize) *codeSize = g->build->listedCode.size();
     return MLGPU_OK;
   }
 
@@ -1100,6 +1137,12 @@ extern "C"
     g->desc.autotune = on != 0;
     return MLGPU_OK;
   }
+  int mlgpu_graph_enable_voice_lists(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_voice_lists: before mlgpu_graph_compile")) return st;
+    g->desc.voiceLists = on != 0;
+    return MLGPU_OK;
+  }
   int mlgpu_graph_set_live_constants(mlgpu_graph* g, int on)
   {
     if (const int st = checkEditable(g, "graph_set_live_constants: before mlgpu_graph_compile")) return st;
@@ -1227,6 +1270,40 @@ extern "C"
     return mlgpu_fill32(g->e, g->d_state.get() + (size_t)(g->desc.nodes[node].sOff + idx) * g->desc.V, value, g->desc.V);
   }
 
+  // What every process call hands its kernel but the outputs: the tables, the streamed inputs as signals of the graph's voices (or of
+  // its input groups) and the controls. MLGPU_OK, or the refusal in `who`'s name.
+  static int signalArgs(mlgpu_graph* g, GraphArgs& a, const char* who, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                        float* const* d_outputs, int outLayout)
+  {
+    const std::string w = who;
+    if (inLayout < 0 || inLayout > MLGPU_LAYOUT_BROADCAST || outLayout < 0 || outLayout > MLGPU_LAYOUT_VOICE_MAJOR) return gfail(g, MLGPU_ERR_INVALID, w + ": bad layout");
+    if ((g->desc.nInputs && !d_inputs) || (g->desc.nControls && !d_controls) || !d_outputs) return gfail(g, MLGPU_ERR_INVALID, w + ": null signal list");
+    memset(&a, 0, sizeof(a));
+    a.coeffs = g->d_coeffs.get();
+    a.state = g->d_state.get();
+    a.params = g->d_params.get();
+    a.consts = g->d_consts.get();
+    a.mem = g->d_mem.get();
+    a.V = g->desc.V;
+    a.T = T;
+    a.flags = g->e->kflags;
+    a.impulseTable = g->e->d_impulseTable.get();
+    for (int i = 0; i < g->desc.nInputs; ++i)
+    {
+      if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, w + ": null / misaligned input");
+      const int lay = (g->inLayoutOverride[i] >= 0) ? g->inLayoutOverride[i] : inLayout;
+      a.in[i] = makeView(d_inputs[i], lay, g->desc.inputGroup[i] > 1 ? g->desc.V / (size_t)g->desc.inputGroup[i] : g->desc.V, T);
+    }
+    for (int i = 0; i < g->desc.nControls; ++i)
+    {
+      if (!d_controls[i]) return gfail(g, MLGPU_ERR_INVALID, w + ": null control signal");
+      a.ctl[i] = d_controls[i];
+    }
+    for (size_t o = 0; o < g->desc.outputs.size(); ++o)
+      if (!d_outputs[o] || ((uintptr_t)d_outputs[o] & 15)) return gfail(g, MLGPU_ERR_INVALID, w + ": null / misaligned output");
+    return MLGPU_OK;
+  }
+
   int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
   {
     return mlgpu_graph_process_ctl(g, T, d_inputs, inLayout, nullptr, d_outputs, outLayout);
@@ -1252,37 +1329,11 @@ extern "C"
     if (g->job) return MLGPU_ERR_BUSY;
     if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph_process: compile first");
     if (T == 0) return MLGPU_OK;
-    if (inLayout < 0 || inLayout > MLGPU_LAYOUT_BROADCAST || outLayout < 0 || outLayout > MLGPU_LAYOUT_VOICE_MAJOR)
-      return gfail(g, MLGPU_ERR_INVALID, "graph_process: bad layout");
-    if ((g->desc.nInputs && !d_inputs) || (g->desc.nControls && !d_controls) || !d_outputs) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null signal list");
     GraphArgs a;
-    memset(&a, 0, sizeof(a));
-    a.coeffs = g->d_coeffs.get();
-    a.state = g->d_state.get();
-    a.params = g->d_params.get();
-    a.consts = g->d_consts.get();
-    a.mem = g->d_mem.get();
-    a.V = g->desc.V;
-    a.T = T;
+    if (const int st = signalArgs(g, a, "graph_process", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     a.t0 = g->vectorCount;
-    a.flags = g->e->kflags;
-    a.impulseTable = g->e->d_impulseTable.get();
-    for (int i = 0; i < g->desc.nInputs; ++i)
-    {
-      if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null / misaligned input");
-      const int lay = (g->inLayoutOverride[i] >= 0) ? g->inLayoutOverride[i] : inLayout;
-      a.in[i] = makeView(d_inputs[i], lay, g->desc.inputGroup[i] > 1 ? g->desc.V / (size_t)g->desc.inputGroup[i] : g->desc.V, T);
-    }
-    for (int i = 0; i < g->desc.nControls; ++i)
-    {
-      if (!d_controls[i]) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null control signal");
-      a.ctl[i] = d_controls[i];
-    }
     for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-    {
-      if (!d_outputs[o] || ((uintptr_t)d_outputs[o] & 15)) return gfail(g, MLGPU_ERR_INVALID, "graph_process: null / misaligned output");
       a.out[o] = makeView(d_outputs[o], outLayout, g->desc.outputGroup[o] ? g->desc.V / (size_t)g->desc.outputGroup[o] : g->desc.V, T);
-    }
     // outputs that are mixdowns: the kernel writes the rows of 64-voice group sums into the engine's mixdown scratch (one region per
     // such output), the later stages follow the launch
     const size_t mixGroups = (g->desc.V + 63) / 64, mixRegion = (mixGroups + (mixGroups + 63) / 64) * T * 64;
@@ -1388,6 +1439,72 @@ extern "C"
         trial->failed = true;
     }
     g->vectorCount += T;
+    return MLGPU_OK;
+  }
+
+  // ---- voice lists: run only the listed voices (mlgpu_voice_list keeps the list, the listed form of the generated kernel runs it) ----
+  static int listsReady(mlgpu_graph* g, const char* who)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->desc.voiceLists) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph has no listed form - mlgpu_graph_enable_voice_lists(g, 1) before compile");
+    if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": compile first");
+    return MLGPU_OK;
+  }
+  int mlgpu_graph_reserve_voice_list(mlgpu_graph* g, size_t maxListed)
+  {
+    if (const int st = listsReady(g, "graph_reserve_voice_list")) return st;
+    const int st = g->list.reserve(g->e, maxListed, "graph_reserve_voice_list");
+    return st == MLGPU_OK ? st : gfail(g, st, g->e->lastError);
+  }
+  int mlgpu_graph_set_voice_list(mlgpu_graph* g, const uint32_t* h_voices, size_t n)
+  {
+    if (const int st = listsReady(g, "graph_set_voice_list")) return st;
+    const int st = g->list.set(g->e, g->desc.V, h_voices, n, "graph_set_voice_list");
+    return st == MLGPU_OK ? st : gfail(g, st, g->e->lastError);
+  }
+  size_t mlgpu_graph_voice_list_size(mlgpu_graph* g) { return (g && !g->job) ? g->list.size : 0; }
+
+  int mlgpu_graph_process_listed(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
+                                 int outLayout, uint32_t* d_peak)
+  {
+    if (const int st = listsReady(g, "graph_process_listed")) return st;
+    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: misaligned peaks");
+    if (T == 0) return MLGPU_OK;
+    GraphArgs a;
+    if (const int st = signalArgs(g, a, "graph_process_listed", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
+    const size_t K = g->list.size;
+    a.t0 = g->vectorCount;  // (not advanced here; no listed graph has a region that reads it)
+    a.voiceList = g->list.d_list.get();
+    a.listed = K;
+    a.peaks = d_peak;
+    // outputs by list position: K rows each; a mixed-down output is the tree of a K-voice graph, its first stage's rows in the scratch
+    const size_t mixGroups = (K + 63) / 64, mixRegion = (mixGroups + (mixGroups + 63) / 64) * T * 64;
+    size_t nMix = 0;
+    for (size_t o = 0; o < g->desc.outputs.size(); ++o)
+    {
+      if (g->desc.outputMix[o]) a.out[o] = makeView(g->e->d_mixScratch.get() + nMix++ * mixRegion, MLGPU_LAYOUT_QUAD, K, T);
+      else a.out[o] = makeView(d_outputs[o], outLayout, K, T);
+    }
+    if (nMix * mixRegion > g->e->mixScratchFloats)
+      return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)");
+    if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
+    if (K == 0)  // (nothing to launch; the sum of no voices: +0.0)
+    {
+      for (size_t o = 0; o < g->desc.outputs.size(); ++o)
+        if (g->desc.outputMix[o] && hipMemsetAsync(d_outputs[o], 0, sizeof(float) * 64 * T, g->e->stream) != hipSuccess)
+          return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: clearing a mixed-down output");
+      return MLGPU_OK;
+    }
+    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream);
+    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed launch: ") + hipGetErrorString(err));
+    for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
+      if (g->desc.outputMix[o])
+      {
+        if (mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream, g->e->kflags) != hipSuccess)
+          return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: the mixdown's later stages");
+        ++r;
+      }
     return MLGPU_OK;
   }
 }

@@ -269,11 +269,12 @@ struct GraphEmitter
   const int VL;
   std::ostringstream s;
   bool windowed, partialWaves, stateAddr32, PF, oscTrips, ringTrips;
-  std::string ringLane;
+  const bool listed;  // the listed form: a lane's place is its position in the voice list (vr), its voice the list's entry there (v)
+  std::string ringLane, places;
   // ring layout 4, per wavefront: every delay node's held sectors (512 floats per ring) and history rows (1024 floats per node)
   std::vector<size_t> sectorLdsOff;
   size_t sectorLdsPerWave{0};
-  GraphEmitter(const GraphDesc& graph, const GraphPlan& plan, const KernelForm& f) : g(graph), p(plan), form(f), VL(f.voicesPerLane), sectorLdsOff(graph.nodes.size(), 0)
+  GraphEmitter(const GraphDesc& graph, const GraphPlan& plan, const KernelForm& f) : g(graph), p(plan), form(f), VL(f.listed ? 1 : f.voicesPerLane), listed(f.listed), sectorLdsOff(graph.nodes.size(), 0)
   {
     windowed = p.rings != RingLayout::ROWS && p.totalRings;
     if (p.rings == RingLayout::SECTORS)
@@ -291,7 +292,11 @@ struct GraphEmitter
     bool anyMix = false;
     for (size_t o = 0; o < g.outputs.size(); ++o) anyMix = anyMix || g.outputMix[o];
     partialWaves = ((p.rings == RingLayout::TRANSPOSED && p.totalRings) || anyMix) && (g.V % 64);
+    // (the listed form: the list's length is known at the launch only - with a mixed-down output the last wavefront's spare lanes
+    // always stay and run the list's last voice again; without one a lane past the list's end returns)
+    if (listed) partialWaves = anyMix;
     ringLane = partialWaves ? "vr" : "v";
+    places = listed ? "a.listed" : "a.V";
     // a row of the state memory at this lane: the row's address is wave-uniform (scalar arithmetic), the lane's place a 32-bit offset on
     // it - one memory instruction where `a.state[row * a.V + v]` with a 64-bit v is a 64-bit vector add in front of it
     stateAddr32 = g.V < ((size_t)1 << 30) && !p.rowAddr64;
@@ -334,7 +339,7 @@ struct GraphEmitter
   void header()
   {
     const std::string ringWindows = p.rings == RingLayout::ROWS ? std::string() : "#define MLGPU_RING_WINDOWS " + std::to_string((int)p.rings) + "\n";
-    s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane)\n" << ringWindows
+    s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane" << (listed ? ", the voices of a list" : "") << ")\n" << ringWindows
       << (g.strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\n#include \"mldsp_ops.hpp\"\n"
       << (g.hasEventRows ? "#include \"mldsp_events.hpp\"\n" : "") << "using namespace mldev;\n";
     for (size_t i = 0; i < g.nodes.size(); ++i)
@@ -347,7 +352,7 @@ struct GraphEmitter
     // windowed rings: the latency of a sector refill is hidden by other waves only, so keep at least two per SIMD
     const std::string bound = (p.rings == RingLayout::TRANSPOSED && p.totalRings == 1) ? ", 4" : ringTrips ? ", 1" : windowed ? ", 2"
                               : form.minWaves ? ", " + std::to_string(form.minWaves) : std::string();
-    s << "extern \"C\" __global__ __launch_bounds__(256" << bound << ") void mlgpu_graph_kernel(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
+    s << "extern \"C\" __global__ __launch_bounds__(256" << bound << ") void " << (listed ? "mlgpu_graph_listed_kernel" : "mlgpu_graph_kernel") << "(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
   }
   void sharedMemory()
   {
@@ -372,7 +377,16 @@ struct GraphEmitter
   {
     s << "  size_t blk = blockIdx.x;\n  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;\n"
          "  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);\n";
-    if (partialWaves)
+    if (listed)
+    {
+      // the lane's place in the list (vr), the place whose voice it runs and whose rows it stores to (pl), the voice (v): everything
+      // below that is made of v - tables, ring rows, input rows, control columns - is the gathered voice's
+      s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n";
+      if (partialWaves) s << "  if ((vr_0 & ~(size_t)63) >= a.listed) return;\n  const size_t pl_0 = vr_0 < a.listed ? vr_0 : a.listed - 1;\n";
+      else s << "  if (vr_0 >= a.listed) return;\n  const size_t pl_0 = vr_0;\n";
+      s << "  const size_t v_0 = a.voiceList[pl_0];\n  uint32_t pk_0 = 0u;\n";
+    }
+    else if (partialWaves)
       s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n  if ((vr_0 & ~(size_t)63) >= a.V) return;\n  const size_t v_0 = vr_0 < a.V ? vr_0 : a.V - 1;\n";
     else
       s << "  const size_t v_0 = blk * " << 256 * VL << " + threadIdx.x;\n  if (v_0 >= a.V) return;\n";
@@ -465,7 +479,7 @@ struct GraphEmitter
         else if (g.outputGroup[o])
           s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + (v" << sfx(l) << " / " << g.outputGroup[o] << ") * a.out[" << o << "].strideV;\n";
         else
-          s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + v" << sfx(l) << " * a.out[" << o << "].strideV;\n";
+          s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + " << (listed ? "pl" : "v") << sfx(l) << " * a.out[" << o << "].strideV;\n";
       }
     // a Downsample2x region's filter pairs its parent's samples (m - 1, m): the previous sample of each of its sources
     for (const Region& R : g.regions)
@@ -773,13 +787,16 @@ struct GraphEmitter
   // the quad's outputs: group sums and mixdowns through LDS, every other output straight to memory
   void outputStores()
   {
+    // the listed form: the running maximum of every output's |sample| bit patterns, before any mixdown (GraphArgs::peaks)
+    for (size_t o = 0; listed && o < g.outputs.size(); ++o)
+      s << "#pragma unroll\n      for (int kk = 0; kk < 4; ++kk)\n      {\n        const uint32_t mag = f2u(y" << o << "_0[kk]) & 0x7fffffffu;\n        pk_0 = mag > pk_0 ? mag : pk_0;\n      }\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
       if (ldsSum(o))
         s << "      group16_park(strip" << o << ", q & 3, y" << o << "_0);\n      if ((q & 3) == 3) group16_sum_store(strip" << o << ", out" << o << "_0 + t * a.out[" << o
           << "].strideT + (q - 3) * a.out[" << o << "].strideQ, a.out[" << o << "].strideQ);\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
       if (g.outputMix[o])
-        s << "      mix64_park(mstrip" << o << ", q & 3, " << (partialWaves ? "(vr_0 < a.V) ? y" + std::to_string(o) + "_0 : f32x4{0.f, 0.f, 0.f, 0.f}" : "y" + std::to_string(o) + "_0")
+        s << "      mix64_park(mstrip" << o << ", q & 3, " << (partialWaves ? "(vr_0 < " + places + ") ? y" + std::to_string(o) + "_0 : f32x4{0.f, 0.f, 0.f, 0.f}" : "y" + std::to_string(o) + "_0")
           << ");\n      if ((q & 3) == 3) mix64_sum_store(mstrip" << o << ", out" << o << "_0 + t * 64 + (q - 3) * 4);\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
       for (int l = 0; l < VL && !ldsSum(o) && !g.outputMix[o]; ++l)
@@ -802,6 +819,7 @@ struct GraphEmitter
     for (size_t i = 0; i < g.nodes.size(); ++i)
       if (g.nodes[i].type == NODE_PROC)
         for (int l = 0; l < VL; ++l) s << "  p" << i << sfx(l) << ".store(m" << i << sfx(l) << ");\n";
+    if (listed) s << "  if (a.peaks != nullptr && vr_0 < a.listed) a.peaks[vr_0] = pk_0;  // (a spare lane has no place in the list)\n";
     s << "}\n";
   }
 };
@@ -911,6 +929,24 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
                                            " rings) next to " + kib(ldsOther) + " of output strips and tables; a workgroup has 160 KiB");
   if (ldsOther > kLdsBytes)
     return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: " + kib(ldsOther) + " of LDS for the outputs summed inside the kernel (21 KiB per mixed-down output, 20.3 KiB per 16-voice group sum); a workgroup has 160 KiB");
+  // The listed form (mlgpu_graph_enable_voice_lists) gathers a wavefront's 64 voices from anywhere in the graph: what goes by lane or
+  // by a block's neighbouring voices has no listed form
+  if (g.voiceLists)
+  {
+    const std::string who = "graph_compile: voice lists (mlgpu_graph_enable_voice_lists): ";
+    if (p.rings != RingLayout::ROWS && p.totalRings)
+      return fail(MLGPU_ERR_UNSUPPORTED, who + "delay layout " + std::to_string(apiLayout(p.rings)) + (g.delayLayout == 3 ? " (what layout 3 resolves to for this graph)" : "") +
+                                             " keeps its rings in pieces made by the neighbouring voices of a 256-voice block; the rows are served: mlgpu_graph_set_delay_layout(g, 0)");
+    for (size_t o = 0; o < g.outputs.size(); ++o)
+    {
+      if (g.outputGroup[o]) return fail(MLGPU_ERR_UNSUPPORTED, who + "an output group sum (mlgpu_graph_set_output_group_sum) has no listed form");
+      if (g.outputMixShard[o]) return fail(MLGPU_ERR_UNSUPPORTED, who + "the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2)) has no listed form");
+    }
+    if (g.hasEventRows) return fail(MLGPU_ERR_UNSUPPORTED, who + "event rows (mlgpu_graph_add_event_row) go by lane, not by voice: no listed form");
+    for (const Region& R : g.regions)
+      if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X)
+        return fail(MLGPU_ERR_UNSUPPORTED, who + "a DOWNSAMPLE_2X region pairs DSPVectors by the graph's count, not by a voice's: no listed form");
+  }
   p.memVoices = p.rings != RingLayout::ROWS ? ((g.V + 255) & ~(size_t)255) : g.V;
   p.minWavesHook = hooks.minWaves;
   p.rowAddr64 = hooks.rowAddr64;

@@ -102,6 +102,7 @@ struct GraphDesc
   int delayLayout{0};            // as mlgpu_graph_set_delay_layout took it (3: the best of 2 / 4 / 1 for the graph)
   int voicesPerLane{0};          // 0 = choose at compile (graphVoicesPerLane); 1 or 2 = forced
   bool autotune{false};
+  bool voiceLists{false};        // a compile makes the listed form of the kernel too (mlgpu_graph_enable_voice_lists)
 };
 
 // Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them by planGraph)
@@ -117,10 +118,12 @@ inline int apiLayout(RingLayout r) { return r == RingLayout::SECTORS ? 4 : (int)
 inline RingLayout ringLayoutOfApi(int layout) { return layout == 4 ? RingLayout::SECTORS : layout == 3 ? RingLayout::WINDOWS : (RingLayout)layout; }  // (3: laid out as 1 where neither 2 nor 4 applies)
 
 // A graph kernel's form besides the graph: voices per lane, quads per trip of the sample loop, and the wavefronts per SIMD its
-// register budget must allow (0: the compiler's choice; generateBudgeted)
+// register budget must allow (0: the compiler's choice; generateBudgeted). `listed`: the kernel of mlgpu_graph_process_listed - a
+// lane's place in the launch is its position in the voice list, its voice GraphArgs::voiceList's entry there (one voice per lane)
 struct KernelForm
 {
   int voicesPerLane{1}, quadsPerTrip{1}, minWaves{0};
+  bool listed{false};
 };
 
 // Test hooks, not settings: the differential tests build a kernel's second form with these (environment variables, readTestHooks)

@@ -95,6 +95,12 @@ struct GraphArgs
   size_t t0;  // DSPVectors processed since the last clear (a Downsample2xFunction region pairs vectors 2k, 2k + 1)
   uint32_t flags;  // MLGPU_KFLAG_*
   EventsDev events;
+  // the listed form of a graph kernel (mlgpu_graph_process_listed): lane i of the launch runs voice voiceList[i] of the graph's V
+  // voices - tables, rings, input rows and control columns are read at the voice, out and peaks written at i; peaks[i] (or nullptr)
+  // gets the largest |sample| bit pattern of the voice's outputs in the launch. Else unused.
+  const uint32_t* voiceList;
+  size_t listed;  // the list's length K
+  uint32_t* peaks;
 };
 
 // row `row` of the state memory at the voice whose byte offset in a row is lane4: the row's address is wave-uniform (scalar

@@ -259,6 +259,27 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
                         std::string& err);
 size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four);  // (test hook: buffer addresses and capacity)
 
+// capi.hip — the voice list of a bank or a graph (mlgpu_bank_set_voice_list, mlgpu_graph_set_voice_list). The list in force lives in ONE
+// device buffer, written by copies on the engine's stream: a listed launch - a recorded one too, which has the address - reads
+// whatever the copies before it in stream order left. The host's copy goes through two pinned sets that take turns (DESIGN.md
+// §3.7, "Staging turns").
+struct mlgpu_voice_list
+{
+  DeviceBuffer<uint32_t> d_list;
+  size_t capacity{0};  // entries of d_list and of each pinned set
+  size_t reserved{0};  // reserve (0: none, the buffers grow inside set)
+  size_t size{0};      // of the list set last: the K of the next listed launch (host order is stream order)
+  struct Set
+  {
+    PinnedBuffer<uint32_t> h_list;
+  };
+  StagingTurns<Set> stage;
+  // `who`: the calling function's name for the engine's last error ("bank_set_voice_list"); nVoices: the owner's voice count
+  int grow(mlgpu_engine* e, size_t need, const char* who);  // buffers of `need` entries, the list in force carried over. Allocates and waits: setup only.
+  int reserve(mlgpu_engine* e, size_t maxListed, const char* who);
+  int set(mlgpu_engine* e, size_t nVoices, const uint32_t* h_voices, size_t n, const char* who);
+};
+
 // coeffs.cpp
 void mlgpu_build_impulse_table(float* out17);
 
