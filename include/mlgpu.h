@@ -556,6 +556,43 @@ int mlgpu_bank_process_listed(mlgpu_bank* b, size_t n_vectors, const float* d_in
                               float* d_out, int out_layout, uint32_t* d_peak);
 int mlgpu_bank_process_listed_mixdown(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout,
                                       const float* d_gains, float* d_out, uint32_t* d_peak);
+/* LISTED GROUP SUMS: one mixed channel per instrument of the listed voices - mlgpu_bank_process_groups' output (Synth::processVector's
+ * voice sum) at the price of a voice list. The bank's voices are instruments of G = out_group adjacent voices: instrument c = voices
+ * c G ... c G + G - 1, G one of 2, 4, 8, 16, n_voices a multiple of G. With the list L[0 .. K) in force:
+ *   The listed instruments M[0 .. J) are the distinct values of L[i] / G in ascending order.
+ *   d_out is a signal of J rows in `out_layout`: 64 * n_vectors * J floats, written once.
+ *   Row j is ((0 + g y[a0]) + g y[a1]) + ... over the listed voices a0 < a1 < ... of instrument M[j]: float32 adds in the engine's
+ *   floating-point mode, y the float mlgpu_bank_process_listed stores for that voice, g = d_gains[voice] (d_gains[n_voices], one
+ *   float multiply; d_gains == NULL: no multiply at all). A lone -0.0 voice gives +0.0. With every voice listed the call gives the
+ *   bits of mlgpu_bank_process_groups.
+ *   Everything else is the VOICE LISTS rule: coefficients, state, the input constant, the gain and the input row are the voice's - with
+ *   in_group P (1, 2, 4, 8, 16) the row is L[i] / P of a signal of n_voices / P rows, MLGPU_LAYOUT_BROADCAST only with P = 1 -,
+ *   d_peak[K] is addressed by list position and taken before the gain, unlisted voices are neither read nor written and no time
+ *   passes for them, and any split of n_vectors into several launches with the same list gives the bits of one launch.
+ *
+ * mlgpu_bank_reserve_voice_list_groups(max_listed, out_group) is the setup call: it allocates and may wait. It does what
+ * mlgpu_bank_reserve_voice_list(max_listed) does, declares G for this bank and sizes the buffers of the LANE PLAN for the worst case
+ * of max_listed voices. The plan is made on the host: a listed instrument's voices are consecutive list positions, but their in-order
+ * sum cannot cross a 64-lane wavefront, so a run that does not fit into the rest of a wavefront starts at the next one and the
+ * lanes in between idle - at most 64 * ceil(K / (65 - G)) lanes for K voices. From then on every mlgpu_bank_set_voice_list also makes
+ * and uploads the plan, with unchanged discipline: validated completely before anything is enqueued, in the same staging turn,
+ * stream-ordered, never waiting except for its own call before last, never allocating. The list in force at the time of the reserve
+ * call gets its plan in that call. mlgpu_bank_process_listed and _listed_mixdown keep working on the same list with the same bits.
+ * out_group 0 turns the plan off again. A later mlgpu_bank_reserve_voice_list(max_listed) resizes the plan's buffers with the list's.
+ * mlgpu_bank_listed_group_count: J of the list in force (0 without a plan). mlgpu_bank_listed_groups: M[0 .. J) into h_groups, from
+ * the host's copy - no device wait (MLGPU_ERR_RANGE: capacity < J).
+ *
+ * mlgpu_bank_process_listed_groups never allocates. With an empty list it launches nothing and returns MLGPU_OK: J = 0, there is
+ * nothing to write. MLGPU_ERR_INVALID: no mlgpu_bank_reserve_voice_list_groups on this bank; an in_group outside 1, 2, 4, 8, 16; an
+ * input group without d_in or with a broadcast input; n_voices not whole groups; null or misaligned signals (16 bytes), gains or
+ * peaks (4 bytes); a bad layout; a call while recording a sequence - the launch's lane count and J go with the list's contents, not
+ * only its length, so a recorded launch could not follow a later list. MLGPU_ERR_UNSUPPORTED, with nothing launched and the state
+ * untouched, as mlgpu_bank_process_groups: a bank that is not one of the ahead-of-time chain kernels. */
+int mlgpu_bank_reserve_voice_list_groups(mlgpu_bank* b, size_t max_listed, int out_group);
+size_t mlgpu_bank_listed_group_count(mlgpu_bank* b);
+int mlgpu_bank_listed_groups(mlgpu_bank* b, uint32_t* h_groups, size_t capacity);
+int mlgpu_bank_process_listed_groups(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
+                                     const float* d_gains, float* d_out, int out_layout, uint32_t* d_peak);
 /* 1 if the chain maps to a single fused kernel, 0 if it runs processor by processor. */
 int mlgpu_bank_is_fused(mlgpu_bank* b);
 /* Name of the device kernel that dominates mlgpu_bank_process (for profile lookup). */

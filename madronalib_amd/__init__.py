@@ -1044,6 +1044,33 @@ class Bank(_Handle):
         pp = None if d_peak is None else ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
         self.engine._check(self.L.mlgpu_bank_process_listed_mixdown(self.h, int(n_vectors), pin, int(in_layout), pg, pout, pp))
 
+    def reserve_voice_list_groups(self, max_listed, out_group):
+        """Setup: reserve_voice_list(max_listed), and the bank's voices are instruments of out_group (2, 4, 8, 16) adjacent voices -
+        from now on set_voice_list also makes and uploads the lane plan process_listed_groups runs by; 0 turns the plan off
+        (mlgpu_bank_reserve_voice_list_groups)."""
+        self.engine._check(self.L.mlgpu_bank_reserve_voice_list_groups(self.h, int(max_listed), int(out_group)))
+
+    @property
+    def listed_groups(self):
+        """The listed instruments M[0 .. J): the distinct list[i] // out_group, ascending, as a numpy uint32 array - from the host's
+        copy, no device wait (mlgpu_bank_listed_groups)."""
+        m = np.zeros(int(self.L.mlgpu_bank_listed_group_count(self.h)), np.uint32)
+        self.engine._check(self.L.mlgpu_bank_listed_groups(self.h, _np_ptr(m) if m.size else None, m.size))
+        return m
+
+    def process_listed_groups(self, n_vectors, d_out, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, in_group=1, d_gains=None,
+                              d_peak=None):
+        """process_groups of the listed voices only: d_out has one row per listed instrument (J = len(listed_groups) rows), the in-order
+        sum ((0 + g y0) + g y1) + ... of the instrument's listed voices; d_in (if any) has V / in_group rows of which a voice reads
+        row voice // in_group, d_gains [V] is indexed by voice, d_peak [K] by list position and taken before the gain. Not while
+        recording a sequence (mlgpu_bank_process_listed_groups)."""
+        pin = None if d_in is None else ctypes.c_void_p(d_in.ptr if hasattr(d_in, "ptr") else int(d_in))
+        pout = ctypes.c_void_p(d_out.ptr if hasattr(d_out, "ptr") else int(d_out))
+        pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
+        pp = None if d_peak is None else ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
+        self.engine._check(self.L.mlgpu_bank_process_listed_groups(self.h, int(n_vectors), pin, int(in_layout), int(in_group), pg, pout,
+                                                                   int(out_layout), pp))
+
     def process_groups_host(self, n_vectors, out_group, in_signal=None, in_group=1, gains=None, layout=Layout.QUAD, in_layout=None):
         """Test convenience beside process_host: in_signal [V / in_group][64T] and the result [V / out_group][64T] are VOICE_MAJOR
         numpy, gains [V] numpy or None; the kernel writes `layout` and reads `in_layout` (default: the same)."""

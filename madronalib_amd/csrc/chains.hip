@@ -58,6 +58,15 @@ hipError_t launchChainListedMix(const ChainArgs& a, hipStream_t stream, int /*cu
   return hipGetLastError();
 }
 
+// the listed voices summed by instrument (mlgpu_bank_process_listed_groups): a.V is the lane plan's length N
+template <bool HAS_SIGNAL, int... KS>
+hipError_t launchChainListedGroups(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
+{
+  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
+  hipLaunchKernelGGL((chain_listed_group_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
+  return hipGetLastError();
+}
+
 // the group form (mlgpu_bank_process_groups): outGroup picks the instantiation, a.inGroupShift and a.mixGains travel as arguments
 template <bool HAS_SIGNAL, int... KS>
 hipError_t launchChainGroups(const ChainArgs& a, int outGroup, hipStream_t stream)
@@ -175,6 +184,8 @@ ChainEntry makeEntry(const char* name)
   e.launchGroupsConst = &launchChainGroups<false, KS...>;
   e.launchListedSignal = &launchChainListed<true, KS...>;
   e.launchListedConst = &launchChainListed<false, KS...>;
+  e.launchListedGroupsSignal = &launchChainListedGroups<true, KS...>;
+  e.launchListedGroupsConst = &launchChainListedGroups<false, KS...>;
   // what a profiler prints for this kernel: "chain_kernel<mldev::Chain<2, 18, 48>, false>(ChainArgs)";
   // `name` is the human-readable alias used in logs.
   static const std::string profName = [] {

@@ -386,6 +386,148 @@ __global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArg
   chain_kernel_body<CH, HAS_SIGNAL, false, OUT_G>(a);
 }
 
+// ---- the listed voices summed by instrument (chain_listed_group_kernel, mlgpu_bank_process_listed_groups) ----
+// chain_listed_kernel's voices, chain_group_kernel's output: row j of a.out is ((0 + g y[a0]) + g y[a1]) + ... over the listed voices
+// of the j-th listed instrument, in voice order. The group size is data - it is in the host's lane plan (a.lanePlan, see ChainArgs),
+// not in the code: one instantiation per chain and input kind. A body of its own, so that the forms above stay the code they were.
+//
+// run_voice's loop with the peak of the LISTED form, then the gain, then mldsp_math.hpp's segment_park / segment_sum_store through the
+// wavefront's LDS strip: every fourth quad the segment's last lane stores four quads to the segment's row (consecutive segments,
+// consecutive rows: in the QUAD layout a wavefront's stores are close to each other). There is no workgroup barrier in the loop.
+template <class CH, bool HAS_SIGNAL, int HEAD>
+__device__ __forceinline__ void run_voice_listed_groups(CH& ch, const ChainArgs& a, size_t vs, size_t row, unsigned rank, unsigned length, int longest,
+                                                        float xc, float* strip, uint32_t* peak)
+{
+  static_assert(HEAD != kHeadTrip || (!HAS_SIGNAL && CH::kHeadHasTrip), "trips want a launch-constant input and a head that has them");
+  uint32_t pk = 0;
+  const float gain = a.mixGains ? a.mixGains[vs] : 1.f;
+  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (vs >> a.inGroupShift) * a.in.strideV : nullptr;
+  f32x4* pout = (f32x4*)a.out.base + row * a.out.strideV;
+  const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
+  const uint32_t slot = wave_slot();
+  for (size_t t = 0; t < a.T; ++t)
+  {
+    const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
+    f32x4* po = pout + t * a.out.strideT;
+    float s[kHeadTripSamples];  // (kHeadTrip: the trip the quad belongs to)
+#pragma unroll 4
+    for (int q = 0; q < 16; ++q)
+    {
+      if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
+      f32x4 y;
+      if constexpr (HEAD == kHeadTrip)
+      {
+        static_assert(kHeadTripSamples == 8, "a trip is two quads");
+        if ((q & 1) == 0) ch.template next_head_trip<kHeadTripSamples>(xc, s);
+        y = (q & 1) ? f32x4{s[4], s[5], s[6], s[7]} : f32x4{s[0], s[1], s[2], s[3]};
+      }
+      else
+      {
+        f32x4 x = {xc, xc, xc, xc};
+        if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
+        y.x = ch.template next_head<HEAD == kHeadFast>(x.x);
+        y.y = ch.template next_head<HEAD == kHeadFast>(x.y);
+        y.z = ch.template next_head<HEAD == kHeadFast>(x.z);
+        y.w = ch.template next_head<HEAD == kHeadFast>(x.w);
+      }
+      const uint32_t m0 = f2u(y.x) & 0x7fffffffu, m1 = f2u(y.y) & 0x7fffffffu, m2 = f2u(y.z) & 0x7fffffffu, m3 = f2u(y.w) & 0x7fffffffu;
+      const uint32_t m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3, m = m01 > m23 ? m01 : m23;
+      pk = pk > m ? pk : m;
+      if (a.mixGains)  // (the same in all lanes: a kernel argument. Without gains there is no multiply at all)
+      {
+        y.x *= gain;
+        y.y *= gain;
+        y.z *= gain;
+        y.w *= gain;
+      }
+      segment_park(strip, q & 3, y);
+      if ((q & 3) == 3) segment_sum_store(strip, rank, length, longest, po + (size_t)(q - 3) * outQ, outQ);
+    }
+    ch.end_vector();
+  }
+  *peak = pk;
+}
+
+// ... in the head mode the wavefront has chosen (the same in all lanes), as run_voice_as
+template <class CH, bool HAS_SIGNAL>
+__device__ __forceinline__ void run_voice_listed_groups_as(int head, CH& ch, const ChainArgs& a, size_t vs, size_t row, unsigned rank, unsigned length,
+                                                           int longest, float xc, float* strip, uint32_t* peak)
+{
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  {
+    if (head == kHeadTrip)
+    {
+      run_voice_listed_groups<CH, HAS_SIGNAL, kHeadTrip>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
+      return;
+    }
+  }
+  if (head != kHeadGeneral)
+    run_voice_listed_groups<CH, HAS_SIGNAL, kHeadFast>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
+  else
+    run_voice_listed_groups<CH, HAS_SIGNAL, kHeadGeneral>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
+}
+
+// Lane l of the launch - found from block and thread exactly as in chain_kernel_body, XCD remap included - runs the voice of its plan
+// entry. Three things the pads decide:
+// 1. A pad takes no part in the wave-uniform head choice: it has left the kernel before the ballots behind fastHead / kHeadTrip are
+//    taken (a ballot counts the lanes that execute it), and the predicates are masked with `!pad` besides, so the choice is the one
+//    the wavefront's voices alone would get.
+// 2. The impulse table's __syncthreads() comes first, before any lane leaves; there is no workgroup barrier after it.
+// 3. The lanes of the last wavefront at or past N have no plan entry: they are pads without reading one. Whole wavefronts at or
+//    past N leave like chain_kernel's.
+// A pad lane loads nothing, runs nothing and stores nothing: no table word, no peak, no output, no strip entry.
+template <class CH, bool HAS_SIGNAL>
+__device__ __forceinline__ void chain_listed_group_body(const ChainArgs& a)
+{
+  apply_fp_mode(a.flags);
+  __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
+  __shared__ __attribute__((aligned(16))) float ldsStrips[(kChainBlock / 64) * kSegmentStrip + kSegmentTail];
+  float* const strip = ldsStrips + (threadIdx.x >> 6) * kSegmentStrip;
+  if constexpr (CH::kHasImpulse)
+  {
+    if (threadIdx.x < Proc<MLGPU_PROC_IMPULSE_GEN>::kTableSize) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];
+    __syncthreads();
+  }
+  size_t blk = blockIdx.x;
+  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
+  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);
+  const size_t l = blk * kChainBlock + threadIdx.x;
+  if (l >= a.V) return;
+  const uint4 plan = ((const uint4*)a.lanePlan)[l];
+  const bool pad = plan.x == 0xFFFFFFFFu;
+  if (pad) return;
+  const size_t vs = plan.x;
+  const unsigned rank = plan.w & 0xFFu, length = plan.w >> 8;
+
+  CH ch;
+  const VoiceMem mem{a.coeffs + vs, a.state + vs, a.tableStride};
+  const KernelTables tables{ldsTable};
+  ch.load(mem, tables);
+
+  const float xc = (!HAS_SIGNAL && a.inConst) ? a.inConst[vs] : 0.f;
+
+  // the head's loop body, once per wavefront: as chain_kernel_body decides it, over the lanes that are voices
+  bool fastHead = false;
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(!pad && CH::head_input_is_odd(xc)) == 0);
+  int head = fastHead ? kHeadFast : kHeadGeneral;
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  {
+    if (fastHead && __builtin_amdgcn_ballot_w64(!pad && trip_freq_is_dense(xc, kHeadTripSamples)) == 0) head = kHeadTrip;
+  }
+  uint32_t pk = 0;
+  // the wavefront's longest segment, rounded up to a size segment_sum_store has the reads of
+  const int longest = __builtin_amdgcn_ballot_w64(length > 8u) ? 16 : (__builtin_amdgcn_ballot_w64(length > 4u) ? 8 : (__builtin_amdgcn_ballot_w64(length > 2u) ? 4 : 2));
+  run_voice_listed_groups_as<CH, HAS_SIGNAL>(head, ch, a, vs, plan.z, rank, length, longest, xc, strip, &pk);
+  ch.store(mem);
+  if (a.peaks != nullptr) a.peaks[plan.y] = pk;  // (the same in all lanes: a kernel argument)
+}
+
+template <class CH, bool HAS_SIGNAL>
+__global__ __launch_bounds__(kChainBlock) void chain_listed_group_kernel(const ChainArgs a)
+{
+  chain_listed_group_body<CH, HAS_SIGNAL>(a);
+}
+
 // ---------------------------------------------------------------------------------------------
 // cascade_kernel — N identical SVF sections in series (config 4), evaluated STAGE-SKEWED.
 //

@@ -164,6 +164,94 @@ MLD void group16_sum_store(const float* strip, group16_f32x4* outQuad0, size_t s
   __builtin_amdgcn_wave_barrier();
 }
 
+// The same sums over SEGMENTS of a wavefront's lanes: runs of 1 .. 16 consecutive lanes that start anywhere (the listed voices of
+// one instrument, laid out by the host: voice_list.hpp, mlvl::planGroups), which no row of 16 confines - hence LDS, not the lane
+// shifts. Every lane that takes part parks its quads for four consecutive quads at its own place of the wavefront's strip,
+// [quad][lane][4]; then the LAST lane of each segment (rank == length - 1) starts from +0.0 and adds its segment's entries in rank
+// order, quad by quad - ds_read_b128, four adds per entry - and stores the four quads of sums. Lanes of the wavefront that are not
+// there (pads, which have left the kernel) are never added: an entry belongs to the segment of the lane that adds it.
+// `longest` is the wavefront's longest segment rounded up to 2, 4, 8 or 16 (wave-uniform): the reads of a quad are that many, issued
+// up to eight at a time before the first add - one or two LDS round trips per quad, not one per entry - and a lane whose segment is shorter reads on past
+// its segment's end (its own later entries, the next quad's, or the tail behind the workgroup's last strip: never added). Parking
+// four quads pays the fences and the turn-around from write to read once per 16 samples.
+// No pad words between entries: ds_read_b128 takes its lanes in four groups of 16 whose lane numbers are all different mod 16, a
+// 16-byte slot's banks are (entry mod 16) * 4 .. + 3, and at step d a last lane l of a segment of n reads entry l - (n - 1) + d - so
+// with equal lengths in a group of 16 no two reads share a bank, and ragged lengths cost an extra cycle only where two of a
+// group's segments happen to differ by a multiple of 16 entries. The writes are 16 contiguous bytes per lane.
+// LDS operations of one wavefront complete in issue order; the fences only keep the compiler from moving them across each other.
+constexpr int kSegmentQuad = 64 * 4;             // floats per parked quad of a wavefront
+constexpr int kSegmentStrip = 4 * kSegmentQuad;  // floats per wavefront
+constexpr int kSegmentTail = 16 * 4;             // floats behind a workgroup's last strip, for the reads past a segment's end
+MLD void segment_park(float* strip, int qq, group16_f32x4 y)
+{
+  *(group16_f32x4*)(strip + qq * kSegmentQuad + (threadIdx.x & 63u) * 4u) = y;
+}
+template <int N>
+MLD group16_f32x4 segment_sum_quad(const group16_f32x4* p, unsigned length)
+{
+  // (at most 8 entries - 32 registers - in flight: a segment of 16 takes two round trips, and the kernel keeps chain_listed_kernel's
+  // four wavefronts per SIMD)
+  constexpr int B = N < 8 ? N : 8;
+  group16_f32x4 acc = {0.f, 0.f, 0.f, 0.f};  // ((0 + x0) + x1) + ...: a lone -0.0 gives +0.0
+#pragma unroll
+  for (int b = 0; b < N; b += B)
+  {
+    group16_f32x4 x[B];
+#pragma unroll
+    for (int d = 0; d < B; ++d) x[d] = p[b + d];
+#pragma unroll
+    for (int d = 0; d < B; ++d)
+    {
+      if ((unsigned)(b + d) < length)
+      {
+        acc.x = acc.x + x[d].x;
+        acc.y = acc.y + x[d].y;
+        acc.z = acc.z + x[d].z;
+        acc.w = acc.w + x[d].w;
+      }
+    }
+    if (b + B < N) __builtin_amdgcn_sched_barrier(0);  // (the next batch's reads stay behind this batch's adds)
+  }
+  return acc;
+}
+template <int N>
+MLD void segment_sum_store_n(const float* first, unsigned length, group16_f32x4* outQuad0, size_t strideQ)
+{
+  if constexpr (N <= 2)  // (all four quads' reads in flight at once: 32 registers)
+  {
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq)
+      __builtin_nontemporal_store(segment_sum_quad<N>((const group16_f32x4*)(first + qq * kSegmentQuad), length), outQuad0 + (size_t)qq * strideQ);
+  }
+  else
+  {
+#pragma unroll 1
+    for (int qq = 0; qq < 4; ++qq)
+      __builtin_nontemporal_store(segment_sum_quad<N>((const group16_f32x4*)(first + qq * kSegmentQuad), length), outQuad0 + (size_t)qq * strideQ);
+  }
+}
+// ... after the fourth quad: the segment's last lane stores the sums of quads 0 .. 3 to outQuad0 + 0 .. 3 * strideQ
+MLD void segment_sum_store(const float* strip, unsigned rank, unsigned length, int longest, group16_f32x4* outQuad0, size_t strideQ)
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (rank + 1u == length)
+  {
+    const float* first = strip + ((threadIdx.x & 63u) - rank) * 4u;
+    if (longest <= 2)
+      segment_sum_store_n<2>(first, length, outQuad0, strideQ);
+    else if (longest <= 4)
+      segment_sum_store_n<4>(first, length, outQuad0, strideQ);
+    else if (longest <= 8)
+      segment_sum_store_n<8>(first, length, outQuad0, strideQ);
+    else
+      segment_sum_store_n<16>(first, length, outQuad0, strideQ);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // clamp(x, lo, hi) = min(max(x, lo), hi) (MLDSPOps.h:747) in TWO instructions instead of six, for the common case the graph
 // generator can prove: lo and hi are constants of the kernel, neither NaN nor zero, lo <= hi, and x is the result of an
 // arithmetic instruction (so never a signaling NaN). v_max_f32 / v_min_f32 differ from maxps / minps only (a) when the SECOND

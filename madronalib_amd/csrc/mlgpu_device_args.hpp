@@ -47,6 +47,13 @@ struct ChainArgs
   const uint32_t* voiceList = nullptr;
   size_t tableStride = 0;
   uint32_t* peaks = nullptr;
+  // chain_listed_group_kernel (mlgpu_bank_process_listed_groups): the launch is V = N lanes laid out by the host (voice_list.hpp:
+  // mlvl::planGroups), lane l's plan entry is the four words lanePlan[4 l .. 4 l + 3], one 16-byte load:
+  //   .x voice (0xFFFFFFFF: a pad lane, which runs nothing)   .y list position i (peaks[i])
+  //   .z output row j of `out`, a signal of J rows             .w rank | length << 8 of the lane in its segment
+  // A segment - the listed voices of one instrument - never crosses a multiple of 64 lanes. coeffs / state / inConst / mixGains are
+  // read at the voice, `in` at row voice >> inGroupShift, tableStride is the bank's voice count. Else unused.
+  const uint32_t* lanePlan = nullptr;
 };
 
 // EventsToSignals settings the device needs (events.hip, mldsp_events.hpp)

@@ -176,6 +176,7 @@ struct ChainEntry
   ChainGroupLauncher launchGroupsSignal{nullptr}, launchGroupsConst{nullptr};  // chain_group_kernel (voices in groups of 1, 2, 4, 8, 16): the chain kernels, not the cascades
   // chain_listed_kernel / chain_listed_mix_kernel (the voices of a list): where chain_group_kernel / chain_mix_kernel are
   ChainLauncher launchListedSignal{nullptr}, launchListedConst{nullptr}, launchListedMixSignal{nullptr}, launchListedMixConst{nullptr};
+  ChainLauncher launchListedGroupsSignal{nullptr}, launchListedGroupsConst{nullptr};  // chain_listed_group_kernel (the listed voices summed by instrument)
   const char* kernelName;  // prefix of the name a profiler shows for the device kernel
   const char* (*kernelNameFor)(size_t V, uint32_t flags){nullptr};  // where the kernel depends on the bank's size (SVF cascades)
   const char* alias;       // e.g. "chain_kernel<SawGen,Bandpass,Gain>"
@@ -269,14 +270,24 @@ struct mlgpu_voice_list
   size_t capacity{0};  // entries of d_list and of each pinned set
   size_t reserved{0};  // reserve (0: none, the buffers grow inside set)
   size_t size{0};      // of the list set last: the K of the next listed launch (host order is stream order)
+  // the lane plan of the listed group sum (mlgpu_bank_reserve_voice_list_groups; voice_list.hpp: mlvl::planGroups). outGroup == 0:
+  // none, and nothing below is touched. Else every `set` makes the plan in its staging set and uploads it behind the list.
+  int outGroup{0};
+  DeviceBuffer<uint32_t> d_plan;     // [mlvl::kLaneWords][planCapacity]
+  size_t planCapacity{0};            // lanes of d_plan and of each pinned set: mlvl::maxPlanLanes(reserved, outGroup)
+  size_t planLanes{0}, planGroups{0};  // N and J of the list in force
+  std::vector<uint32_t> groups;      // M[0 .. J) of the list in force (the host's copy: mlgpu_bank_listed_groups); sized at the reserve
   struct Set
   {
     PinnedBuffer<uint32_t> h_list;
+    PinnedBuffer<uint32_t> h_plan;
+    std::vector<uint32_t> h_groups;
   };
   StagingTurns<Set> stage;
   // `who`: the calling function's name for the engine's last error ("bank_set_voice_list"); nVoices: the owner's voice count
   int grow(mlgpu_engine* e, size_t need, const char* who);  // buffers of `need` entries, the list in force carried over. Allocates and waits: setup only.
-  int reserve(mlgpu_engine* e, size_t maxListed, const char* who);
+  // newOutGroup: -1 keeps the plan's group size (and resizes its buffers with the list's), 0 turns the plan off, 2 / 4 / 8 / 16 set it
+  int reserve(mlgpu_engine* e, size_t maxListed, const char* who, int newOutGroup = -1);
   int set(mlgpu_engine* e, size_t nVoices, const uint32_t* h_voices, size_t n, const char* who);
 };
 

@@ -34,4 +34,39 @@ int validate(const uint32_t* list, size_t n, size_t nVoices, size_t reserved, ch
   }
   return MLGPU_OK;
 }
+
+LanePlan planGroups(const uint32_t* list, size_t n, unsigned G, uint32_t* lanes, uint32_t* groups)
+{
+  LanePlan plan{0, 0};
+  size_t i = 0;
+  while (i < n)
+  {
+    const uint32_t c = list[i] / G;
+    size_t len = 1;
+    while (i + len < n && list[i + len] / G == c) ++len;  // (ascending and distinct: at most G of them)
+    const size_t room = kWave - plan.lanes % kWave;
+    if (len > room)
+    {
+      for (size_t p = 0; p < room; ++p)
+      {
+        uint32_t* w = lanes + kLaneWords * (plan.lanes + p);
+        w[0] = kPad;
+        w[1] = w[2] = w[3] = 0;
+      }
+      plan.lanes += room;
+    }
+    for (size_t r = 0; r < len; ++r)
+    {
+      uint32_t* w = lanes + kLaneWords * (plan.lanes + r);
+      w[0] = list[i + r];
+      w[1] = (uint32_t)(i + r);
+      w[2] = (uint32_t)plan.groups;
+      w[3] = (uint32_t)r | ((uint32_t)len << 8);
+    }
+    groups[plan.groups++] = c;
+    plan.lanes += len;
+    i += len;
+  }
+  return plan;
+}
 }  // namespace mlvl
