@@ -25,63 +25,28 @@ static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGr
 
 namespace
 {
-template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChain(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
+// the launch of every form of the chain kernel: a lane per a.V (the bank's voices, a list's length, a lane plan's length)
+template <void (*KERNEL)(const ChainArgs)>
+hipError_t launchChain(const ChainArgs& a, hipStream_t stream, int /*outGroup*/)
 {
   const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL((chain_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
-  return hipGetLastError();
-}
-
-template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChainMix(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
-{
-  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL((chain_mix_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
-  return hipGetLastError();
-}
-
-// the voice-list forms (mlgpu_bank_process_listed, _listed_mixdown): a.V is the list's length
-template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChainListed(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
-{
-  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL((chain_listed_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
-  return hipGetLastError();
-}
-
-template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChainListedMix(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
-{
-  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL((chain_listed_mix_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
-  return hipGetLastError();
-}
-
-// the listed voices summed by instrument (mlgpu_bank_process_listed_groups): a.V is the lane plan's length N
-template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChainListedGroups(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
-{
-  const unsigned blocks = (unsigned)((a.V + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL((chain_listed_group_kernel<Chain<KS...>, HAS_SIGNAL>), dim3(blocks), dim3(kChainBlock), 0, stream, a);
+  hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(kChainBlock), 0, stream, a);
   return hipGetLastError();
 }
 
 // the group form (mlgpu_bank_process_groups): outGroup picks the instantiation, a.inGroupShift and a.mixGains travel as arguments
 template <bool HAS_SIGNAL, int... KS>
-hipError_t launchChainGroups(const ChainArgs& a, int outGroup, hipStream_t stream)
+hipError_t launchChainGroups(const ChainArgs& a, hipStream_t stream, int outGroup)
 {
-  const dim3 blocks((unsigned)((a.V + kChainBlock - 1) / kChainBlock)), block(kChainBlock);
   switch (outGroup)
   {
-    case 1: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 1>), blocks, block, 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 2>), blocks, block, 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 4>), blocks, block, 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 8>), blocks, block, 0, stream, a); break;
-    case 16: hipLaunchKernelGGL((chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 16>), blocks, block, 0, stream, a); break;
+    case 1: return launchChain<chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 1>>(a, stream, 0);
+    case 2: return launchChain<chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 2>>(a, stream, 0);
+    case 4: return launchChain<chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 4>>(a, stream, 0);
+    case 8: return launchChain<chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 8>>(a, stream, 0);
+    case 16: return launchChain<chain_group_kernel<Chain<KS...>, HAS_SIGNAL, 16>>(a, stream, 0);
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 // How many wavefront lanes share one channel of a head-less SVF cascade (cascade_lanes_kernel). One lane per channel is the
@@ -110,7 +75,7 @@ hipError_t launchLanes(const ChainArgs& a, hipStream_t stream)
 }
 
 template <bool HAS_SIGNAL, int KIND, int N, int... HEADS>
-hipError_t launchCascade(const ChainArgs& a, hipStream_t stream, int /*cuCount*/)
+hipError_t launchCascade(const ChainArgs& a, hipStream_t stream, int /*outGroup*/)
 {
   if constexpr (sizeof...(HEADS) == 0)
   {
@@ -157,8 +122,8 @@ ChainEntry makeCascadeEntry(const char* name)
   ChainEntry e;
   e.kinds = {HEADS...};
   for (int s = 0; s < N; ++s) e.kinds.push_back(KIND);
-  e.launchSignal = &launchCascade<true, KIND, N, HEADS...>;
-  e.launchConst = &launchCascade<false, KIND, N, HEADS...>;
+  e.launch[kFormPlain][1] = &launchCascade<true, KIND, N, HEADS...>;
+  e.launch[kFormPlain][0] = &launchCascade<false, KIND, N, HEADS...>;
   static const std::string profName = [] {
     std::string n = "cascade_kernel<mldev::Chain<";
     const int hs[] = {HEADS..., 0};
@@ -178,14 +143,14 @@ ChainEntry makeEntry(const char* name)
 {
   ChainEntry e;
   e.kinds = {KS...};
-  e.launchSignal = &launchChain<true, KS...>;
-  e.launchConst = &launchChain<false, KS...>;
-  e.launchGroupsSignal = &launchChainGroups<true, KS...>;
-  e.launchGroupsConst = &launchChainGroups<false, KS...>;
-  e.launchListedSignal = &launchChainListed<true, KS...>;
-  e.launchListedConst = &launchChainListed<false, KS...>;
-  e.launchListedGroupsSignal = &launchChainListedGroups<true, KS...>;
-  e.launchListedGroupsConst = &launchChainListedGroups<false, KS...>;
+  e.launch[kFormPlain][1] = &launchChain<chain_kernel<Chain<KS...>, true>>;
+  e.launch[kFormPlain][0] = &launchChain<chain_kernel<Chain<KS...>, false>>;
+  e.launch[kFormGroups][1] = &launchChainGroups<true, KS...>;
+  e.launch[kFormGroups][0] = &launchChainGroups<false, KS...>;
+  e.launch[kFormListed][1] = &launchChain<chain_listed_kernel<Chain<KS...>, true>>;
+  e.launch[kFormListed][0] = &launchChain<chain_listed_kernel<Chain<KS...>, false>>;
+  e.launch[kFormListedGroups][1] = &launchChain<chain_listed_group_kernel<Chain<KS...>, true>>;
+  e.launch[kFormListedGroups][0] = &launchChain<chain_listed_group_kernel<Chain<KS...>, false>>;
   // what a profiler prints for this kernel: "chain_kernel<mldev::Chain<2, 18, 48>, false>(ChainArgs)";
   // `name` is the human-readable alias used in logs.
   static const std::string profName = [] {
@@ -206,10 +171,10 @@ template <int... KS>
 ChainEntry makeMixEntry(const char* name)
 {
   ChainEntry e = makeEntry<KS...>(name);
-  e.launchMixSignal = &launchChainMix<true, KS...>;
-  e.launchMixConst = &launchChainMix<false, KS...>;
-  e.launchListedMixSignal = &launchChainListedMix<true, KS...>;
-  e.launchListedMixConst = &launchChainListedMix<false, KS...>;
+  e.launch[kFormMix][1] = &launchChain<chain_mix_kernel<Chain<KS...>, true>>;
+  e.launch[kFormMix][0] = &launchChain<chain_mix_kernel<Chain<KS...>, false>>;
+  e.launch[kFormListedMix][1] = &launchChain<chain_listed_mix_kernel<Chain<KS...>, true>>;
+  e.launch[kFormListedMix][0] = &launchChain<chain_listed_mix_kernel<Chain<KS...>, false>>;
   return e;
 }
 

@@ -78,33 +78,29 @@ struct MixStrips<true>
   }
 };
 
-// the streaming loop of one voice: T DSPVectors, 16 quads each, one 16-byte access per quad
-// (SCALED: the summing form with per-voice gains and / or spare lanes in the wavefront - a loop of its own, so that the plain one
-// pays nothing for them)
-// (LISTED: the voice-list forms - what belongs to the voice, its gain and its input row, is at voice vs, what the launch produces at
-// the lane's list position v; *peak gets the largest bits(y) & 0x7fffffff of the launch, y before any gain, kept in a register)
-// HEAD: how the head processor takes a launch-constant input, decided once per wavefront (chain_kernel_body) - kHeadGeneral: per
+// ---- the streaming loop of one voice, the same for every form of the chain kernel ----
+// T DSPVectors, 16 quads each, one 16-byte access per quad. The forms differ in two places only: which row of a.in the voice reads
+// (vin >> inShift: the voice, and the input group's shift or 0) and what becomes of a finished quad (the SINK, below).
+// HEAD: how the head processor takes a launch-constant input, decided once per wavefront (choose_head) - kHeadGeneral: per
 // sample, range test included; kHeadFast: per sample, the range test done; kHeadTrip: 8 samples (two quads) at a time, the polyBLEP
 // corrections once per zone per trip (Chain::next_head_trip) - same bits, about a third fewer instructions.
+// PEAK: the largest bits(y) & 0x7fffffff of the launch, y before any gain, kept in a register and returned (0 without PEAK).
 constexpr int kHeadGeneral = 0, kHeadFast = 1, kHeadTrip = 2;
 constexpr int kHeadTripSamples = 8;
 
-template <class CH, bool HAS_SIGNAL, int HEAD, bool MIX = false, bool SCALED = false, bool LISTED = false>
-__device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip = nullptr, bool live = true, size_t vs = 0,
-                                          uint32_t* peak = nullptr)
+template <class CH, bool HAS_SIGNAL, int HEAD, bool PEAK, class SINK>
+__device__ __forceinline__ uint32_t stream_voice(CH& ch, const ChainArgs& a, size_t vin, uint32_t inShift, float xc, SINK sink)
 {
   static_assert(HEAD != kHeadTrip || (!HAS_SIGNAL && CH::kHeadHasTrip), "trips want a launch-constant input and a head that has them");
-  const size_t vin = LISTED ? vs : v;
   uint32_t pk = 0;
-  const float mixGain = (SCALED && a.mixGains) ? a.mixGains[vin] : 1.f;
-  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + vin * a.in.strideV : nullptr;
-  f32x4* pout = MIX ? nullptr : (f32x4*)a.out.base + v * a.out.strideV;
-  const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
+  sink.start(a);
+  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (vin >> inShift) * a.in.strideV : nullptr;
+  const size_t inQ = a.in.strideQ;
   const uint32_t slot = wave_slot();
   for (size_t t = 0; t < a.T; ++t)
   {
     const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
-    f32x4* po = MIX ? nullptr : pout + t * a.out.strideT;
+    sink.vector(a, t);
     float s[kHeadTripSamples];  // (kHeadTrip: the trip the quad belongs to)
 #pragma unroll 4
     for (int q = 0; q < 16; ++q)
@@ -126,53 +122,85 @@ __device__ __forceinline__ void run_voice(CH& ch, const ChainArgs& a, size_t v, 
         y.z = ch.template next_head<HEAD == kHeadFast>(x.z);
         y.w = ch.template next_head<HEAD == kHeadFast>(x.w);
       }
-      if constexpr (LISTED)
+      if constexpr (PEAK)
       {
         const uint32_t m0 = f2u(y.x) & 0x7fffffffu, m1 = f2u(y.y) & 0x7fffffffu, m2 = f2u(y.z) & 0x7fffffffu, m3 = f2u(y.w) & 0x7fffffffu;
         const uint32_t m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3, m = m01 > m23 ? m01 : m23;
         pk = pk > m ? pk : m;
       }
-      if constexpr (MIX)
-      {
-        if constexpr (SCALED)
-        {
-          if (a.mixGains)  // (wave-uniform; the first stage's `y *= g`)
-          {
-            y.x *= mixGain;
-            y.y *= mixGain;
-            y.z *= mixGain;
-            y.w *= mixGain;
-          }
-          if (!live) y = f32x4{0.f, 0.f, 0.f, 0.f};  // (a voice the bank does not have counts as +0)
-        }
-        mix64_park(strip, q & 3, y);
-        if ((q & 3) == 3) mix64_sum_store(strip, a.mix + ((v >> 6) * a.T + t) * 64 + (size_t)(q & ~3) * 4);
-      }
-      else
-        __builtin_nontemporal_store(y, po + q * outQ);
+      sink.quad(a, t, q, y);
     }
     ch.end_vector();
   }
-  if constexpr (LISTED) *peak = pk;
+  return pk;
 }
 
-// run_voice in the head mode the wavefront has chosen (the same in all lanes)
-template <class CH, bool HAS_SIGNAL, bool MIX, bool SCALED, bool LISTED>
-__device__ __forceinline__ void run_voice_as(int head, CH& ch, const ChainArgs& a, size_t v, float xc, float* strip, bool live, size_t vs, uint32_t* peak)
+// stream_voice in the head mode the wavefront has chosen (the same in all lanes). A sink without trips (SINK::kTrips) runs a
+// wavefront that could take them on the fast head.
+template <class CH, bool HAS_SIGNAL, bool PEAK, class SINK>
+__device__ __forceinline__ uint32_t stream_voice_as(int head, CH& ch, const ChainArgs& a, size_t vin, uint32_t inShift, float xc, SINK sink)
 {
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip && SINK::kTrips)
   {
-    if (head == kHeadTrip)
-    {
-      run_voice<CH, HAS_SIGNAL, kHeadTrip, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
-      return;
-    }
+    if (head == kHeadTrip) return stream_voice<CH, HAS_SIGNAL, kHeadTrip, PEAK>(ch, a, vin, inShift, xc, sink);
   }
-  if (head != kHeadGeneral)
-    run_voice<CH, HAS_SIGNAL, kHeadFast, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
-  else
-    run_voice<CH, HAS_SIGNAL, kHeadGeneral, MIX, SCALED, LISTED>(ch, a, v, xc, strip, live, vs, peak);
+  if (head != kHeadGeneral) return stream_voice<CH, HAS_SIGNAL, kHeadFast, PEAK>(ch, a, vin, inShift, xc, sink);
+  return stream_voice<CH, HAS_SIGNAL, kHeadGeneral, PEAK>(ch, a, vin, inShift, xc, sink);
 }
+
+// ---- the sinks: start(a) once, vector(a, t) before a DSPVector's quads, quad(a, t, q, y) with each finished quad ----
+// A new form of the kernel is a new sink (and, if its lanes are laid out differently, a body that finds them): the loop stays one.
+// A constructor only notes which voice, row and strip; the gain is loaded and the row's address made in start(), which the loop
+// calls - so in the loop function of the chosen head mode, like the input row's index, and nothing of it is live across the choice
+// (made ahead of it, two more VGPRs cost two group kernels a wavefront per SIMD).
+
+// the voice's own signal: row `row` of a.out (chain_kernel, chain_listed_kernel; chain_group_kernel with OUT_G = 1)
+struct StoreSink
+{
+  static constexpr bool kTrips = true;
+  size_t row, outQ;
+  f32x4 *pout, *po;
+  __device__ __forceinline__ explicit StoreSink(size_t row_) : row(row_), outQ(0), pout(nullptr), po(nullptr) {}
+  __device__ __forceinline__ void start(const ChainArgs& a)
+  {
+    pout = (f32x4*)a.out.base + row * a.out.strideV;
+    outQ = a.out.strideQ;
+  }
+  __device__ __forceinline__ void vector(const ChainArgs& a, size_t t) { po = pout + t * a.out.strideT; }
+  __device__ __forceinline__ void quad(const ChainArgs&, size_t, int q, f32x4 y) { __builtin_nontemporal_store(y, po + q * outQ); }
+};
+
+// the wavefront's 64 voices summed through the mix strip (chain_mix_kernel, chain_listed_mix_kernel): lane position v, gain of voice
+// vin. SCALED: the form with per-voice gains and / or spare lanes in the wavefront - a loop of its own, so that the plain one pays
+// nothing for them.
+template <bool SCALED>
+struct MixSink
+{
+  static constexpr bool kTrips = true;
+  float* strip;
+  size_t v, vin;
+  float mixGain;
+  bool live;
+  __device__ __forceinline__ MixSink(float* strip_, size_t v_, size_t vin_, bool live_) : strip(strip_), v(v_), vin(vin_), mixGain(1.f), live(live_) {}
+  __device__ __forceinline__ void start(const ChainArgs& a) { mixGain = (SCALED && a.mixGains) ? a.mixGains[vin] : 1.f; }
+  __device__ __forceinline__ void vector(const ChainArgs&, size_t) {}
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t t, int q, f32x4 y)
+  {
+    if constexpr (SCALED)
+    {
+      if (a.mixGains)  // (wave-uniform; the first stage's `y *= g`)
+      {
+        y.x *= mixGain;
+        y.y *= mixGain;
+        y.z *= mixGain;
+        y.w *= mixGain;
+      }
+      if (!live) y = f32x4{0.f, 0.f, 0.f, 0.f};  // (a voice the bank does not have counts as +0)
+    }
+    mix64_park(strip, q & 3, y);
+    if ((q & 3) == 3) mix64_sum_store(strip, a.mix + ((v >> 6) * a.T + t) * 64 + (size_t)(q & ~3) * 4);
+  }
+};
 
 // ---- groups of adjacent voices inside the voice kernel (chain_group_kernel) ----
 // A bank of instruments (OUT_G voices each, one mixed channel per instrument: Synth::processVector's voice sum, source/app/MLSynth.h:43-57)
@@ -199,58 +227,140 @@ struct GroupStrips<16>
   }
 };
 
-// run_voice with the group forms of input and output (GAINS: a.mixGains scales the voice before the sum - a loop of its own, so that
-// a launch without gains has no multiply at all)
-template <class CH, bool HAS_SIGNAL, bool FAST_HEAD, int OUT_G, bool GAINS>
-__device__ __forceinline__ void run_voice_groups(CH& ch, const ChainArgs& a, size_t v, float xc, float* strip)
+// (GAINS: a.mixGains scales the voice before the sum - a loop of its own, so that a launch without gains has no multiply at all)
+template <int OUT_G, bool GAINS>
+struct GroupSink
 {
   static_assert(OUT_G == 1 || OUT_G == 2 || OUT_G == 4 || OUT_G == 8 || OUT_G == 16, "group_sum_in_order's sizes, or none");
-  const float gain = GAINS ? a.mixGains[v] : 1.f;
-  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (v >> a.inGroupShift) * a.in.strideV : nullptr;
-  f32x4* pout = (f32x4*)a.out.base + (v / OUT_G) * a.out.strideV;  // (OUT_G == 16: lane (g, s)'s own channel is the group g it adds up)
-  const bool lastOfGroup = (threadIdx.x & (OUT_G - 1)) == OUT_G - 1;
-  const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
-  const uint32_t slot = wave_slot();
-  for (size_t t = 0; t < a.T; ++t)
+  static constexpr bool kTrips = false;  // the group form chooses between the general and the fast head only: trips there are a measured change of their own
+  float* strip;
+  size_t v;
+  float gain;
+  StoreSink row;  // (OUT_G == 16: lane (g, s)'s own channel is the group g it adds up)
+  bool lastOfGroup;
+  __device__ __forceinline__ GroupSink(float* strip_, size_t v_) : strip(strip_), v(v_), gain(1.f), row(0), lastOfGroup(false) {}
+  __device__ __forceinline__ void start(const ChainArgs& a)
   {
-    const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
-    f32x4* po = pout + t * a.out.strideT;
-#pragma unroll 4
-    for (int q = 0; q < 16; ++q)
-    {
-      if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
-      f32x4 x = {xc, xc, xc, xc};
-      if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
-      f32x4 y;
-      y.x = ch.template next_head<FAST_HEAD>(x.x);
-      y.y = ch.template next_head<FAST_HEAD>(x.y);
-      y.z = ch.template next_head<FAST_HEAD>(x.z);
-      y.w = ch.template next_head<FAST_HEAD>(x.w);
-      if constexpr (GAINS)
-      {
-        y.x *= gain;
-        y.y *= gain;
-        y.z *= gain;
-        y.w *= gain;
-      }
-      if constexpr (OUT_G == 1)
-        __builtin_nontemporal_store(y, po + q * outQ);
-      else if constexpr (OUT_G == 16)
-      {
-        group16_park(strip, q & 3, y);
-        if ((q & 3) == 3) group16_sum_store(strip, po + (size_t)(q - 3) * outQ, outQ);
-      }
-      else
-      {
-        y.x = group_sum_in_order<OUT_G>(y.x);
-        y.y = group_sum_in_order<OUT_G>(y.y);
-        y.z = group_sum_in_order<OUT_G>(y.z);
-        y.w = group_sum_in_order<OUT_G>(y.w);
-        if (lastOfGroup) __builtin_nontemporal_store(y, po + q * outQ);
-      }
-    }
-    ch.end_vector();
+    gain = GAINS ? a.mixGains[v] : 1.f;
+    row = StoreSink(v / OUT_G);
+    row.start(a);
+    lastOfGroup = (threadIdx.x & (OUT_G - 1)) == OUT_G - 1;
   }
+  __device__ __forceinline__ void vector(const ChainArgs& a, size_t t) { row.vector(a, t); }
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t t, int q, f32x4 y)
+  {
+    if constexpr (GAINS)
+    {
+      y.x *= gain;
+      y.y *= gain;
+      y.z *= gain;
+      y.w *= gain;
+    }
+    if constexpr (OUT_G == 1)
+      row.quad(a, t, q, y);
+    else if constexpr (OUT_G == 16)
+    {
+      group16_park(strip, q & 3, y);
+      if ((q & 3) == 3) group16_sum_store(strip, row.po + (size_t)(q - 3) * row.outQ, row.outQ);
+    }
+    else
+    {
+      y.x = group_sum_in_order<OUT_G>(y.x);
+      y.y = group_sum_in_order<OUT_G>(y.y);
+      y.z = group_sum_in_order<OUT_G>(y.z);
+      y.w = group_sum_in_order<OUT_G>(y.w);
+      if (lastOfGroup) row.quad(a, t, q, y);
+    }
+  }
+};
+
+// the listed voices of one instrument - a segment of the wavefront's lanes, its size data of the host's lane plan - summed through
+// the segment strip (chain_listed_group_kernel): the gain, then mldsp_math.hpp's segment_park / segment_sum_store; every fourth quad
+// the segment's last lane stores four quads to the segment's row (consecutive segments, consecutive rows: in the QUAD layout a
+// wavefront's stores are close to each other). There is no workgroup barrier in the loop.
+struct SegmentSink
+{
+  static constexpr bool kTrips = true;
+  float* strip;
+  size_t vs;
+  float gain;
+  StoreSink row;
+  unsigned rank, length;
+  int longest;
+  __device__ __forceinline__ SegmentSink(float* strip_, size_t vs_, size_t j, unsigned rank_, unsigned length_, int longest_)
+      : strip(strip_), vs(vs_), gain(1.f), row(j), rank(rank_), length(length_), longest(longest_)
+  {
+    __builtin_assume(length_ != 0u);  // (a lane's segment holds the lane itself: the sum's first entry needs no test)
+  }
+  __device__ __forceinline__ void start(const ChainArgs& a)
+  {
+    gain = a.mixGains ? a.mixGains[vs] : 1.f;
+    row.start(a);
+  }
+  __device__ __forceinline__ void vector(const ChainArgs& a, size_t t) { row.vector(a, t); }
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t, int q, f32x4 y)
+  {
+    if (a.mixGains)  // (the same in all lanes: a kernel argument. Without gains there is no multiply at all)
+    {
+      y.x *= gain;
+      y.y *= gain;
+      y.z *= gain;
+      y.w *= gain;
+    }
+    segment_park(strip, q & 3, y);
+    if ((q & 3) == 3) segment_sum_store(strip, rank, length, longest, row.po + (size_t)(q - 3) * row.outQ, row.outQ);
+  }
+};
+
+// ---- what the kernels do before the loop ----
+// XCD-aware workgroup -> voice mapping. Workgroup b is dispatched to XCD b % 8 (observed on
+// MI355X; used for speed only, any bijection is correct). Give XCD x the x-th contiguous eighth
+// of the voices, so each XCD's L2 writes back one contiguous segment of every signal row instead
+// of every 8th KiB: measured +37 % on the bare store pattern (tools/membench2.hip).
+__device__ __forceinline__ size_t remapped_block()
+{
+  size_t blk = blockIdx.x;
+  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
+  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);
+  return blk;
+}
+
+// the ImpulseGen table staged in LDS by the whole workgroup: its __syncthreads() comes before any lane leaves the kernel
+template <class CH>
+__device__ __forceinline__ const float* staged_impulse_table(const ChainArgs& a)
+{
+  __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
+  if constexpr (CH::kHasImpulse)
+  {
+    if (threadIdx.x < Proc<MLGPU_PROC_IMPULSE_GEN>::kTableSize) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];
+    __syncthreads();
+  }
+  return ldsTable;
+}
+
+// coefficients and state of the voice at `mem` into registers; returns its launch-constant input xc (voice vs of a.inConst)
+template <class CH, bool HAS_SIGNAL>
+__device__ __forceinline__ float load_voice(CH& ch, const ChainArgs& a, const VoiceMem& mem, size_t vs, const float* ldsTable)
+{
+  const KernelTables tables{ldsTable};
+  ch.load(mem, tables);
+  return (!HAS_SIGNAL && a.inConst) ? a.inConst[vs] : 0.f;
+}
+
+// A launch-constant input lets the head processor (SawGen / PulseGen) skip its per-sample range test: decide once per wavefront
+// which loop body to run. A ballot counts the lanes that execute it: the lanes that have left the kernel take no part.
+template <class CH, bool HAS_SIGNAL>
+__device__ __forceinline__ int choose_head(float xc)
+{
+  bool fastHead = false;
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(CH::head_input_is_odd(xc)) == 0);
+  // ... and a SawGen head whose frequencies also allow it (0 < f <= 1/16 in every lane) makes its samples in trips of 8
+  int head = fastHead ? kHeadFast : kHeadGeneral;
+  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
+  {
+    if (fastHead && __builtin_amdgcn_ballot_w64(trip_freq_is_dense(xc, kHeadTripSamples)) == 0) head = kHeadTrip;
+  }
+  return head;
 }
 
 // OUT_G != 0: the group form (chain_group_kernel)
@@ -265,21 +375,9 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   static_assert(!(MIX && OUT_G), "one summing form at a time");
   static_assert(!(LISTED && OUT_G), "no group form of a voice list");
   apply_fp_mode(a.flags);
-  __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
+  const float* const ldsTable = staged_impulse_table<CH>(a);
   float* const strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
-  if constexpr (CH::kHasImpulse)
-  {
-    if (threadIdx.x < Proc<MLGPU_PROC_IMPULSE_GEN>::kTableSize) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];
-    __syncthreads();
-  }
-  // XCD-aware workgroup -> voice mapping. Workgroup b is dispatched to XCD b % 8 (observed on
-  // MI355X; used for speed only, any bijection is correct). Give XCD x the x-th contiguous eighth
-  // of the voices, so each XCD's L2 writes back one contiguous segment of every signal row instead
-  // of every 8th KiB: measured +37 % on the bare store pattern (tools/membench2.hip).
-  size_t blk = blockIdx.x;
-  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
-  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);
-  size_t v = blk * kChainBlock + threadIdx.x;
+  size_t v = remapped_block() * kChainBlock + threadIdx.x;
   bool live = true;
   if constexpr (MIX)
   {
@@ -303,45 +401,40 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
 
   CH ch;
   const VoiceMem mem{a.coeffs + vs, a.state + vs, stride};
-  const KernelTables tables{ldsTable};
-  ch.load(mem, tables);
-
-  const float xc = (!HAS_SIGNAL && a.inConst) ? a.inConst[vs] : 0.f;
-
-  // A launch-constant input lets the head processor (SawGen / PulseGen) skip its per-sample
-  // range test: decide once per wavefront which loop body to run.
-  bool fastHead = false;
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(CH::head_input_is_odd(xc)) == 0);
-  // ... and a SawGen head whose frequencies also allow it (0 < f <= 1/16 in every lane) makes its samples in trips of 8
-  int head = fastHead ? kHeadFast : kHeadGeneral;
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
-  {
-    if (fastHead && __builtin_amdgcn_ballot_w64(trip_freq_is_dense(xc, kHeadTripSamples)) == 0) head = kHeadTrip;
-  }
+  const float xc = load_voice<CH, HAS_SIGNAL>(ch, a, mem, vs, ldsTable);
+  const int head = choose_head<CH, HAS_SIGNAL>(xc);
   if constexpr (OUT_G != 0)
   {
     if (a.mixGains != nullptr)  // (the same in all lanes: a kernel argument)
     {
-      if (fastHead)
-        run_voice_groups<CH, HAS_SIGNAL, true, OUT_G, true>(ch, a, v, xc, strip);
-      else
-        run_voice_groups<CH, HAS_SIGNAL, false, OUT_G, true>(ch, a, v, xc, strip);
+      GroupSink<OUT_G, true> sink(strip, v);
+      stream_voice_as<CH, HAS_SIGNAL, false>(head, ch, a, v, a.inGroupShift, xc, sink);
     }
-    else if (fastHead)
-      run_voice_groups<CH, HAS_SIGNAL, true, OUT_G, false>(ch, a, v, xc, strip);
     else
-      run_voice_groups<CH, HAS_SIGNAL, false, OUT_G, false>(ch, a, v, xc, strip);
+    {
+      GroupSink<OUT_G, false> sink(strip, v);
+      stream_voice_as<CH, HAS_SIGNAL, false>(head, ch, a, v, a.inGroupShift, xc, sink);
+    }
   }
   else if constexpr (MIX)
   {
     const bool scaled = a.mixGains != nullptr || __builtin_amdgcn_ballot_w64(!live) != 0;  // (the same in all lanes)
     if (scaled)
-      run_voice_as<CH, HAS_SIGNAL, true, true, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
+    {
+      MixSink<true> sink(strip, v, vs, live);
+      pk = stream_voice_as<CH, HAS_SIGNAL, LISTED>(head, ch, a, vs, 0, xc, sink);
+    }
     else
-      run_voice_as<CH, HAS_SIGNAL, true, false, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
+    {
+      MixSink<false> sink(strip, v, vs, live);
+      pk = stream_voice_as<CH, HAS_SIGNAL, LISTED>(head, ch, a, vs, 0, xc, sink);
+    }
   }
   else
-    run_voice_as<CH, HAS_SIGNAL, false, false, LISTED>(head, ch, a, v, xc, strip, live, vs, &pk);
+  {
+    StoreSink sink(v);
+    pk = stream_voice_as<CH, HAS_SIGNAL, LISTED>(head, ch, a, vs, 0, xc, sink);
+  }
   ch.store(mem);
   if constexpr (LISTED)
   {
@@ -378,7 +471,7 @@ __global__ __launch_bounds__(kChainBlock) void chain_listed_mix_kernel(const Cha
   chain_kernel_body<CH, HAS_SIGNAL, true, 0, true>(a);
 }
 
-// the same voices in groups: input row v >> a.inGroupShift, one output channel per OUT_G adjacent voices (see run_voice_groups);
+// the same voices in groups: input row v >> a.inGroupShift, one output channel per OUT_G adjacent voices (see GroupSink);
 // state as chain_kernel leaves it.
 template <class CH, bool HAS_SIGNAL, int OUT_G>
 __global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArgs a)
@@ -389,89 +482,13 @@ __global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArg
 // ---- the listed voices summed by instrument (chain_listed_group_kernel, mlgpu_bank_process_listed_groups) ----
 // chain_listed_kernel's voices, chain_group_kernel's output: row j of a.out is ((0 + g y[a0]) + g y[a1]) + ... over the listed voices
 // of the j-th listed instrument, in voice order. The group size is data - it is in the host's lane plan (a.lanePlan, see ChainArgs),
-// not in the code: one instantiation per chain and input kind. A body of its own, so that the forms above stay the code they were.
+// not in the code: one instantiation per chain and input kind. The body is its own because its lanes are found differently; the
+// pieces before the loop and the loop itself (with SegmentSink and the peak) are the shared ones.
 //
-// run_voice's loop with the peak of the LISTED form, then the gain, then mldsp_math.hpp's segment_park / segment_sum_store through the
-// wavefront's LDS strip: every fourth quad the segment's last lane stores four quads to the segment's row (consecutive segments,
-// consecutive rows: in the QUAD layout a wavefront's stores are close to each other). There is no workgroup barrier in the loop.
-template <class CH, bool HAS_SIGNAL, int HEAD>
-__device__ __forceinline__ void run_voice_listed_groups(CH& ch, const ChainArgs& a, size_t vs, size_t row, unsigned rank, unsigned length, int longest,
-                                                        float xc, float* strip, uint32_t* peak)
-{
-  static_assert(HEAD != kHeadTrip || (!HAS_SIGNAL && CH::kHeadHasTrip), "trips want a launch-constant input and a head that has them");
-  uint32_t pk = 0;
-  const float gain = a.mixGains ? a.mixGains[vs] : 1.f;
-  const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (vs >> a.inGroupShift) * a.in.strideV : nullptr;
-  f32x4* pout = (f32x4*)a.out.base + row * a.out.strideV;
-  const size_t inQ = a.in.strideQ, outQ = a.out.strideQ;
-  const uint32_t slot = wave_slot();
-  for (size_t t = 0; t < a.T; ++t)
-  {
-    const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
-    f32x4* po = pout + t * a.out.strideT;
-    float s[kHeadTripSamples];  // (kHeadTrip: the trip the quad belongs to)
-#pragma unroll 4
-    for (int q = 0; q < 16; ++q)
-    {
-      if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
-      f32x4 y;
-      if constexpr (HEAD == kHeadTrip)
-      {
-        static_assert(kHeadTripSamples == 8, "a trip is two quads");
-        if ((q & 1) == 0) ch.template next_head_trip<kHeadTripSamples>(xc, s);
-        y = (q & 1) ? f32x4{s[4], s[5], s[6], s[7]} : f32x4{s[0], s[1], s[2], s[3]};
-      }
-      else
-      {
-        f32x4 x = {xc, xc, xc, xc};
-        if constexpr (HAS_SIGNAL) x = __builtin_nontemporal_load(pi + q * inQ);
-        y.x = ch.template next_head<HEAD == kHeadFast>(x.x);
-        y.y = ch.template next_head<HEAD == kHeadFast>(x.y);
-        y.z = ch.template next_head<HEAD == kHeadFast>(x.z);
-        y.w = ch.template next_head<HEAD == kHeadFast>(x.w);
-      }
-      const uint32_t m0 = f2u(y.x) & 0x7fffffffu, m1 = f2u(y.y) & 0x7fffffffu, m2 = f2u(y.z) & 0x7fffffffu, m3 = f2u(y.w) & 0x7fffffffu;
-      const uint32_t m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3, m = m01 > m23 ? m01 : m23;
-      pk = pk > m ? pk : m;
-      if (a.mixGains)  // (the same in all lanes: a kernel argument. Without gains there is no multiply at all)
-      {
-        y.x *= gain;
-        y.y *= gain;
-        y.z *= gain;
-        y.w *= gain;
-      }
-      segment_park(strip, q & 3, y);
-      if ((q & 3) == 3) segment_sum_store(strip, rank, length, longest, po + (size_t)(q - 3) * outQ, outQ);
-    }
-    ch.end_vector();
-  }
-  *peak = pk;
-}
-
-// ... in the head mode the wavefront has chosen (the same in all lanes), as run_voice_as
-template <class CH, bool HAS_SIGNAL>
-__device__ __forceinline__ void run_voice_listed_groups_as(int head, CH& ch, const ChainArgs& a, size_t vs, size_t row, unsigned rank, unsigned length,
-                                                           int longest, float xc, float* strip, uint32_t* peak)
-{
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
-  {
-    if (head == kHeadTrip)
-    {
-      run_voice_listed_groups<CH, HAS_SIGNAL, kHeadTrip>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
-      return;
-    }
-  }
-  if (head != kHeadGeneral)
-    run_voice_listed_groups<CH, HAS_SIGNAL, kHeadFast>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
-  else
-    run_voice_listed_groups<CH, HAS_SIGNAL, kHeadGeneral>(ch, a, vs, row, rank, length, longest, xc, strip, peak);
-}
-
 // Lane l of the launch - found from block and thread exactly as in chain_kernel_body, XCD remap included - runs the voice of its plan
 // entry. Three things the pads decide:
-// 1. A pad takes no part in the wave-uniform head choice: it has left the kernel before the ballots behind fastHead / kHeadTrip are
-//    taken (a ballot counts the lanes that execute it), and the predicates are masked with `!pad` besides, so the choice is the one
-//    the wavefront's voices alone would get.
+// 1. A pad takes no part in the wave-uniform head choice: it has left the kernel before the ballots of choose_head are taken (a
+//    ballot counts the lanes that execute it), so the choice is the one the wavefront's voices alone would get.
 // 2. The impulse table's __syncthreads() comes first, before any lane leaves; there is no workgroup barrier after it.
 // 3. The lanes of the last wavefront at or past N have no plan entry: they are pads without reading one. Whole wavefronts at or
 //    past N leave like chain_kernel's.
@@ -480,44 +497,24 @@ template <class CH, bool HAS_SIGNAL>
 __device__ __forceinline__ void chain_listed_group_body(const ChainArgs& a)
 {
   apply_fp_mode(a.flags);
-  __shared__ float ldsTable[CH::kHasImpulse ? 32 : 1];
+  const float* const ldsTable = staged_impulse_table<CH>(a);
   __shared__ __attribute__((aligned(16))) float ldsStrips[(kChainBlock / 64) * kSegmentStrip + kSegmentTail];
   float* const strip = ldsStrips + (threadIdx.x >> 6) * kSegmentStrip;
-  if constexpr (CH::kHasImpulse)
-  {
-    if (threadIdx.x < Proc<MLGPU_PROC_IMPULSE_GEN>::kTableSize) ldsTable[threadIdx.x] = a.impulseTable[threadIdx.x];
-    __syncthreads();
-  }
-  size_t blk = blockIdx.x;
-  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
-  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);
-  const size_t l = blk * kChainBlock + threadIdx.x;
+  const size_t l = remapped_block() * kChainBlock + threadIdx.x;
   if (l >= a.V) return;
   const uint4 plan = ((const uint4*)a.lanePlan)[l];
-  const bool pad = plan.x == 0xFFFFFFFFu;
-  if (pad) return;
+  if (plan.x == 0xFFFFFFFFu) return;  // a pad
   const size_t vs = plan.x;
   const unsigned rank = plan.w & 0xFFu, length = plan.w >> 8;
 
   CH ch;
   const VoiceMem mem{a.coeffs + vs, a.state + vs, a.tableStride};
-  const KernelTables tables{ldsTable};
-  ch.load(mem, tables);
-
-  const float xc = (!HAS_SIGNAL && a.inConst) ? a.inConst[vs] : 0.f;
-
-  // the head's loop body, once per wavefront: as chain_kernel_body decides it, over the lanes that are voices
-  bool fastHead = false;
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasFastPath) fastHead = (__builtin_amdgcn_ballot_w64(!pad && CH::head_input_is_odd(xc)) == 0);
-  int head = fastHead ? kHeadFast : kHeadGeneral;
-  if constexpr (!HAS_SIGNAL && CH::kHeadHasTrip)
-  {
-    if (fastHead && __builtin_amdgcn_ballot_w64(!pad && trip_freq_is_dense(xc, kHeadTripSamples)) == 0) head = kHeadTrip;
-  }
-  uint32_t pk = 0;
+  const float xc = load_voice<CH, HAS_SIGNAL>(ch, a, mem, vs, ldsTable);
+  const int head = choose_head<CH, HAS_SIGNAL>(xc);  // (over the lanes that are voices)
   // the wavefront's longest segment, rounded up to a size segment_sum_store has the reads of
   const int longest = __builtin_amdgcn_ballot_w64(length > 8u) ? 16 : (__builtin_amdgcn_ballot_w64(length > 4u) ? 8 : (__builtin_amdgcn_ballot_w64(length > 2u) ? 4 : 2));
-  run_voice_listed_groups_as<CH, HAS_SIGNAL>(head, ch, a, vs, plan.z, rank, length, longest, xc, strip, &pk);
+  SegmentSink sink(strip, vs, plan.z, rank, length, longest);
+  const uint32_t pk = stream_voice_as<CH, HAS_SIGNAL, true>(head, ch, a, vs, a.inGroupShift, xc, sink);
   ch.store(mem);
   if (a.peaks != nullptr) a.peaks[plan.y] = pk;  // (the same in all lanes: a kernel argument)
 }
@@ -699,10 +696,7 @@ __global__ __launch_bounds__(kChainBlock) void cascade_kernel(const ChainArgs a)
   // with B == 0 the steady loop's last prefetch (inQuad(q + A + QT + 1 + k)) would read one quad past the input
   static_assert((N - 1) % 4 != 0, "cascade lengths with (N - 1) % 4 == 0 need a bounded prefetch");
   apply_fp_mode(a.flags);
-  size_t blk = blockIdx.x;
-  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
-  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);  // XCD-aware, see chain_kernel
-  const size_t v = blk * kChainBlock + threadIdx.x;
+  const size_t v = remapped_block() * kChainBlock + threadIdx.x;
   if (v >= a.V) return;
 
   HEAD head;
@@ -860,9 +854,7 @@ __device__ __forceinline__ void cascade_lanes_body(const ChainArgs& a)
   constexpr int NCK = Core::NCK, H = Core::H;
   constexpr int kChannelsPerBlock = kChainBlock / LPC;
   apply_fp_mode(a.flags);
-  size_t blk = blockIdx.x;
-  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;
-  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);  // XCD-aware, see chain_kernel
+  const size_t blk = remapped_block();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = (lane >> 2) % LPC;                                   // which stage group of its channel this lane runs
   const size_t v = blk * kChannelsPerBlock + (size_t)wave * (64 / LPC) + (lane / (4 * LPC)) * 4 + (lane & 3);

@@ -36,18 +36,18 @@ struct ChainArgs
   size_t V, T;
   const float* impulseTable;
   uint32_t flags;  // MLGPU_KFLAG_*
-  float* mix;      // chain_mix_kernel: the rows of 64-voice group sums, [(group * T + t) * 64 + sample] (mlgpu_mixdown's first stage); else unused
+  float* mix;      // chain_mix_kernel (mldsp_kernels.hpp: MixSink): the rows of 64-voice group sums, [(group * T + t) * 64 + sample] (mlgpu_mixdown's first stage); else unused
   const float* mixGains;  // ... and the per-voice gains the voices are scaled by before (mlgpu_mixdown's d_gains), or nullptr
-  // chain_group_kernel (which scales by mixGains too, before its group sums): voice v reads row v >> inGroupShift of `in`, and
+  // chain_group_kernel (GroupSink; it scales by mixGains too, before its group sums): voice v reads row v >> inGroupShift of `in`, and
   // `out` is a signal of V / OUT_G channels; else unused
   uint32_t inGroupShift = 0;
-  // chain_listed_kernel / chain_listed_mix_kernel (mlgpu_bank_process_listed): lane i of the launch runs voice voiceList[i] of a
+  // chain_listed_kernel / chain_listed_mix_kernel (mlgpu_bank_process_listed; chain_kernel_body's LISTED with StoreSink / MixSink): lane i of the launch runs voice voiceList[i] of a
   // bank of tableStride voices - V is then the list's length, coeffs / state / inConst / in / mixGains are read at the voice, out /
   // mix / peaks written at i; peaks[i] (or nullptr) gets the largest |sample| bit pattern of the launch. Else unused.
   const uint32_t* voiceList = nullptr;
   size_t tableStride = 0;
   uint32_t* peaks = nullptr;
-  // chain_listed_group_kernel (mlgpu_bank_process_listed_groups): the launch is V = N lanes laid out by the host (voice_list.hpp:
+  // chain_listed_group_kernel (mlgpu_bank_process_listed_groups; SegmentSink): the launch is V = N lanes laid out by the host (voice_list.hpp:
   // mlvl::planGroups), lane l's plan entry is the four words lanePlan[4 l .. 4 l + 3], one 16-byte load:
   //   .x voice (0xFFFFFFFF: a pad lane, which runs nothing)   .y list position i (peaks[i])
   //   .z output row j of `out`, a signal of J rows             .w rank | length << 8 of the lane in its segment

@@ -164,19 +164,24 @@ inline SignalView makeView(const float* p, int layout, size_t V, size_t T)
   return s;
 }
 
-typedef hipError_t (*ChainLauncher)(const ChainArgs& a, hipStream_t stream, int cuCount);
-typedef hipError_t (*ChainGroupLauncher)(const ChainArgs& a, int outGroup, hipStream_t stream);
+// the forms of a chain's kernel (mldsp_kernels.hpp: one loop, one sink per form)
+enum ChainForm
+{
+  kFormPlain,         // chain_kernel, cascade_kernel / cascade_lanes_kernel: every entry has it
+  kFormMix,           // chain_mix_kernel (the voices' sum instead of their signals): the fused voice chains
+  kFormGroups,        // chain_group_kernel (voices in groups of 1, 2, 4, 8, 16): the chain kernels, not the cascades
+  kFormListed,        // chain_listed_kernel (the voices of a list): where kFormGroups is
+  kFormListedMix,     // chain_listed_mix_kernel: where kFormMix is
+  kFormListedGroups,  // chain_listed_group_kernel (the listed voices summed by instrument): where kFormGroups is
+  kChainForms
+};
+// outGroup: the group size of kFormGroups, which picks the instantiation; no other form reads it
+typedef hipError_t (*ChainLauncher)(const ChainArgs& a, hipStream_t stream, int outGroup);
 
 struct ChainEntry
 {
   std::vector<int> kinds;
-  ChainLauncher launchSignal;  // streamed input
-  ChainLauncher launchConst;   // per-voice constant (or no) input
-  ChainLauncher launchMixSignal{nullptr}, launchMixConst{nullptr};  // chain_mix_kernel (the voices' sum instead of their signals), where instantiated
-  ChainGroupLauncher launchGroupsSignal{nullptr}, launchGroupsConst{nullptr};  // chain_group_kernel (voices in groups of 1, 2, 4, 8, 16): the chain kernels, not the cascades
-  // chain_listed_kernel / chain_listed_mix_kernel (the voices of a list): where chain_group_kernel / chain_mix_kernel are
-  ChainLauncher launchListedSignal{nullptr}, launchListedConst{nullptr}, launchListedMixSignal{nullptr}, launchListedMixConst{nullptr};
-  ChainLauncher launchListedGroupsSignal{nullptr}, launchListedGroupsConst{nullptr};  // chain_listed_group_kernel (the listed voices summed by instrument)
+  ChainLauncher launch[kChainForms][2]{};  // [form][input is streamed]; null: the chain has no such form
   const char* kernelName;  // prefix of the name a profiler shows for the device kernel
   const char* (*kernelNameFor)(size_t V, uint32_t flags){nullptr};  // where the kernel depends on the bank's size (SVF cascades)
   const char* alias;       // e.g. "chain_kernel<SawGen,Bandpass,Gain>"

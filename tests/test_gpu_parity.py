@@ -630,6 +630,44 @@ def test_empty_and_error_paths(eng):
     assert eng.op(Op.ADD, np.zeros(0, np.float32), np.zeros(0, np.float32)).size == 0
 
 
+# (keyword arguments of Bank.process on a 64-voice Lopass bank; "out" / "in" are byte offsets into a device buffer, None is a null
+# pointer) -> the status and the whole message, or None where the call goes through
+BANK_PROCESS_REFUSALS = [
+    (dict(T=0, out=None), None),                                                    # no vectors: nothing is looked at
+    (dict(T=0, out=4, out_layout=9), None),
+    (dict(T=1, out=None), "bank_process: null output"),
+    (dict(T=1, out=None, out_layout=9), "bank_process: null output"),               # (the output first)
+    (dict(T=1, out=0, out_layout=Layout.BROADCAST), "bank_process: bad layout"),
+    (dict(T=1, out=0, out_layout=-1), "bank_process: bad layout"),
+    (dict(T=1, out=0, inp=0, in_layout=4), "bank_process: bad layout"),
+    (dict(T=1, out=0, inp=0, in_layout=-1), "bank_process: bad layout"),
+    (dict(T=1, out=4, out_layout=9), "bank_process: bad layout"),                   # (the layouts before the alignment)
+    (dict(T=1, out=0, in_layout=7), None),                                          # (no input: its layout is not looked at)
+    (dict(T=1, out=4), "bank_process: signals must be 16-byte aligned"),
+    (dict(T=1, out=0, inp=8), "bank_process: signals must be 16-byte aligned"),
+    (dict(T=1, out=0, inp=0, in_layout=Layout.BROADCAST), None),
+]
+
+
+@pytest.mark.parametrize("args,message", BANK_PROCESS_REFUSALS)
+def test_bank_process_refusals(eng, args, message):
+    """mlgpu_bank_process's argument checks: status MLGPU_ERR_INVALID and the message, word for word, in the order the checks are made."""
+    import madronalib_amd as ml
+    bank = eng.bank([Proc.LOPASS], 64)
+    bufs = {"out": eng.alloc(64 * 64 * 4 + 16), "inp": eng.alloc(64 * 64 * 4 + 16)}
+    at = lambda k: 0 if args.get(k) is None else bufs[k].ptr + args[k]  # noqa: E731
+    call = lambda: bank.process(args["T"], at("out"), args.get("out_layout", Layout.QUAD), at("inp") if "inp" in args else None,  # noqa: E731
+                                args.get("in_layout", Layout.QUAD))
+    if message is None:
+        call()
+        eng.sync()
+    else:
+        with pytest.raises(ml.MlgpuError) as ei:
+            call()
+        assert ei.value.status == ml.Status.ERR_INVALID and str(ei.value).endswith(") " + message), str(ei.value)
+    bank.close()
+
+
 def test_default_constructed_peak_holds_for_44100_samples(eng, oracle):
     """A bank installs the coefficients of a default-constructed reference object: Peak's third coefficient is
     peakHoldSamples{44100} (MLDSPFilters.h:574). A host that only sets makeCoeffs' a0 / b1 must get that hold time."""

@@ -342,6 +342,48 @@ def test_sharded_mixdown_gives_one_bank_bits(eng, oracle, V, shards):
         eng.bank(chain, 100).process_mixdown_shard(T, d_rows[0])     # not whole first-stage groups: no exact hand-over
 
 
+# (arguments of Bank.process_mixdown on a 128-voice SawGen -> Bandpass -> Gain bank - `fused` False: on a Lopass bank, which has no
+# summing form; "out" / "inp" are byte offsets into a device buffer, None is a null pointer) -> the whole message, or None where the
+# call goes through
+MIXDOWN_REFUSALS = [
+    (dict(T=0, out=None), None),                                                          # no vectors: nothing is looked at
+    (dict(T=0, out=4, inp=8, in_layout=9), None),
+    (dict(T=0, out=None, fused=False), None),
+    (dict(T=1, out=None), "bank_process_mixdown: null output"),
+    (dict(T=1, out=None, inp=0, in_layout=9), "bank_process_mixdown: null output"),        # (the output first)
+    (dict(T=1, out=None, fused=False), "bank_process_mixdown: null output"),               # (... and before the kernel's form)
+    (dict(T=1, out=0, inp=0, in_layout=4), "bank_process_mixdown: bad layout"),
+    (dict(T=1, out=0, inp=0, in_layout=-1), "bank_process_mixdown: bad layout"),
+    (dict(T=1, out=4, inp=0, in_layout=4), "bank_process_mixdown: bad layout"),            # (the layout before the alignment)
+    (dict(T=1, out=0, in_layout=7), None),                                                 # (no input: its layout is not looked at)
+    (dict(T=1, out=4), "bank_process_mixdown: signals must be 16-byte aligned"),
+    (dict(T=1, out=0, inp=8), "bank_process_mixdown: signals must be 16-byte aligned"),
+    (dict(T=1, out=4, fused=False), "bank_process_mixdown: signals must be 16-byte aligned"),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("args,message", MIXDOWN_REFUSALS)
+def test_bank_process_mixdown_argument_checks(eng, args, message):
+    """mlgpu_bank_process_mixdown's argument checks: status MLGPU_ERR_INVALID and the message, word for word, in the order the checks
+    are made."""
+    import madronalib_amd as ml
+    eng.mixdown_reserve(4096, 1)
+    V = 128
+    bank = eng.bank([Proc.SAW_GEN, Proc.BANDPASS, Proc.GAIN] if args.get("fused", True) else [Proc.LOPASS], V)
+    bufs = {"out": eng.alloc(4 * 64 + 16), "inp": eng.alloc(4 * V * 64 + 16)}
+    at = lambda k: 0 if args.get(k) is None else bufs[k].ptr + args[k]  # noqa: E731
+    call = lambda: bank.process_mixdown(args["T"], at("out"), at("inp") if "inp" in args else None, args.get("in_layout", Layout.QUAD))  # noqa: E731
+    if message is None:
+        call()
+        eng.sync()
+    else:
+        with pytest.raises(ml.MlgpuError) as ei:
+            call()
+        assert ei.value.status == ml.Status.ERR_INVALID and str(ei.value).endswith(") " + message), str(ei.value)
+    bank.close()
+
+
 @pytest.mark.gpu
 def test_bank_process_mixdown_refusals(eng):
     import madronalib_amd as ml

@@ -299,6 +299,40 @@ def test_process_listed_mixdown_in_both_float_modes(eng, oracle, flush):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("with_gains", [pytest.param(False, id="plain"), pytest.param(True, id="gains")])
+def test_process_listed_mixdown_on_a_streamed_frequency(eng, oracle, with_gains):
+    """The listed summing form with a streamed input (the cases above give SawGen -> Bandpass -> Gain its frequency as a per-voice
+    constant): the frequency as a signal of V rows, lane i reading row L[i]. V = 64 * 2 + 37, T = 3, every voice listed but 7, 64 and
+    150 - K = 162, two wavefronts and 34 lanes, so the last wavefront has spare lanes. The sum against the oracle's voices under the
+    oracle's tree, the peaks, the listed voices' state against the oracle and the unlisted voices' against a download before the call."""
+    Vs = 64 * 2 + 37
+    ch = make_chain(oracle, "saw", Vs)
+    wobble = 1.0 + 0.3 * np.sin(np.arange(64 * T)[None, :] * 0.003 * (1 + np.arange(Vs)[:, None] % 7))
+    ch.in_rows, ch.in_const = np.ascontiguousarray((ch.in_const[:, None] * wobble).astype(np.float32)), None
+    rest = np.array([7, 64, 150])
+    L = np.setdiff1d(np.arange(Vs), rest).astype(np.uint32)
+    K = L.size
+    st0 = oracle.chain_clear(ch.procs, Vs)
+    oracle.chain_process(ch.procs, 1, ch.coeffs, st0, np.ascontiguousarray(ch.in_rows[:, :64]), None, n_threads=4, want_out=False)   # (make_bank's DSPVector)
+    st = st0.copy()
+    y = expected_listed(oracle, ch, L, st, 0, T)
+    gains = special_gains(Vs) if with_gains else None
+    want = expected_listed_mixdown(oracle, y, L, gains)
+    bank = make_bank(eng, ch)
+    bank.set_voice_list(L)
+    before = bank.get_all_state()
+    got, peaks = run_listed(eng, bank, ch, K, [T], mix=True, d_gains=None if gains is None else eng.to_device(gains))
+    after = bank.get_all_state()
+    bank.close()
+    assert np.isfinite(want).all() and np.abs(want).max() > 1e-6
+    assert_bits_equal(before, st0, False, "state before the call against the oracle")
+    assert_bits_equal(got, want, True, "one launch against the oracle's voices and tree")
+    check_peaks(peaks, y, [T], "streamed frequency")
+    assert_bits_equal(after[:, L], st[:, L], False, "state of the listed voices against the oracle")
+    assert_bits_equal(after[:, rest], before[:, rest], False, "state of the unlisted voices against the download before the call")
+
+
+@pytest.mark.gpu
 def test_peaks_show_a_nan_and_a_silent_voice(eng, oracle):
     """d_peak[i] = max over the launch of bits(y) & 0x7fffffff as an unsigned integer, y the voice's own sample.
     A Gain bank (y = input constant * gain): the voice given a NaN input constant reports a value above 0x7f800000, the voice whose

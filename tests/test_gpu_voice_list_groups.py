@@ -188,6 +188,40 @@ def test_every_group_size(eng, oracle, G, lname):
 
 
 @pytest.mark.gpu
+def test_a_wavefront_on_the_fast_head_beside_one_in_trips(eng, oracle):
+    """The head mode no other case of this form reaches: a constant frequency above 1/16 in a lane sends its wavefront to the fast
+    per-sample head, neither trips nor the range test. V = 80, G = 16, T = 3: the first wavefront (64 lanes, four instruments, voice 3
+    unlisted) makes trips, the ragged second one (16 lanes, voice 70 unlisted) has three lanes above 1/16. Rows, peaks and the
+    listed voices' state against the oracle as in check_groups; the unlisted voices' state against a download before the call."""
+    Vs, G = 80, 16
+    ch = Chain("saw", oracle, Vs)
+    freq = ch.in_const.copy()
+    assert ((freq > 0) & (freq <= np.float32(1.0 / 16.0))).all()          # (as the chain comes: trips everywhere)
+    freq[[66, 71, 79]] = np.array([0.07, 0.11, 0.2], np.float32)
+    ch.in_const = freq
+    L = np.setdiff1d(np.arange(Vs), [3, 70]).astype(np.uint32)
+    K, rest = L.size, np.array([3, 70])
+    st0 = oracle.chain_clear(ch.procs, Vs)
+    oracle.chain_process(ch.procs, 1, ch.coeffs, st0, None, freq, n_threads=4, want_out=False)    # (make_bank's DSPVector of all voices)
+    st = st0.copy()
+    y = expected_listed(oracle, ch, L, st, 0, T)
+    want, M = expected_listed_groups(oracle, y, L, G)
+    bank = make_bank(eng, ch)
+    bank.reserve_voice_list_groups(K, G)
+    bank.set_voice_list(L)
+    before = bank.get_all_state()
+    got, peaks = run_groups(eng, bank, ch, K, M.size, [T])
+    after = bank.get_all_state()
+    bank.close()
+    assert M.size == Vs // G and np.isfinite(want).all() and np.abs(want).max() > 1e-6
+    assert_bits_equal(before, st0, False, "state before the call against the oracle")
+    assert_bits_equal(got, want, True, "one launch against the oracle's voices summed by instrument")
+    check_peaks(peaks, y, [T], "fast head")
+    assert_bits_equal(after[:, L], st[:, L], False, "state of the listed voices against the oracle")
+    assert_bits_equal(after[:, rest], before[:, rest], False, "state of the unlisted voices against the download before the call")
+
+
+@pytest.mark.gpu
 def test_an_input_group_is_read_at_the_voice(eng, oracle):
     """in_group 4: the streamed input has V / 4 rows and voice v reads row v // 4, listed or not."""
     check_groups(eng, oracle, "bandpass", "k2100", 16, in_group=4)
