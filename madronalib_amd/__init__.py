@@ -246,6 +246,24 @@ class Engine(_Handle):
     def get_cascade_lanes(self):
         return int(self.L.mlgpu_engine_get_cascade_lanes(self.h))
 
+    def set_launch_parts(self, parts):
+        """How a plain launch of a large bank goes out (mlgpu_engine_set_launch_parts): 0 = in two parts on two streams where the bank
+        is large enough (the default), 1 = always one launch, 2 = two parts whenever the form allows (tests). Same bits either way."""
+        self._check(self.L.mlgpu_engine_set_launch_parts(self.h, int(parts)))
+
+    def get_launch_parts(self):
+        return int(self.L.mlgpu_engine_get_launch_parts(self.h))
+
+    def launch_parts_possible(self):
+        """False once this engine launches in one part whatever set_launch_parts says: it runs on a caller's stream, or `stream` was read."""
+        return bool(self.L.mlgpu_engine_launch_parts_possible(self.h))
+
+    def launch_stats(self):
+        """(launches that went out in two parts, times the two streams met again) since the engine was made."""
+        split, joins = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.L.mlgpu_engine_launch_stats(self.h, ctypes.byref(split), ctypes.byref(joins)))
+        return split.value, joins.value
+
     def set_jit(self, enabled):
         """hiprtc fusion of chains that have no ahead-of-time kernel (default on)."""
         self._check(self.L.mlgpu_engine_set_jit(self.h, 1 if enabled else 0))

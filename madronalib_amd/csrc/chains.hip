@@ -145,6 +145,7 @@ ChainEntry makeEntry(const char* name)
   e.kinds = {KS...};
   e.launch[kFormPlain][1] = &launchChain<chain_kernel<Chain<KS...>, true>>;
   e.launch[kFormPlain][0] = &launchChain<chain_kernel<Chain<KS...>, false>>;
+  e.plainTakesWindow = true;
   e.launch[kFormGroups][1] = &launchChainGroups<true, KS...>;
   e.launch[kFormGroups][0] = &launchChainGroups<false, KS...>;
   e.launch[kFormListed][1] = &launchChain<chain_listed_kernel<Chain<KS...>, true>>;

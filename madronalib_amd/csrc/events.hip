@@ -1036,7 +1036,7 @@ extern "C"
     hipError_t err = hipSetDevice(e->device);
     if (err == hipSuccess) err = allocate(ev->d_state, (size_t)kStateWords * maxLanes);
     if (err == hipSuccess) err = allocate(ev->d_recRange, maxLanes);
-    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * maxLanes, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(ev->d_recRange.get(), 0, sizeof(uint2) * maxLanes, e->stream());
     for (mlgpu_events::Staging& st : ev->stage.set)
       if (err == hipSuccess) err = createTurn(st.turn);
     if (err != hipSuccess)
@@ -1120,8 +1120,8 @@ extern "C"
     const size_t lanes = router.ctlLanes(), nRecs = router.ctlRecordCount();
     if (!growPair(sg.h_recs, sg.d_recs, sg.recCapacity, nRecs + 1, std::max<size_t>(1024, 2 * (nRecs + 1)))) return efail(ev, MLGPU_ERR_OOM, "events_process: controller record buffer");
     router.packControllers(sg.h_recs.get(), sg.h_recStart.get());
-    hipError_t err = hipMemcpyAsync(sg.d_recStart.get(), sg.h_recStart.get(), sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream);
+    hipError_t err = hipMemcpyAsync(sg.d_recStart.get(), sg.h_recStart.get(), sizeof(uint32_t) * (lanes + 1), hipMemcpyHostToDevice, e->stream());
+    if (err == hipSuccess && nRecs) err = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(CtlRec) * nRecs, hipMemcpyHostToDevice, e->stream());
     if (err != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process controller upload: ") + hipGetErrorString(err));
     CtlArgs a;
     a.state = ev->d_ctlState.get();
@@ -1134,7 +1134,7 @@ extern "C"
     a.slotStride = 64 * ev->ctlCapacityVectors * router.instruments();  // (the capacity, not the current limit: a slot's signal stays where it is while the buffer is not replaced)
     a.glideVectors = s.ctlGlideVectors;
     a.glideDy = s.ctlGlideDy;
-    hipLaunchKernelGGL(ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
+    hipLaunchKernelGGL(ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     err = hipGetLastError();
     if (err != hipSuccess) return efail(ev, MLGPU_ERR_HIP, std::string("events_process controller launch: ") + hipGetErrorString(err));
     return MLGPU_OK;
@@ -1148,11 +1148,11 @@ extern "C"
   {
     if (sg.nDirtySet)
     {
-      hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream, (const uint4*)sg.d_dirty.get(), sg.nDirtySet, ev->d_recRange.get());
+      hipLaunchKernelGGL(clear_rec_ranges_kernel, dim3((unsigned)((sg.nDirtySet + 255) / 256)), dim3(256), 0, ev->e->stream(), (const uint4*)sg.d_dirty.get(), sg.nDirtySet, ev->d_recRange.get());
       (void)hipGetLastError();
       sg.nDirtySet = 0;
     }
-    sg.turn.submitted(ev->e->stream);
+    sg.turn.submitted(ev->e->stream());
   }
 
   // One block of nVectors DSPVectors starting at frame startOffset of the event times, up to the kernel that consumes it: the block's
@@ -1179,11 +1179,11 @@ extern "C"
     if (!growPair(sg.h_dirty, sg.d_dirty, sg.dirtyCapacity, nDirty, std::max<size_t>(1024, 2 * nDirty))) return giveUp(MLGPU_ERR_OOM, "events_process: lane list");
     router.pack(sg.h_recs.get(), sg.h_dirty.get());
     hipError_t cerr = hipSuccess;
-    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(LaneRange) * nDirty, hipMemcpyHostToDevice, e->stream);
-    if (cerr == hipSuccess && nRecs) cerr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(Rec) * nRecs, hipMemcpyHostToDevice, e->stream);
+    if (nDirty) cerr = hipMemcpyAsync(sg.d_dirty.get(), sg.h_dirty.get(), sizeof(LaneRange) * nDirty, hipMemcpyHostToDevice, e->stream());
+    if (cerr == hipSuccess && nRecs) cerr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(Rec) * nRecs, hipMemcpyHostToDevice, e->stream());
     if (cerr == hipSuccess && nDirty)
     {
-      hipLaunchKernelGGL(set_rec_ranges_kernel, dim3((unsigned)((nDirty + 255) / 256)), dim3(256), 0, e->stream, (const uint4*)sg.d_dirty.get(), nDirty, ev->d_recRange.get());
+      hipLaunchKernelGGL(set_rec_ranges_kernel, dim3((unsigned)((nDirty + 255) / 256)), dim3(256), 0, e->stream(), (const uint4*)sg.d_dirty.get(), nDirty, ev->d_recRange.get());
       cerr = hipGetLastError();
       if (cerr == hipSuccess) sg.nDirtySet = nDirty;
     }
@@ -1207,7 +1207,7 @@ extern "C"
   static int launched(mlgpu_events* ev, mlgpu_events::Staging& sg)
   {
     sg.nDirtySet = 0;  // (the consuming kernel clears the ranges it read)
-    sg.turn.submitted(ev->e->stream);  // no wait here: the host goes on routing the next block while this one runs
+    sg.turn.submitted(ev->e->stream());  // no wait here: the host goes on routing the next block while this one runs
     return MLGPU_OK;
   }
 
@@ -1242,9 +1242,9 @@ extern "C"
     a.slotBase = ev->router.slotBase();
     a.polyphony = ev->router.polyphony();
     if ((a.rowMask & ~3u) == 0)
-      hipLaunchKernelGGL(e2s_kernel<true>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
+      hipLaunchKernelGGL(e2s_kernel<true>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     else
-      hipLaunchKernelGGL(e2s_kernel<false>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
+      hipLaunchKernelGGL(e2s_kernel<false>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {
@@ -1260,7 +1260,7 @@ extern "C"
     mlgpu_engine* e = ev->e;
     const size_t lanes = ev->router.lanes();
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    hipStreamSynchronize(e->stream);
+    hipStreamSynchronize(e->stream());
     // recorded graph launches have these pointers baked in: the old buffers are retired, the new ones serve from now on
     e->retire(std::move(ev->d_ctlRecs));
     e->retire(std::move(ev->d_rowP));
@@ -1324,7 +1324,7 @@ extern "C"
     a.ctl = ev->d_ctlRecs.get();
     a.rowP = (float4*)ev->d_rowP.get();
     a.rowG = (float4*)ev->d_rowG.get();
-    hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, a);
+    hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {
@@ -1362,7 +1362,7 @@ extern "C"
         if (numbers[j] == numbers[i]) return efail(ev, MLGPU_ERR_INVALID, "events_watch_controllers: a controller number twice");
     }
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
-    hipStreamSynchronize(e->stream);
+    hipStreamSynchronize(e->stream());
     if (n > 0 && ev->router.watched() == std::vector<int>(numbers, numbers + n))  // the same controllers: only the reserved length changes
     {
       if (maxVectors <= ev->ctlCapacityVectors)  // the signals' pointers (mlgpu_events_controller_signal) are only ever replaced to grow
@@ -1374,7 +1374,7 @@ extern "C"
         return efail(ev, MLGPU_ERR_INVALID, "events_watch_controllers would move the controller signals that recorded sequences of this engine may read: destroy them first");
       DeviceBuffer<float> fresh;
       if (allocate(fresh, 64 * maxVectors * ev->router.ctlLanes()) != hipSuccess) return efail(ev, MLGPU_ERR_OOM, "events_watch_controllers: controller signals");
-      hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * ev->router.ctlLanes(), e->stream);
+      hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * ev->router.ctlLanes(), e->stream());
       ev->d_ctlOut = std::move(fresh);
       ev->ctlMaxVectors = ev->ctlCapacityVectors = maxVectors;
       return MLGPU_OK;
@@ -1393,7 +1393,7 @@ extern "C"
       if (err == hipSuccess) err = allocate(st.d_recStart, lanes + 1);
       if (err == hipSuccess) err = allocate(st.h_recStart, lanes + 1);
     }
-    if (err == hipSuccess) err = hipMemsetAsync(ev->d_ctlOut.get(), 0, sizeof(float) * 64 * maxVectors * lanes, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(ev->d_ctlOut.get(), 0, sizeof(float) * 64 * maxVectors * lanes, e->stream());
     if (err != hipSuccess)
     {
       freeControllers(ev);

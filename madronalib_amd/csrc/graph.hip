@@ -888,10 +888,10 @@ extern "C"
     if (err == hipSuccess) err = allocate(g->d_params, V * (size_t)(g->desc.nParams + 1));
     const size_t memV = plan.memVoices;
     if (err == hipSuccess && plan.memFloatsPerVoice) err = allocate(g->d_mem, memV * plan.memFloatsPerVoice);
-    if (err == hipSuccess && plan.memFloatsPerVoice) err = hipMemsetAsync(g->d_mem.get(), 0, sizeof(float) * memV * plan.memFloatsPerVoice, e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_state.get(), 0, sizeof(uint32_t) * V * (size_t)(g->desc.NS + 1), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_coeffs.get(), 0, sizeof(float) * V * (size_t)(g->desc.NC + 1), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(g->d_params.get(), 0, sizeof(float) * V * (size_t)(g->desc.nParams + 1), e->stream);
+    if (err == hipSuccess && plan.memFloatsPerVoice) err = hipMemsetAsync(g->d_mem.get(), 0, sizeof(float) * memV * plan.memFloatsPerVoice, e->stream());
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_state.get(), 0, sizeof(uint32_t) * V * (size_t)(g->desc.NS + 1), e->stream());
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_coeffs.get(), 0, sizeof(float) * V * (size_t)(g->desc.NC + 1), e->stream());
+    if (err == hipSuccess) err = hipMemsetAsync(g->d_params.get(), 0, sizeof(float) * V * (size_t)(g->desc.nParams + 1), e->stream());
     if (err == hipSuccess && g->desc.liveConsts)
     {
       err = allocate(g->d_consts, (size_t)(g->desc.nConsts + 1));
@@ -900,7 +900,7 @@ extern "C"
         {
           uint32_t u;
           memcpy(&u, &n.value, 4);
-          err = mlgpu_launch_fill32((uint32_t*)g->d_consts.get() + n.slot, u, 1, e->stream);
+          err = mlgpu_launch_fill32((uint32_t*)g->d_consts.get() + n.slot, u, 1, e->stream());
         }
     }
     for (const Node& n : g->desc.nodes)
@@ -912,12 +912,12 @@ extern "C"
       {
         uint32_t u;
         memcpy(&u, &dc[i], 4);
-        if (u) err = mlgpu_launch_fill32((uint32_t*)g->d_coeffs.get() + (size_t)(n.cOff + i) * V, u, V, e->stream);
+        if (u) err = mlgpu_launch_fill32((uint32_t*)g->d_coeffs.get() + (size_t)(n.cOff + i) * V, u, V, e->stream());
       }
       uint32_t words[MLGPU_MAX_PROC_STATE];
       mlgpu_proc_clear_state(n.kind, words, false);
       for (int i = 0; i < n.ns && err == hipSuccess; ++i)
-        err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * V, words[i], V, e->stream);
+        err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * V, words[i], V, e->stream());
     }
     if (err != hipSuccess) return gfail(g, err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP, std::string("graph_compile: ") + hipGetErrorString(err));
     g->compiled = true;
@@ -934,7 +934,7 @@ extern "C"
     hipError_t err = hipSetDevice(g->e->device);  // (a host thread may drive engines on several devices in turn)
     if (n.type == NODE_FEEDBACK)
     {
-      for (int i = 0; i < n.ns && err == hipSuccess; ++i) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->desc.V, 0u, g->desc.V, g->e->stream);
+      for (int i = 0; i < n.ns && err == hipSuccess; ++i) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->desc.V, 0u, g->desc.V, g->e->stream());
     }
     else if (n.type == NODE_PROC)
     {
@@ -942,9 +942,9 @@ extern "C"
       mlgpu_proc_clear_state(n.kind, words, true);
       const uint64_t mask = mlgpu_proc_clear_mask(n.kind);
       for (int i = 0; i < n.ns && err == hipSuccess; ++i)
-        if ((mask >> (i < 64 ? i : 63)) & 1) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->desc.V, words[i], g->desc.V, g->e->stream);
+        if ((mask >> (i < 64 ? i : 63)) & 1) err = mlgpu_launch_fill32(g->d_state.get() + (size_t)(n.sOff + i) * g->desc.V, words[i], g->desc.V, g->e->stream());
       if (err == hipSuccess && n.ringLen)
-        err = mlgpu_launch_fill32((uint32_t*)g->d_mem.get() + g->build->plan.nodes[node].memOff * g->build->plan.memVoices, 0u, n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * g->build->plan.memVoices, g->e->stream);
+        err = mlgpu_launch_fill32((uint32_t*)g->d_mem.get() + g->build->plan.nodes[node].memOff * g->build->plan.memVoices, 0u, n.ringLen * (size_t)mlgpu_proc_rings(n.kind) * g->build->plan.memVoices, g->e->stream());
     }
     if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, hipGetErrorString(err));
     return MLGPU_OK;
@@ -1405,8 +1405,8 @@ extern "C"
       g->eventOffset = -1;
       if (est != MLGPU_OK) return gfail(g, est, "graph_process: the events object refused the block (see its last error)");
     }
-    if (trial) hipEventRecord(g->tuneEv0.get(), g->e->stream);
-    const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->desc.V + (size_t)vl - 1) / (size_t)vl, g->e->stream);
+    if (trial) hipEventRecord(g->tuneEv0.get(), g->e->stream());
+    const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->desc.V + (size_t)vl - 1) / (size_t)vl, g->e->stream());
     if (err != hipSuccess)
     {
       if (eventStaging) mlgpu_events_abandoned_by_graph(g->events, eventStaging);  // (the lanes' record ranges back to "none": no kernel will consume them)
@@ -1421,14 +1421,14 @@ extern "C"
       if (g->desc.outputMix[o])
       {
         const hipError_t merr = g->desc.outputMixShard[o]
-                                    ? mlgpu_launch_mixdown_rows_partial(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], mlgpu_mixdown_shard_level(g->desc.V) - 1, g->e->stream, g->e->kflags)
-                                    : mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream, g->e->kflags);
+                                    ? mlgpu_launch_mixdown_rows_partial(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], mlgpu_mixdown_shard_level(g->desc.V) - 1, g->e->stream(), g->e->kflags)
+                                    : mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream(), g->e->kflags);
         if (merr != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "graph_process: the mixdown's later stages");
         ++r;
       }
     if (trial)
     {
-      hipEventRecord(g->tuneEv1.get(), g->e->stream);
+      hipEventRecord(g->tuneEv1.get(), g->e->stream());
       float ms = 0.f;
       if (hipEventSynchronize(g->tuneEv1.get()) == hipSuccess && hipEventElapsedTime(&ms, g->tuneEv0.get(), g->tuneEv1.get()) == hipSuccess)
       {
@@ -1492,16 +1492,16 @@ extern "C"
     if (K == 0)  // (nothing to launch; the sum of no voices: +0.0)
     {
       for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-        if (g->desc.outputMix[o] && hipMemsetAsync(d_outputs[o], 0, sizeof(float) * 64 * T, g->e->stream) != hipSuccess)
+        if (g->desc.outputMix[o] && hipMemsetAsync(d_outputs[o], 0, sizeof(float) * 64 * T, g->e->stream()) != hipSuccess)
           return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: clearing a mixed-down output");
       return MLGPU_OK;
     }
-    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream);
+    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream());
     if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed launch: ") + hipGetErrorString(err));
     for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
       if (g->desc.outputMix[o])
       {
-        if (mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream, g->e->kflags) != hipSuccess)
+        if (mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream(), g->e->kflags) != hipSuccess)
           return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: the mixdown's later stages");
         ++r;
       }

@@ -397,6 +397,11 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
     vs = a.voiceList[v];
     stride = a.tableStride;
   }
+  else if constexpr (!MIX && OUT_G == 0)
+  {
+    // the plain form over a window of a bank's voices (a launch in two parts): the tables are rows of the whole bank
+    if (a.tableStride != 0) stride = a.tableStride;
+  }
   uint32_t pk = 0;
 
   CH ch;

@@ -44,6 +44,8 @@ struct ChainArgs
   // chain_listed_kernel / chain_listed_mix_kernel (mlgpu_bank_process_listed; chain_kernel_body's LISTED with StoreSink / MixSink): lane i of the launch runs voice voiceList[i] of a
   // bank of tableStride voices - V is then the list's length, coeffs / state / inConst / in / mixGains are read at the voice, out /
   // mix / peaks written at i; peaks[i] (or nullptr) gets the largest |sample| bit pattern of the launch. Else unused.
+  // chain_kernel itself reads tableStride too: non-zero, the launch is a window [v0, v0 + V) of a bank of tableStride voices - coeffs,
+  // state, inConst and out are the host's pointers moved to voice v0, the table rows are tableStride apart (mlgpu_bank_process in two parts)
   const uint32_t* voiceList = nullptr;
   size_t tableStride = 0;
   uint32_t* peaks = nullptr;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mlgpu.h"
+#include "launch_parts.hpp"
 #include "mlgpu_device_args.hpp"
 #include "param_updates.hpp"
 #include "staging_turns.hpp"
@@ -87,7 +88,6 @@ inline hipError_t createTurn(StagingTurn& turn)  // (for the create functions, w
 struct mlgpu_engine
 {
   int device{0};
-  hipStream_t stream{nullptr};
   bool ownsStream{false};
   int cuCount{256};
   std::string lastError;
@@ -123,7 +123,7 @@ struct mlgpu_engine
       return MLGPU_ERR_INVALID;
     }
     hipSetDevice(device);
-    hipStreamSynchronize(stream);
+    hipStreamSynchronize(stream());
     atOnce(obj);
     retire(std::unique_ptr<T>(obj));
     return MLGPU_OK;
@@ -133,6 +133,78 @@ struct mlgpu_engine
   {
     return release(obj, what, [](T*) {});
   }
+
+  // ---- the engine's stream, and the side stream of launches that go out in two parts (launch_parts.hpp) ----
+  // Everything the engine enqueues, waits for or hands out goes through stream(), which first lets the main stream wait for
+  // what is pending on the side stream: nobody can forget the join. Only the two-part launch itself (capi.hip:
+  // mlgpu_bank_process) asks for the streams as they are.
+  hipStream_t stream()
+  {
+    if (parts.any()) join();
+    return mainStream;
+  }
+  hipStream_t streamAsIs() const { return mainStream; }
+  void adoptStream(hipStream_t s) { mainStream = s; }  // (createEngine)
+  // The side stream takes up where the main stream is now. It is made on first use, with the main stream's priority, together with
+  // the two events: all three or none, so a failure leaves nothing half made and the next call tries again. hipSuccess, or why
+  // not: nothing is pending then, and the caller launches in one part.
+  hipError_t fork(hipStream_t* side)
+  {
+    hipError_t err = hipSuccess;
+    if (!sideStream)
+    {
+      int prio = 0;
+      hipStream_t made = nullptr;
+      OwnedEvent fe, je;
+      if ((err = hipStreamGetPriority(mainStream, &prio)) != hipSuccess) return err;
+      if ((err = hipStreamCreateWithPriority(&made, hipStreamNonBlocking, prio)) != hipSuccess) return err;
+      if ((err = allocate(fe, hipEventDisableTiming)) != hipSuccess || (err = allocate(je, hipEventDisableTiming)) != hipSuccess)
+      {
+        hipStreamDestroy(made);
+        return err;
+      }
+      sideStream = made;
+      forkEvent = std::move(fe);
+      joinEvent = std::move(je);
+    }
+    if ((err = hipEventRecord(forkEvent.get(), mainStream)) != hipSuccess) return err;
+    if ((err = hipStreamWaitEvent(sideStream, forkEvent.get(), 0)) != hipSuccess) return err;
+    *side = sideStream;
+    return hipSuccess;
+  }
+  hipStream_t sideAsIs() const { return sideStream; }
+  // The main stream waits for the side stream's work; where the event cannot carry that, the host waits instead. What failed
+  // is kept in sideError, with the name of the call whose part was pending, for the next call that reports a status.
+  void join()
+  {
+    hipError_t err = hipEventRecord(joinEvent.get(), sideStream);
+    if (err == hipSuccess) err = hipStreamWaitEvent(mainStream, joinEvent.get(), 0);
+    if (err != hipSuccess)
+    {
+      const hipError_t waited = hipStreamSynchronize(sideStream);
+      sideError = waited != hipSuccess ? waited : err;
+      sideErrorCall = partsCall;
+    }
+    parts.joined();
+    ++joins;
+  }
+  ~mlgpu_engine()
+  {
+    if (sideStream) hipStreamDestroy(sideStream);
+  }
+
+  mlparts::Pending parts;     // what runs on the side stream since the streams last met
+  const char* partsCall{""};  // ... and the call that put it there
+  int launchParts{mlparts::kAuto};  // mlgpu_engine_set_launch_parts
+  bool streamHandedOut{false};      // mlgpu_engine_stream has given the main stream away: every launch in one part from then on
+  uint64_t splitLaunches{0}, joins{0};  // mlgpu_engine_launch_stats
+  hipError_t sideError{hipSuccess};
+  const char* sideErrorCall{""};
+
+ private:
+  hipStream_t mainStream{nullptr};
+  hipStream_t sideStream{nullptr};
+  OwnedEvent forkEvent, joinEvent;
 };
 
 struct mlgpu_fence  // mlgpu_engine_signal / mlgpu_engine_wait: a point in one engine's stream that another engine's stream can wait for
@@ -185,6 +257,7 @@ struct ChainEntry
   const char* kernelName;  // prefix of the name a profiler shows for the device kernel
   const char* (*kernelNameFor)(size_t V, uint32_t flags){nullptr};  // where the kernel depends on the bank's size (SVF cascades)
   const char* alias;       // e.g. "chain_kernel<SawGen,Bandpass,Gain>"
+  bool plainTakesWindow{false};  // the plain form runs a window of a bank's voices (ChainArgs::tableStride): chain_kernel, not the cascades
   int nc, ns;
 };
 

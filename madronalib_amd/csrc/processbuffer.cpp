@@ -203,7 +203,7 @@ extern "C"
       const char* step = "H2D";
       hipError_t err = hipSetDevice(e->device);
       const bool deviceSet = err == hipSuccess;  // from here on the stream may hold work that uses the set: one way out, through submitted()
-      if (err == hipSuccess && nIn) err = hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(float) * nIn * chan, hipMemcpyHostToDevice, e->stream);
+      if (err == hipSuccess && nIn) err = hipMemcpyAsync(sg.d.get(), sg.h.get(), sizeof(float) * nIn * chan, hipMemcpyHostToDevice, e->stream());
       int st = MLGPU_OK;
       if (err == hipSuccess)
       {
@@ -211,9 +211,9 @@ extern "C"
         for (size_t c = 0; c < nOut; ++c) p->d_out[c] = sg.d.get() + (nIn + c) * chan;
         st = fn(user, K, p->d_in.data(), p->d_out.data());
         step = "D2H";
-        if (st == MLGPU_OK) err = hipMemcpyAsync(sg.h.get() + nIn * chan, sg.d.get() + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream);
+        if (st == MLGPU_OK) err = hipMemcpyAsync(sg.h.get() + nIn * chan, sg.d.get() + nIn * chan, sizeof(float) * nOut * chan, hipMemcpyDeviceToHost, e->stream());
       }
-      if (deviceSet) sg.turn.submitted(e->stream);
+      if (deviceSet) sg.turn.submitted(e->stream());
       if (err != hipSuccess)
       {
         e->lastError = std::string("process_buffer_process (") + step + "): " + hipGetErrorString(err);

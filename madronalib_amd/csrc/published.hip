@@ -115,7 +115,7 @@ extern "C"
     if (hipSetDevice(e->device) != hipSuccess) return MLGPU_ERR_HIP;
     if (floats > p->stageFloats)
     {
-      hipStreamSynchronize(e->stream);
+      hipStreamSynchronize(e->stream());
       p->stageFloats = 0;
       if (allocate(p->d_stage, floats) != hipSuccess || allocate(p->h_stage, floats) != hipSuccess)
       {
@@ -144,10 +144,10 @@ extern "C"
     a.framesPerVector = framesPerVector;
     size_t blocks = (nVectors * nVoices * (size_t)framesPerVector + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(publish_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, e->stream, a);
+    hipLaunchKernelGGL(publish_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, e->stream(), a);
     hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(p->h_stage.get(), p->d_stage.get(), floats * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(p->h_stage.get(), p->d_stage.get(), floats * sizeof(float), hipMemcpyDeviceToHost, e->stream());
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream());
     if (err != hipSuccess)
     {
       e->lastError = std::string("published_signal_write: ") + hipGetErrorString(err);

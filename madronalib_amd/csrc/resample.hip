@@ -209,7 +209,7 @@ extern "C"
   {
     if (!r) return MLGPU_ERR_INVALID;
     if (hipSetDevice(r->e->device) != hipSuccess) return MLGPU_ERR_HIP;
-    const hipError_t err = hipMemsetAsync(r->d_state.get(), 0, sizeof(float) * r->V * (size_t)(r->octaves * 9 + 1), r->e->stream);
+    const hipError_t err = hipMemsetAsync(r->d_state.get(), 0, sizeof(float) * r->V * (size_t)(r->octaves * 9 + 1), r->e->stream());
     if (err != hipSuccess)
     {
       r->e->lastError = std::string("resampler_clear: ") + hipGetErrorString(err);
@@ -278,13 +278,13 @@ extern "C"
     hipError_t err = hipSuccess;
     switch (r->octaves)
     {
-      case 0: err = launchResample<0>(r->up, a, e->stream); break;
-      case 1: err = launchResample<1>(r->up, a, e->stream); break;
-      case 2: err = launchResample<2>(r->up, a, e->stream); break;
-      case 3: err = launchResample<3>(r->up, a, e->stream); break;
-      case 4: err = launchResample<4>(r->up, a, e->stream); break;
-      case 5: err = launchResample<5>(r->up, a, e->stream); break;
-      default: err = launchResample<6>(r->up, a, e->stream); break;
+      case 0: err = launchResample<0>(r->up, a, e->stream()); break;
+      case 1: err = launchResample<1>(r->up, a, e->stream()); break;
+      case 2: err = launchResample<2>(r->up, a, e->stream()); break;
+      case 3: err = launchResample<3>(r->up, a, e->stream()); break;
+      case 4: err = launchResample<4>(r->up, a, e->stream()); break;
+      case 5: err = launchResample<5>(r->up, a, e->stream()); break;
+      default: err = launchResample<6>(r->up, a, e->stream()); break;
     }
     if (err != hipSuccess)
     {

@@ -184,9 +184,9 @@ extern "C"
       if (err == hipSuccess) err = allocate(s.h, n);
       if (err == hipSuccess) err = createTurn(s.turn);
     }
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_omega.get(), 0, sizeof(float) * n, e->stream);  // omega_{0}, dpdt_{0}
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_dpdt.get(), 0, sizeof(double) * n, e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(t->d_out.get(), 0, sizeof(float) * 64 * maxVectors * n, e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_omega.get(), 0, sizeof(float) * n, e->stream());  // omega_{0}, dpdt_{0}
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_dpdt.get(), 0, sizeof(double) * n, e->stream());
+    if (err == hipSuccess) err = hipMemsetAsync(t->d_out.get(), 0, sizeof(float) * 64 * maxVectors * n, e->stream());
     if (err != hipSuccess)
     {
       e->lastError = std::string("transport_create: ") + hipGetErrorString(err);
@@ -211,10 +211,10 @@ extern "C"
     if (t->e->liveSequences > 0)
       return tfail(t, MLGPU_ERR_INVALID, "transport_reserve would move the beat-phase signal that recorded sequences of this engine may read: destroy them first");
     if (hipSetDevice(t->e->device) != hipSuccess) return tfail(t, MLGPU_ERR_HIP, "hipSetDevice");
-    hipStreamSynchronize(t->e->stream);
+    hipStreamSynchronize(t->e->stream());
     DeviceBuffer<float> fresh;
     if (allocate(fresh, 64 * maxVectors * t->n) != hipSuccess) return tfail(t, MLGPU_ERR_OOM, "transport_reserve");
-    hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * t->n, t->e->stream);
+    hipMemsetAsync(fresh.get(), 0, sizeof(float) * 64 * maxVectors * t->n, t->e->stream());
     t->d_out = std::move(fresh);  // mlgpu_transport_beat_phase returns the new pointer from now on
     t->maxVectors = t->capacityVectors = maxVectors;
     return MLGPU_OK;
@@ -267,13 +267,13 @@ extern "C"
         s.dirty = s.setOmega = false;
       }
       t->dirty.clear();
-      const bool uploaded = hipMemcpyAsync(sg->d.get(), sg->h.get(), sizeof(Update) * n, hipMemcpyHostToDevice, e->stream) == hipSuccess;
+      const bool uploaded = hipMemcpyAsync(sg->d.get(), sg->h.get(), sizeof(Update) * n, hipMemcpyHostToDevice, e->stream()) == hipSuccess;
       if (uploaded)
-        hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, sg->d.get(), n, t->d_omega.get(), t->d_dpdt.get());
-      sg->turn.submitted(e->stream);  // (after a failed copy too)
+        hipLaunchKernelGGL(transport_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream(), sg->d.get(), n, t->d_omega.get(), t->d_dpdt.get());
+      sg->turn.submitted(e->stream());  // (after a failed copy too)
       if (!uploaded) return tfail(t, MLGPU_ERR_HIP, "transport_process: upload");
     }
-    hipLaunchKernelGGL(transport_kernel, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, e->stream, t->d_omega.get(), t->d_dpdt.get(), t->d_out.get(), t->n, nVectors);
+    hipLaunchKernelGGL(transport_kernel, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, e->stream(), t->d_omega.get(), t->d_dpdt.get(), t->d_out.get(), t->n, nVectors);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {

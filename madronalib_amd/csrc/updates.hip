@@ -110,7 +110,7 @@ int mlgpu_updater_reserve(mlgpu_engine* e, mlgpu_updater& u, size_t maxDeviceRec
   if (maxDeviceRecords == 0 || maxDeviceRecords > kMaxDeviceRecords) return ufail(err, MLGPU_ERR_INVALID, "reserve_updates: 1 .. 2^25 device records");
   if (hipSetDevice(e->device) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "hipSetDevice");
   // (launches that read the old buffers may be in flight)
-  if (hipStreamSynchronize(e->stream) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipStreamSynchronize");
+  if (hipStreamSynchronize(e->stream()) != hipSuccess) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipStreamSynchronize");
   u.stage.drained();
   if (!u.stage.create()) return ufail(err, MLGPU_ERR_HIP, "reserve_updates: hipEventCreate");
   for (mlgpu_updater::Set& sg : u.stage.set)
@@ -150,7 +150,7 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
   // setup convenience that allocates and may wait (nothing of this set is in flight: it was taken)
   if (!u.reserved && !growPair(sg.h_recs, sg.d_recs, sg.capacity, nDev, std::max<size_t>(1024, 2 * nDev))) return ufail(err, MLGPU_ERR_OOM, "apply_updates: record buffers");
   u.planner.pack(u.desc, recs, n, sg.h_recs.get());
-  hipError_t herr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(DevRec) * nDev, hipMemcpyHostToDevice, e->stream);
+  hipError_t herr = hipMemcpyAsync(sg.d_recs.get(), sg.h_recs.get(), sizeof(DevRec) * nDev, hipMemcpyHostToDevice, e->stream());
   UpdateArgs a;
   for (uint32_t t = 0; t < mlupd::kTables; ++t) a.tables[t] = tables[t];
   a.V = u.desc.V;
@@ -160,7 +160,7 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
     const size_t end = u.planner.batchEnd(b);
     a.recs = (const uint4*)(sg.d_recs.get() + begin);
     a.n = (uint32_t)(end - begin);
-    hipLaunchKernelGGL(apply_updates_kernel, dim3(a.n / 4u + (a.n % 4u ? 1u : 0u)), dim3(256), 0, e->stream, a);
+    hipLaunchKernelGGL(apply_updates_kernel, dim3(a.n / 4u + (a.n % 4u ? 1u : 0u)), dim3(256), 0, e->stream(), a);
     herr = hipGetLastError();
     begin = end;
   }
@@ -181,10 +181,10 @@ int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tabl
     ra.mem = ringMem;
     ra.memWords = ringMemWords;
     ra.wide = wordsPerStore == 4u;
-    hipLaunchKernelGGL(clear_rings_kernel, dim3((uint32_t)nRing, (uint32_t)y), dim3(256), 0, e->stream, ra);
+    hipLaunchKernelGGL(clear_rings_kernel, dim3((uint32_t)nRing, (uint32_t)y), dim3(256), 0, e->stream(), ra);
     herr = hipGetLastError();
   }
-  sg.turn.submitted(e->stream);  // (after a failed copy or launch too)
+  sg.turn.submitted(e->stream());  // (after a failed copy or launch too)
   if (herr != hipSuccess) return ufail(err, MLGPU_ERR_HIP, std::string("apply_updates: ") + hipGetErrorString(herr));
   return MLGPU_OK;
 }
