@@ -934,7 +934,8 @@ int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h
  * voice lists enabled that the listed form does not serve:
  *   delay ring layouts 1, 2 and 4 - also where layout 3 resolves to one of them: their LDS windows and 64-byte pieces are made by a
  *   wavefront's neighbouring voices of one 256-voice block (layout 0, the rows, is served: mlgpu_graph_set_delay_layout(g, 0));
- *   an output group sum (mlgpu_graph_set_output_group_sum); the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2));
+ *   an output group sum (mlgpu_graph_set_output_group_sum) without mlgpu_graph_enable_voice_list_groups (below), with it a mixdown of
+ *   all voices in either form and outputs summed by groups of different sizes or none at all; the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2));
  *   event rows (mlgpu_graph_add_event_row: the events object goes by lane); a MLGPU_REGION_DOWNSAMPLE_2X region (it pairs DSPVectors
  *   2k and 2k + 1 by the graph's count, not by a voice's).
  * Input groups, UPSAMPLE_2X regions, feedback nodes, controls, live constants, const vectors, routes and impulse tables are served.
@@ -962,6 +963,45 @@ int mlgpu_graph_process_listed(mlgpu_graph* g, size_t n_vectors, const float* co
                                const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
 const char* mlgpu_graph_listed_source(mlgpu_graph* g);
 int mlgpu_graph_emit_listed(mlgpu_graph* g, const void** code, size_t* code_size);
+/* LISTED GROUP SUMS of a graph: Synth::processVector's voice sum per instrument over the listed voices only - the bank's LISTED GROUP
+ * SUMS (mlgpu_bank_process_listed_groups) for a graph whose outputs are summed by mlgpu_graph_set_output_group_sum. The graph's voices
+ * are instruments of G adjacent voices, G the one group size of its group-summed outputs. With the list L[0 .. K) in force:
+ *   The listed instruments M[0 .. J) are the distinct values of L[i] / G in ascending order.
+ *   A group-summed output is a signal of J rows in `out_layout`: 64 * n_vectors * J floats, written once. Row j is
+ *   ((0 + y[a0]) + y[a1]) + ... over the listed voices a0 < a1 < ... of instrument M[j]: float32 adds in the engine's floating-point
+ *   mode, y the float mlgpu_graph_process_listed would store for that voice. A lone -0.0 voice gives +0.0. With every voice listed the
+ *   output has the bits of mlgpu_graph_process on the same graph. There are no gains: a graph multiplies inside the graph.
+ *   Everything else is the VOICE LISTS rule above: every plain output is a signal of K rows by list position, d_peak[K] is by list
+ *   position and taken before the sums, over every output; what belongs to a voice is addressed by its voice index; unlisted voices are
+ *   neither read nor written and no time passes for them; any split of n_vectors into several calls gives the bits of one call.
+ *
+ * mlgpu_graph_enable_voice_list_groups(g, 1) is a build call like mlgpu_graph_enable_voice_lists, and turns that on too
+ * (mlgpu_graph_enable_voice_lists(g, 0) turns both off). The graph's listed kernel - still one extra kernel, under the same name, in
+ * the same caches, emitted by mlgpu_graph_emit_listed - then goes by the bank's LANE PLAN: a listed instrument's voices are a run of
+ * lanes that never crosses a wavefront, the lanes in between idle. Without the switch nothing changes: both kernels' text, and the
+ * refusal of voice lists with an output group sum. With it mlgpu_graph_compile / mlgpu_graph_emit refuse, naming the reason:
+ *   MLGPU_ERR_INVALID      no output with a group sum, or group sums of different sizes;
+ *   MLGPU_ERR_UNSUPPORTED  an output that is the mixdown of all voices, in either form (its tree goes by list position in whole
+ *                          wavefronts, a lane plan has idle lanes); what the listed form refuses anyway - ring layouts 1, 2 and 4,
+ *                          event rows, a DOWNSAMPLE_2X region; more LDS than a workgroup has (16 KiB + 256 B per group-summed output
+ *                          next to the early ring reads' slots and the impulse table).
+ *
+ * mlgpu_graph_reserve_voice_list_groups(max_listed) is the setup call, mlgpu_bank_reserve_voice_list_groups with the graph's G: it
+ * allocates and may wait, and from then on mlgpu_graph_set_voice_list makes and uploads the plan with the list, with unchanged
+ * discipline. mlgpu_graph_reserve_voice_list and mlgpu_graph_set_voice_list are the calls they were. mlgpu_graph_listed_group_count:
+ * J of the list in force. mlgpu_graph_listed_groups: M[0 .. J) into h_groups from the host's copy (MLGPU_ERR_RANGE: capacity < J).
+ *
+ * mlgpu_graph_process_listed_groups never allocates and does not advance the graph's DSPVector count. With an empty list it launches
+ * nothing and returns MLGPU_OK. MLGPU_ERR_INVALID: a graph without mlgpu_graph_enable_voice_list_groups; no
+ * mlgpu_graph_reserve_voice_list_groups; misaligned peaks (4 bytes); null or misaligned signals; a bad layout; a call while recording a
+ * sequence - the launch's lane count and J go with the list's contents, not only its length, so a recorded launch could not follow a
+ * later list. On a graph with the switch mlgpu_graph_process_listed answers MLGPU_ERR_INVALID and names this call. */
+int mlgpu_graph_enable_voice_list_groups(mlgpu_graph* g, int on);
+int mlgpu_graph_reserve_voice_list_groups(mlgpu_graph* g, size_t max_listed);
+size_t mlgpu_graph_listed_group_count(mlgpu_graph* g);
+int mlgpu_graph_listed_groups(mlgpu_graph* g, uint32_t* h_groups, size_t capacity);
+int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t n_vectors, const float* const* d_inputs, int in_layout,
+                                      const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
 
 /* Chains without an ahead-of-time kernel are fused with hiprtc when their bank is created
  * (default on). With jit off they run processor by processor through HBM scratch signals. */

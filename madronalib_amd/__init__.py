@@ -1161,7 +1161,7 @@ class Graph(_Handle):
     _destroy = "mlgpu_graph_destroy"
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
-                 live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False):
+                 live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1182,6 +1182,8 @@ class Graph(_Handle):
             self._check(self.L.mlgpu_graph_set_live_constants(self.h, 1))
         if voice_lists:   # compile makes the listed form of the kernel too: set_voice_list / process_listed
             self.enable_voice_lists()
+        if voice_list_groups:   # ... and the listed form goes by the lane plan: reserve_voice_list_groups / process_listed_groups
+            self.enable_voice_list_groups()
         if description is not None:
             for n in description:
                 self.add(**n)
@@ -1263,6 +1265,36 @@ class Graph(_Handle):
         pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
         pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
         self._check(self.L.mlgpu_graph_process_listed(self.h, int(n_vectors), pi, int(in_layout), pc, po, int(out_layout), pp))
+
+    def enable_voice_list_groups(self, on=True):
+        """Before compile: voice lists, with the listed kernel going by the lane plan - the group-summed outputs get one row per
+        listed instrument (mlgpu_graph_enable_voice_list_groups). enable_voice_lists(False) turns both off."""
+        self._check(self.L.mlgpu_graph_enable_voice_list_groups(self.h, 1 if on else 0))
+
+    def reserve_voice_list_groups(self, max_listed):
+        """Setup: reserve_voice_list(max_listed), and from now on set_voice_list also makes and uploads the lane plan
+        process_listed_groups runs by; the instruments are the groups of the graph's group-summed outputs
+        (mlgpu_graph_reserve_voice_list_groups)."""
+        self._check(self.L.mlgpu_graph_reserve_voice_list_groups(self.h, int(max_listed)))
+
+    @property
+    def listed_groups(self):
+        """The listed instruments M[0 .. J): the distinct list[i] // G, ascending, as a numpy uint32 array - from the host's copy, no
+        device wait (mlgpu_graph_listed_groups)."""
+        m = np.zeros(int(self.L.mlgpu_graph_listed_group_count(self.h)), np.uint32)
+        self._check(self.L.mlgpu_graph_listed_groups(self.h, _np_ptr(m) if m.size else None, m.size))
+        return m
+
+    def process_listed_groups(self, n_vectors, d_inputs, d_outputs, in_layout=Layout.QUAD, out_layout=Layout.QUAD, d_controls=(), d_peak=None):
+        """process_listed with every group-summed output summed by instrument: such an output has one row per listed instrument
+        (J = len(listed_groups()) rows), the in-order sum ((0 + y0) + y1) + ... of the instrument's listed voices; plain outputs have
+        K rows and d_peak K words by list position. Not while recording a sequence (mlgpu_graph_process_listed_groups)."""
+        raw = lambda b: b.ptr if hasattr(b, "ptr") else int(b)  # noqa: E731
+        pi = (ctypes.c_void_p * max(1, len(d_inputs)))(*[raw(b) for b in d_inputs])
+        po = (ctypes.c_void_p * max(1, len(d_outputs)))(*[raw(b) for b in d_outputs])
+        pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
+        pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
+        self._check(self.L.mlgpu_graph_process_listed_groups(self.h, int(n_vectors), pi, int(in_layout), pc, po, int(out_layout), pp))
 
     def _id(self, ref):
         return self.ids[ref] if isinstance(ref, str) else int(ref)

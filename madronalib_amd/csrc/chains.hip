@@ -19,7 +19,7 @@
 #include "mldsp_kernels.hpp"
 
 using namespace mldev;
-static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip && kHostTurnClockShift == kTurnClockShift &&
+static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip && kHostSegmentStripFloats == kSegmentStrip && kHostSegmentTailFloats == kSegmentTail && kHostTurnClockShift == kTurnClockShift &&
                   kHostGraphMaxInputs == MLGPU_GRAPH_MAX_INPUTS && kHostGraphMaxOutputs == MLGPU_GRAPH_MAX_OUTPUTS,
               "graph_codegen.hpp's copies of what the device headers fix");
 

@@ -48,11 +48,13 @@ struct GraphBuild
   std::string listedSource, listedLog;
   std::vector<char> listedCode;
 };
-// the listed kernel's form: one voice per lane, the plan's quads per trip (autotune and voices per lane do not apply to it)
-KernelForm listedForm(const GraphPlan& p)
+// the listed kernel's form: one voice per lane, the plan's quads per trip (autotune and voices per lane do not apply to it); by the
+// lane plan where the description says so (mlgpu_graph_enable_voice_list_groups)
+KernelForm listedForm(const GraphDesc& d, const GraphPlan& p)
 {
   KernelForm f{1, p.form.quadsPerTrip, 0};
   f.listed = true;
+  f.planned = d.voiceListGroups;
   return f;
 }
 }  // namespace
@@ -155,8 +157,13 @@ TestHooks readTestHooks()
 // 128 + 156 bytes of scratch per lane, 1.82 -> 1.46 ms; the voice with its EventsToSignals rows inside: 259 -> 128 + 528 bytes,
 // 3.13 -> 1.56 ms, where bounds of two and three wavefronts give 1.96 and 1.85). The test hook MLGPU_GRAPH_MIN_WAVES=0 / N
 // overrides (GraphPlan::minWavesHook).
+// The lane plan's listed form (KernelForm::planned) takes a bound only if it costs no scratch at all: its segment sums hold up to
+// 32 registers of LDS reads next to the voice's state every fourth quad, a spill there is paid in the loop, and its launches are the
+// sounding voices of a bank, not the bank (the config-5 voice, K = V / 8: 397 us at p50 bounded to four wavefronts with 168 bytes of
+// scratch, 278 us unbounded - profiles/graph_voice_list_groups.md).
 bool generateBudgeted(const GraphDesc& d, const GraphPlan& p, KernelForm form, std::string& source, std::vector<char>& code, std::string& log)
 {
+  const long maxScratch = form.planned ? 0 : 640;
   form.minWaves = std::max(0, p.minWavesHook);
   source = generateGraphSource(d, p, form);
   if (!mlgpu_jit_code(source, code, log)) return false;
@@ -171,7 +178,7 @@ bool generateBudgeted(const GraphDesc& d, const GraphPlan& p, KernelForm form, s
     std::vector<char> boundedCode;
     std::string boundedLog;
     long scratch = 0;
-    if (mlgpu_jit_code(bounded, boundedCode, boundedLog) && mlgpu_jit_code_number(boundedCode, ".private_segment_fixed_size", scratch) && scratch <= 640)
+    if (mlgpu_jit_code(bounded, boundedCode, boundedLog) && mlgpu_jit_code_number(boundedCode, ".private_segment_fixed_size", scratch) && scratch <= maxScratch)
     {
       source = bounded;
       code.swap(boundedCode);
@@ -735,7 +742,7 @@ extern "C"
       r.error = "graph_compile (hiprtc): " + b.log;
       return;
     }
-    if (!d.voiceLists || generateBudgeted(d, b.plan, listedForm(b.plan), b.listedSource, b.listedCode, b.listedLog)) return;
+    if (!d.voiceLists || generateBudgeted(d, b.plan, listedForm(d, b.plan), b.listedSource, b.listedCode, b.listedLog)) return;
     r.status = MLGPU_ERR_UNSUPPORTED;
     r.error = "graph_compile (hiprtc, the listed form): " + b.listedLog;
   }
@@ -1141,6 +1148,16 @@ extern "C"
   {
     if (const int st = checkEditable(g, "graph_enable_voice_lists: before mlgpu_graph_compile")) return st;
     g->desc.voiceLists = on != 0;
+    if (!on) g->desc.voiceListGroups = false;
+    return MLGPU_OK;
+  }
+  // ... and the listed form goes by the host's lane plan: the graph's group-summed outputs get one row per listed instrument
+  // (mlgpu_graph_process_listed_groups). on = 1 turns voice lists on too; mlgpu_graph_enable_voice_lists(g, 0) turns both off.
+  int mlgpu_graph_enable_voice_list_groups(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_voice_list_groups: before mlgpu_graph_compile")) return st;
+    g->desc.voiceListGroups = on != 0;
+    if (on) g->desc.voiceLists = true;
     return MLGPU_OK;
   }
   int mlgpu_graph_set_live_constants(mlgpu_graph* g, int on)
@@ -1469,6 +1486,8 @@ extern "C"
                                  int outLayout, uint32_t* d_peak)
   {
     if (const int st = listsReady(g, "graph_process_listed")) return st;
+    if (g->desc.voiceListGroups)
+      return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: the graph's listed kernel goes by the lane plan (mlgpu_graph_enable_voice_list_groups): mlgpu_graph_process_listed_groups runs it");
     if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: misaligned peaks");
     if (T == 0) return MLGPU_OK;
     GraphArgs a;
@@ -1505,6 +1524,64 @@ extern "C"
           return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: the mixdown's later stages");
         ++r;
       }
+    return MLGPU_OK;
+  }
+
+  // ---- the listed voices with the group-summed outputs summed by instrument (voice_list.hpp plans the lanes, the planned form of the generated kernel runs them) ----
+  static int listGroupsReady(mlgpu_graph* g, const char* who)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->desc.voiceListGroups)
+      return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph's listed form does not go by a lane plan - mlgpu_graph_enable_voice_list_groups(g, 1) before compile");
+    if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": compile first");
+    return MLGPU_OK;
+  }
+  int mlgpu_graph_reserve_voice_list_groups(mlgpu_graph* g, size_t maxListed)
+  {
+    if (const int st = listGroupsReady(g, "graph_reserve_voice_list_groups")) return st;
+    int G = 0;  // (planGraph: every group-summed output has this size, and there is one)
+    for (size_t o = 0; o < g->desc.outputs.size(); ++o) G = g->desc.outputGroup[o] ? g->desc.outputGroup[o] : G;
+    const int st = g->list.reserve(g->e, maxListed, "graph_reserve_voice_list_groups", G);
+    return st == MLGPU_OK ? st : gfail(g, st, g->e->lastError);
+  }
+  size_t mlgpu_graph_listed_group_count(mlgpu_graph* g) { return (g && !g->job) ? g->list.planGroups : 0; }
+  int mlgpu_graph_listed_groups(mlgpu_graph* g, uint32_t* h_groups, size_t capacity)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    const size_t J = g->list.planGroups;
+    if (J == 0) return MLGPU_OK;
+    if (!h_groups) return gfail(g, MLGPU_ERR_INVALID, "graph_listed_groups: null array");
+    if (capacity < J) return gfail(g, MLGPU_ERR_RANGE, "graph_listed_groups: the array is shorter than mlgpu_graph_listed_group_count");
+    memcpy(h_groups, g->list.groups.data(), sizeof(uint32_t) * J);
+    return MLGPU_OK;
+  }
+
+  int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
+                                        int outLayout, uint32_t* d_peak)
+  {
+    if (const int st = listGroupsReady(g, "graph_process_listed_groups")) return st;
+    if (g->e->recording)
+      return gfail(g, MLGPU_ERR_INVALID,
+                   "graph_process_listed_groups: not while recording a sequence - the launch's lane count and its rows go with the list's contents, not "
+                   "only its length, so a recorded launch could not follow a later list");
+    if (g->list.outGroup == 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed_groups: call mlgpu_graph_reserve_voice_list_groups(graph, max listed voices) at setup");
+    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed_groups: misaligned peaks");
+    if (T == 0) return MLGPU_OK;
+    GraphArgs a;
+    if (const int st = signalArgs(g, a, "graph_process_listed_groups", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
+    const size_t K = g->list.size, N = g->list.planLanes, J = g->list.planGroups;
+    if (K == 0) return MLGPU_OK;  // (no listed instrument: no row to write)
+    a.t0 = g->vectorCount;  // (not advanced here; no listed graph has a region that reads it)
+    a.listed = N;
+    a.lanePlan = g->list.d_plan.get();
+    a.peaks = d_peak;
+    // a group-summed output: J rows, one per listed instrument; every other output: K rows by list position
+    for (size_t o = 0; o < g->desc.outputs.size(); ++o) a.out[o] = makeView(d_outputs[o], outLayout, g->desc.outputGroup[o] ? J : K, T);
+    if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
+    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream());
+    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed_groups launch: ") + hipGetErrorString(err));
     return MLGPU_OK;
   }
 }

@@ -270,11 +270,14 @@ struct GraphEmitter
   std::ostringstream s;
   bool windowed, partialWaves, stateAddr32, PF, oscTrips, ringTrips;
   const bool listed;  // the listed form: a lane's place is its position in the voice list (vr), its voice the list's entry there (v)
+  // ... by the host's lane plan (mlgpu_graph_process_listed_groups): a lane's place in the launch (vr) is a plan entry - its voice (v), its
+  // list position (pl), the row of its instrument and its place in the segment of that instrument's listed voices - or a pad
+  const bool planned;
   std::string ringLane, places;
   // ring layout 4, per wavefront: every delay node's held sectors (512 floats per ring) and history rows (1024 floats per node)
   std::vector<size_t> sectorLdsOff;
   size_t sectorLdsPerWave{0};
-  GraphEmitter(const GraphDesc& graph, const GraphPlan& plan, const KernelForm& f) : g(graph), p(plan), form(f), VL(f.listed ? 1 : f.voicesPerLane), listed(f.listed), sectorLdsOff(graph.nodes.size(), 0)
+  GraphEmitter(const GraphDesc& graph, const GraphPlan& plan, const KernelForm& f) : g(graph), p(plan), form(f), VL(f.listed ? 1 : f.voicesPerLane), listed(f.listed), planned(f.listed && f.planned), sectorLdsOff(graph.nodes.size(), 0)
   {
     windowed = p.rings != RingLayout::ROWS && p.totalRings;
     if (p.rings == RingLayout::SECTORS)
@@ -295,6 +298,7 @@ struct GraphEmitter
     // (the listed form: the list's length is known at the launch only - with a mixed-down output the last wavefront's spare lanes
     // always stay and run the list's last voice again; without one a lane past the list's end returns)
     if (listed) partialWaves = anyMix;
+    if (planned) partialWaves = false;  // (the lane plan has no mixdown tree - planGraph -, and a lane at or past its end leaves)
     ringLane = partialWaves ? "vr" : "v";
     places = listed ? "a.listed" : "a.V";
     // a row of the state memory at this lane: the row's address is wave-uniform (scalar arithmetic), the lane's place a 32-bit offset on
@@ -309,7 +313,10 @@ struct GraphEmitter
   // a group sum of 16 voices (one instrument's voices): four quads of the wavefront's 64 voices are parked in LDS and every lane
   // then adds up ONE (instrument, sample) pair in voice order - 2.3 instructions per voice-sample where the lane-shift chain
   // (group_sum_in_order) takes 16
-  bool ldsSum(size_t o) const { return VL == 1 && g.outputGroup[o] == 16; }
+  bool ldsSum(size_t o) const { return !planned && VL == 1 && g.outputGroup[o] == 16; }
+  // the lane plan's group sum, for every group size: a group's listed voices are a SEGMENT of the wavefront's lanes, parked in the
+  // wavefront's segment strip and added up in rank order by the segment's last lane (mldsp_math.hpp: segment_park / segment_sum_store)
+  bool segSum(size_t o) const { return planned && g.outputGroup[o] != 0; }
   std::string stateRef(const std::string& row, int l) const
   {
     return stateAddr32 ? "*state_row(a, " + row + ", v4" + sfx(l) + ")" : "a.state[(size_t)(" + row + ") * a.V + v" + sfx(l) + "]";
@@ -339,7 +346,7 @@ struct GraphEmitter
   void header()
   {
     const std::string ringWindows = p.rings == RingLayout::ROWS ? std::string() : "#define MLGPU_RING_WINDOWS " + std::to_string((int)p.rings) + "\n";
-    s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane" << (listed ? ", the voices of a list" : "") << ")\n" << ringWindows
+    s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane" << (planned ? ", the voices of a list by its lane plan" : listed ? ", the voices of a list" : "") << ")\n" << ringWindows
       << (g.strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\n#include \"mldsp_ops.hpp\"\n"
       << (g.hasEventRows ? "#include \"mldsp_events.hpp\"\n" : "") << "using namespace mldev;\n";
     for (size_t i = 0; i < g.nodes.size(); ++i)
@@ -369,6 +376,10 @@ struct GraphEmitter
       if (ldsSum(o))
         s << "  __shared__ float ldsSum" << o << "[4 * kGroup16Strip];\n  float* const strip" << o << " = ldsSum" << o << " + (threadIdx.x >> 6) * kGroup16Strip;\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (segSum(o))
+        s << "  __shared__ __attribute__((aligned(16))) float ldsSeg" << o << "[4 * kSegmentStrip + kSegmentTail];\n  float* const seg" << o << " = ldsSeg" << o
+          << " + (threadIdx.x >> 6) * kSegmentStrip;\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
       if (g.outputMix[o])
         s << "  __shared__ __attribute__((aligned(16))) float ldsMix" << o << "[4 * kMixStrip];\n  float* const mstrip" << o << " = ldsMix" << o << " + (threadIdx.x >> 6) * kMixStrip;\n";
   }
@@ -377,7 +388,19 @@ struct GraphEmitter
   {
     s << "  size_t blk = blockIdx.x;\n  const size_t nbFull = (size_t)gridDim.x & ~(size_t)7;\n"
          "  if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);\n";
-    if (listed)
+    if (planned)
+    {
+      // The lane's place in the launch (vr) and its plan entry, one 16-byte load: .x the voice (v), .y the list position (pl: plain
+      // outputs and peaks), .z the row of its instrument, .w rank | length << 8 in its segment. A lane at or past the plan's end and a
+      // pad leave here - after the impulse table's barrier, the only one of the kernel, and before every wave-uniform ballot below,
+      // which so counts the wavefront's voices alone. A pad loads, runs and stores nothing.
+      s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n  if (vr_0 >= a.listed) return;\n  const uint4 plan = ((const uint4*)a.lanePlan)[vr_0];\n"
+           "  if (plan.x == 0xFFFFFFFFu) return;  // a pad\n  const size_t v_0 = plan.x, pl_0 = plan.y;\n"
+           "  const unsigned rank_0 = plan.w & 0xFFu, length_0 = plan.w >> 8;\n  __builtin_assume(length_0 != 0u);\n  uint32_t pk_0 = 0u;\n";
+      // the wavefront's longest segment, rounded up to a size segment_sum_store has the reads of
+      s << "  const int longest = " << ballot("length_0 > 8u") << " ? 16 : (" << ballot("length_0 > 4u") << " ? 8 : (" << ballot("length_0 > 2u") << " ? 4 : 2));\n";
+    }
+    else if (listed)
     {
       // the lane's place in the list (vr), the place whose voice it runs and whose rows it stores to (pl), the voice (v): everything
       // below that is made of v - tables, ring rows, input rows, control columns - is the gathered voice's
@@ -474,7 +497,9 @@ struct GraphEmitter
     for (size_t o = 0; o < g.outputs.size(); ++o)
       for (int l = 0; l < VL; ++l)
       {
-        if (g.outputMix[o])  // the rows of 64-voice group sums (mlgpu_mixdown's first stage): [(group * T + t) * 64 + sample]
+        if (segSum(o))  // row j of a signal of J rows: the lane's instrument among the listed ones
+          s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + (size_t)plan.z * a.out[" << o << "].strideV;\n";
+        else if (g.outputMix[o])  // the rows of 64-voice group sums (mlgpu_mixdown's first stage): [(group * T + t) * 64 + sample]
           s << "  float* const out" << o << sfx(l) << " = (float*)a.out[" << o << "].base + ((" << ringLane << sfx(l) << " >> 6) * a.T) * 64;\n";
         else if (g.outputGroup[o])
           s << "  f32x4* out" << o << sfx(l) << " = (f32x4*)a.out[" << o << "].base + (v" << sfx(l) << " / " << g.outputGroup[o] << ") * a.out[" << o << "].strideV;\n";
@@ -774,7 +799,7 @@ struct GraphEmitter
     for (size_t o = 0; o < g.outputs.size(); ++o)
       for (int l = 0; l < VL; ++l)
       {
-        if (g.outputGroup[o] && !ldsSum(o)) s << "        y" << o << sfx(l) << "[k] = group_sum_in_order<" << g.outputGroup[o] << ">(n" << g.outputs[o] << sfx(l) << ");\n";
+        if (g.outputGroup[o] && !ldsSum(o) && !segSum(o)) s << "        y" << o << sfx(l) << "[k] = group_sum_in_order<" << g.outputGroup[o] << ">(n" << g.outputs[o] << sfx(l) << ");\n";
         else s << "        y" << o << sfx(l) << "[k] = n" << g.outputs[o] << sfx(l) << ";\n";
       }
     // feedback: keep this sample's value for the same sample of the next DSPVector (its old value was read above)
@@ -795,11 +820,15 @@ struct GraphEmitter
         s << "      group16_park(strip" << o << ", q & 3, y" << o << "_0);\n      if ((q & 3) == 3) group16_sum_store(strip" << o << ", out" << o << "_0 + t * a.out[" << o
           << "].strideT + (q - 3) * a.out[" << o << "].strideQ, a.out[" << o << "].strideQ);\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
+      if (segSum(o))
+        s << "      segment_park(seg" << o << ", q & 3, y" << o << "_0);\n      if ((q & 3) == 3) segment_sum_store(seg" << o << ", rank_0, length_0, longest, out" << o
+          << "_0 + t * a.out[" << o << "].strideT + (q - 3) * a.out[" << o << "].strideQ, a.out[" << o << "].strideQ);\n";
+    for (size_t o = 0; o < g.outputs.size(); ++o)
       if (g.outputMix[o])
         s << "      mix64_park(mstrip" << o << ", q & 3, " << (partialWaves ? "(vr_0 < " + places + ") ? y" + std::to_string(o) + "_0 : f32x4{0.f, 0.f, 0.f, 0.f}" : "y" + std::to_string(o) + "_0")
           << ");\n      if ((q & 3) == 3) mix64_sum_store(mstrip" << o << ", out" << o << "_0 + t * 64 + (q - 3) * 4);\n";
     for (size_t o = 0; o < g.outputs.size(); ++o)
-      for (int l = 0; l < VL && !ldsSum(o) && !g.outputMix[o]; ++l)
+      for (int l = 0; l < VL && !ldsSum(o) && !segSum(o) && !g.outputMix[o]; ++l)
         s << "      " << (g.outputGroup[o] ? "if ((threadIdx.x & " + std::to_string(g.outputGroup[o] - 1) + ") == " + std::to_string(g.outputGroup[o] - 1) + ") " : std::string())
           << "__builtin_nontemporal_store(y" << o << sfx(l) << ", out" << o << sfx(l) << " + t * a.out[" << o << "].strideT + q * a.out[" << o << "].strideQ);\n";
     s << "    }\n";
@@ -819,7 +848,8 @@ struct GraphEmitter
     for (size_t i = 0; i < g.nodes.size(); ++i)
       if (g.nodes[i].type == NODE_PROC)
         for (int l = 0; l < VL; ++l) s << "  p" << i << sfx(l) << ".store(m" << i << sfx(l) << ");\n";
-    if (listed) s << "  if (a.peaks != nullptr && vr_0 < a.listed) a.peaks[vr_0] = pk_0;  // (a spare lane has no place in the list)\n";
+    if (planned) s << "  if (a.peaks != nullptr) a.peaks[pl_0] = pk_0;\n";
+    else if (listed) s << "  if (a.peaks != nullptr && vr_0 < a.listed) a.peaks[vr_0] = pk_0;  // (a spare lane has no place in the list)\n";
     s << "}\n";
   }
 };
@@ -933,13 +963,28 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   // by a block's neighbouring voices has no listed form
   if (g.voiceLists)
   {
-    const std::string who = "graph_compile: voice lists (mlgpu_graph_enable_voice_lists): ";
+    const std::string who = g.voiceListGroups ? "graph_compile: voice lists by a lane plan (mlgpu_graph_enable_voice_list_groups): " : "graph_compile: voice lists (mlgpu_graph_enable_voice_lists): ";
     if (p.rings != RingLayout::ROWS && p.totalRings)
       return fail(MLGPU_ERR_UNSUPPORTED, who + "delay layout " + std::to_string(apiLayout(p.rings)) + (g.delayLayout == 3 ? " (what layout 3 resolves to for this graph)" : "") +
                                              " keeps its rings in pieces made by the neighbouring voices of a 256-voice block; the rows are served: mlgpu_graph_set_delay_layout(g, 0)");
+    // the lane plan (mlgpu_graph_enable_voice_list_groups): instruments of ONE size, and no mixdown - the tree of a K-voice graph goes
+    // by list position in whole wavefronts, a lane plan has pads
+    int planGroup = 0;
+    for (size_t o = 0; g.voiceListGroups && o < g.outputs.size(); ++o)
+    {
+      if (g.outputGroup[o] && planGroup && g.outputGroup[o] != planGroup)
+        return fail(MLGPU_ERR_INVALID, who + "the outputs' group sums are of " + std::to_string(planGroup) + " and of " + std::to_string(g.outputGroup[o]) +
+                                           " voices; the lane plan lays out instruments of one size");
+      if (g.outputGroup[o]) planGroup = g.outputGroup[o];
+    }
+    if (g.voiceListGroups && !planGroup)
+      return fail(MLGPU_ERR_INVALID, who + "no output has a group sum (mlgpu_graph_set_output_group_sum); without one mlgpu_graph_enable_voice_lists serves the graph");
     for (size_t o = 0; o < g.outputs.size(); ++o)
     {
-      if (g.outputGroup[o]) return fail(MLGPU_ERR_UNSUPPORTED, who + "an output group sum (mlgpu_graph_set_output_group_sum) has no listed form");
+      if (g.voiceListGroups && g.outputMix[o])
+        return fail(MLGPU_ERR_UNSUPPORTED, who + "an output that is the mixdown of all voices (mlgpu_graph_set_output_mixdown) goes by list position in whole wavefronts, a lane plan has pads: no such form");
+      if (g.outputGroup[o] && !g.voiceListGroups)
+        return fail(MLGPU_ERR_UNSUPPORTED, who + "an output group sum (mlgpu_graph_set_output_group_sum) has no listed form without the lane plan: mlgpu_graph_enable_voice_list_groups(g, 1)");
       if (g.outputMixShard[o]) return fail(MLGPU_ERR_UNSUPPORTED, who + "the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2)) has no listed form");
     }
     if (g.hasEventRows) return fail(MLGPU_ERR_UNSUPPORTED, who + "event rows (mlgpu_graph_add_event_row) go by lane, not by voice: no listed form");
@@ -973,6 +1018,20 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
         slots += n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY ? 2 : 1;
       }
     }
+  }
+  // The lane plan's listed kernel has LDS of its own - the plan is one value for both kernels, so not in ldsOther: the impulse table
+  // and the early reads' landing slots as in the plain kernel, and per group-summed output the four wavefronts' segment strips and
+  // the tail behind them (16 KiB + 256 B) where the plain kernel has a 16-voice group's strip or none
+  if (g.voiceListGroups)
+  {
+    size_t sums = 0;
+    for (size_t o = 0; o < g.outputs.size(); ++o) sums += g.outputGroup[o] ? 1 : 0;
+    const size_t ldsTables = g.hasImpulse ? 128 : 0, ldsEarly = (size_t)p.earlySlots * 4 * 64 * sizeof(float);
+    const size_t ldsSegments = sums * sizeof(float) * (4 * (size_t)kHostSegmentStripFloats + (size_t)kHostSegmentTailFloats);
+    if (ldsTables + ldsEarly + ldsSegments > kLdsBytes)
+      return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: voice lists by a lane plan (mlgpu_graph_enable_voice_list_groups): " + kib(ldsSegments) + " of LDS for the segment strips of " +
+                                             std::to_string(sums) + " group-summed outputs (16 KiB + 256 B each) next to " + kib(ldsEarly) + " of early ring reads and " +
+                                             std::to_string(ldsTables) + " B of tables; a workgroup has 160 KiB");
   }
   planStreamLocks(g, p);
   planEarlyReads(g, p);

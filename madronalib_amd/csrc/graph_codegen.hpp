@@ -22,6 +22,7 @@ bool mlgpu_proc_is_vector_rate(int kind);  // one float per DSPVector in (Interp
 // shift of take_turns_by_clock, and the sizes of GraphArgs' signal lists
 constexpr int kHostMixStripFloats = 64 * 20 + 3 * 16 + 16;
 constexpr int kHostGroup16StripFloats = 4 * (4 * 80 + 4);
+constexpr int kHostSegmentStripFloats = 4 * 64 * 4, kHostSegmentTailFloats = 16 * 4;
 constexpr int kHostTurnClockShift = 13;
 constexpr int kHostGraphMaxInputs = 32, kHostGraphMaxOutputs = 8;
 
@@ -103,6 +104,7 @@ struct GraphDesc
   int voicesPerLane{0};          // 0 = choose at compile (graphVoicesPerLane); 1 or 2 = forced
   bool autotune{false};
   bool voiceLists{false};        // a compile makes the listed form of the kernel too (mlgpu_graph_enable_voice_lists)
+  bool voiceListGroups{false};   // ... and that form goes by the host's lane plan, its group-summed outputs one row per listed instrument (mlgpu_graph_enable_voice_list_groups)
 };
 
 // Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them by planGraph)
@@ -119,11 +121,14 @@ inline RingLayout ringLayoutOfApi(int layout) { return layout == 4 ? RingLayout:
 
 // A graph kernel's form besides the graph: voices per lane, quads per trip of the sample loop, and the wavefronts per SIMD its
 // register budget must allow (0: the compiler's choice; generateBudgeted). `listed`: the kernel of mlgpu_graph_process_listed - a
-// lane's place in the launch is its position in the voice list, its voice GraphArgs::voiceList's entry there (one voice per lane)
+// lane's place in the launch is its position in the voice list, its voice GraphArgs::voiceList's entry there (one voice per lane).
+// `planned` (with `listed`): the kernel of mlgpu_graph_process_listed_groups - a lane's voice, list position, output row and place in
+// its segment are its entry of GraphArgs::lanePlan (voice_list.hpp: mlvl::planGroups), a pad lane leaves before anything else
 struct KernelForm
 {
   int voicesPerLane{1}, quadsPerTrip{1}, minWaves{0};
   bool listed{false};
+  bool planned{false};
 };
 
 // Test hooks, not settings: the differential tests build a kernel's second form with these (environment variables, readTestHooks)

@@ -110,6 +110,11 @@ struct GraphArgs
   const uint32_t* voiceList;
   size_t listed;  // the list's length K
   uint32_t* peaks;
+  // the listed form by a lane plan (mlgpu_graph_process_listed_groups): the launch is `listed` = N lanes laid out by the host, lane l's
+  // entry the four words lanePlan[4 l .. 4 l + 3] of ChainArgs::lanePlan (voice or pad, list position, output row, rank | length << 8).
+  // Tables, rings, input rows and control columns are read at the voice, plain outputs and peaks written at the list position, a
+  // group-summed output at its row of a signal of J rows; voiceList is unused. Else unused.
+  const uint32_t* lanePlan;
 };
 
 // row `row` of the state memory at the voice whose byte offset in a row is lane4: the row's address is wave-uniform (scalar

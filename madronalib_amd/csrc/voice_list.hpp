@@ -17,7 +17,7 @@ namespace mlvl
 // The whole list is looked at before the answer: nothing is written anywhere but `err`. n == 0 is a valid, empty list.
 int validate(const uint32_t* list, size_t n, size_t nVoices, size_t reserved, char* err, size_t errLen);
 
-// ---- the lane plan of a listed group sum (mlgpu_bank_process_listed_groups; a graph's listed output group sum is to use it too) ----
+// ---- the lane plan of a listed group sum (mlgpu_bank_process_listed_groups, mlgpu_graph_process_listed_groups) ----
 // The bank's voices are instruments of G adjacent voices (G = 2, 4, 8, 16). The listed voices of one instrument - a SEGMENT, a
 // maximal run of equal list[i] / G - are consecutive list positions, and their in-order float sum must not cross a wavefront: a
 // segment that does not fit into what is left of the current 64 lanes starts at the next multiple of 64, the lanes in between are
