@@ -673,21 +673,25 @@ extern "C"
     if (const int st = checkEditable(g)) return st;
     if (index < 0 || index >= (int)g->desc.outputs.size()) return gfail(g, MLGPU_ERR_RANGE, "graph_set_output_mixdown: no such output");
     if (on && g->desc.outputGroup[index]) return gfail(g, MLGPU_ERR_INVALID, "graph_set_output_mixdown: the output is a group sum already");
-    if (on == 2 && mlgpu_mixdown_shard_level(g->desc.V) == 0)
+    if (on == 2 && mlmix::shardLevel(g->desc.V) == 0)
       return gfail(g, MLGPU_ERR_INVALID, "graph_set_output_mixdown: the shard form needs a voice count that is a multiple of 64 (whole first-stage groups of the tree)");
     g->desc.outputMix[index] = on != 0;
     g->desc.outputMixShard[index] = on == 2;
     return MLGPU_OK;
   }
-  // setup: the engine's mixdown scratch for this graph's mixed-down outputs, launches of up to maxVectors DSPVectors
+  static size_t mixedOutputs(const mlgpu_graph* g)
+  {
+    size_t n = 0;
+    for (size_t o = 0; o < g->desc.outputs.size(); ++o) n += g->desc.outputMix[o] ? 1 : 0;
+    return n;
+  }
+  // setup: the engine's mixdown scratch for this graph's mixed-down outputs - a region of the voices' tree each (mixdown_tree.hpp) -
+  // for launches of up to maxVectors DSPVectors
   int mlgpu_graph_reserve_mixdown(mlgpu_graph* g, size_t maxVectors)
   {
     if (!g) return MLGPU_ERR_INVALID;
     if (!g->e) return gfail(g, MLGPU_ERR_INVALID, "graph_reserve_mixdown: a graph without an engine");
-    size_t nMix = 0;
-    for (size_t o = 0; o < g->desc.outputs.size(); ++o) nMix += g->desc.outputMix[o] ? 1 : 0;
-    const size_t groups = (g->desc.V + 63) / 64;
-    const int st = mlgpu_mixdown_reserve_floats(g->e, nMix * (groups + (groups + 63) / 64) * maxVectors * 64);
+    const int st = mlgpu_mixdown_reserve_floats(g->e, mixedOutputs(g) * mlmix::regionFloats(g->desc.V, maxVectors));
     return st == MLGPU_OK ? st : gfail(g, st, "graph_reserve_mixdown: see the engine's last error");
   }
   int mlgpu_graph_node(mlgpu_graph* g, const char* name)
@@ -929,6 +933,50 @@ extern "C"
     if (err != hipSuccess) return gfail(g, err == hipErrorOutOfMemory ? MLGPU_ERR_OOM : MLGPU_ERR_HIP, std::string("graph_compile: ") + hipGetErrorString(err));
     g->compiled = true;
     return MLGPU_OK;
+  }
+
+  // Online tuning over those candidates: launches big enough to time take turns through the variants, 3 runs each with the first
+  // one discarded. The variant this launch tries, built here before its first run - or null: too small to time, or the tuning is settled.
+  static mlgpu_graph::Variant* tuningTrial(mlgpu_graph* g, size_t T)
+  {
+    if (!g->desc.autotune || g->tuned || g->desc.V * T * MLGPU_FLOATS_PER_DSPVECTOR < ((size_t)1 << 22)) return nullptr;
+    mlgpu_graph::Variant* trial = nullptr;
+    for (mlgpu_graph::Variant& v : g->variants)
+      if (!v.failed && v.runs < 3 && (!trial || v.runs < trial->runs)) trial = &v;
+    if (trial && !trial->fn)
+    {
+      std::string src, log;
+      std::vector<char> code;
+      if (generateBudgeted(g->desc, g->build->plan, KernelForm{trial->vl, trial->unroll, 0}, src, code, log)) trial->fn = mlgpu_jit_function(g->e->device, src, "mlgpu_graph_kernel", log);
+      if (!trial->fn) trial->failed = true;
+    }
+    if (trial && !trial->failed) return trial;
+    // keep the fastest; the default form stays unless another one is at least 3 % faster (two timed launches per form are a
+    // coarse measurement)
+    const auto score = [g](const mlgpu_graph::Variant& v) { return v.bestMs * ((v.fn == g->fn) ? 0.97f : 1.0f); };
+    const mlgpu_graph::Variant* best = nullptr;
+    for (const mlgpu_graph::Variant& v : g->variants)
+      if (!v.failed && v.fn && v.runs >= 2 && (!best || score(v) < score(*best))) best = &v;
+    if (best)
+    {
+      g->fn = best->fn;
+      g->activeForm = KernelForm{best->vl, best->unroll, 0};
+    }
+    g->tuned = true;
+    return nullptr;
+  }
+  // ... and the trial's time, taken between the graph's two events once the launch and what follows it are enqueued (waits for them)
+  static void tuningRecord(mlgpu_graph* g, mlgpu_graph::Variant* trial, size_t T)
+  {
+    hipEventRecord(g->tuneEv1.get(), g->e->stream());
+    float ms = 0.f;
+    if (hipEventSynchronize(g->tuneEv1.get()) != hipSuccess || hipEventElapsedTime(&ms, g->tuneEv0.get(), g->tuneEv1.get()) != hipSuccess)
+    {
+      trial->failed = true;
+      return;
+    }
+    if (trial->runs >= 1) trial->bestMs = std::min(trial->bestMs, ms / (float)T);
+    trial->runs++;
   }
 
   const char* mlgpu_graph_source(mlgpu_graph* g) { return (g && !g->job && g->build) ? g->build->source.c_str() : ""; }
@@ -1303,6 +1351,7 @@ extern "C"
     a.mem = g->d_mem.get();
     a.V = g->desc.V;
     a.T = T;
+    a.t0 = g->vectorCount;  // (advanced by the plain call only; no listed graph has a region that reads it)
     a.flags = g->e->kflags;
     a.impulseTable = g->e->d_impulseTable.get();
     for (int i = 0; i < g->desc.nInputs; ++i)
@@ -1319,6 +1368,48 @@ extern "C"
     for (size_t o = 0; o < g->desc.outputs.size(); ++o)
       if (!d_outputs[o] || ((uintptr_t)d_outputs[o] & 15)) return gfail(g, MLGPU_ERR_INVALID, w + ": null / misaligned output");
     return MLGPU_OK;
+  }
+
+  // The outputs of a call whose kernel writes `rows` rows per output - voices, or list positions - and `groupRows` for a group-summed
+  // one (0: rows / the output's group). A mixed-down output is the tree of the `rows` voices: the kernel writes its first stage into
+  // that output's region of the engine's mixdown scratch, mixdownStages follows the launch. MLGPU_OK, or the refusal `noScratch`.
+  static int outputViews(mlgpu_graph* g, GraphArgs& a, size_t T, float* const* d_outputs, int outLayout, size_t rows, size_t groupRows, const char* noScratch)
+  {
+    const size_t nMix = mixedOutputs(g);
+    for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
+    {
+      const size_t group = (size_t)g->desc.outputGroup[o];
+      if (!g->desc.outputMix[o]) a.out[o] = makeView(d_outputs[o], outLayout, !group ? rows : (groupRows ? groupRows : rows / group), T);
+      else if (rows)  // (no voices: no tree, nothing launched)
+      {
+        float* const region = g->e->mixdownRegion(rows, T, r++, nMix);
+        if (!region) return gfail(g, MLGPU_ERR_INVALID, noScratch);
+        a.out[o] = makeView(region, MLGPU_LAYOUT_QUAD, rows, T);
+      }
+    }
+    return MLGPU_OK;
+  }
+  // ... over the region outputViews gave it (the shard form is the plain call's alone: planGraph refuses it a listed form)
+  static int mixdownStages(mlgpu_graph* g, size_t T, float* const* d_outputs, size_t voices, const char* who)
+  {
+    const size_t nMix = mixedOutputs(g);
+    for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
+      if (g->desc.outputMix[o] &&
+          mlgpu_launch_mixdown_rows(mlmix::groupsOf(voices), T, g->e->mixdownRegion(voices, T, r++, nMix), d_outputs[o],
+                                    g->desc.outputMixShard[o] ? mlmix::shardLevel(voices) - 1 : mlmix::kToTheEnd, g->e->stream(), g->e->kflags) != hipSuccess)
+        return gfail(g, MLGPU_ERR_HIP, std::string(who) + ": the mixdown's later stages");
+    return MLGPU_OK;
+  }
+  // Event rows: the host half of the EventsToSignals block (routing the block's events into records, their upload) goes first, on
+  // the same stream; the kernel then walks the records itself. *staging: null without event rows, else what the launch is reported with.
+  static int prepareEvents(mlgpu_graph* g, size_t T, GraphArgs& a, void** staging)
+  {
+    if (!g->desc.hasEventRows) return MLGPU_OK;
+    if (!g->events) return gfail(g, MLGPU_ERR_INVALID, "graph_process: the graph has event rows but no events object (graph_bind_events)");
+    if (g->eventOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with event rows is run with mlgpu_graph_process_events");
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, &a.events, staging);
+    g->eventOffset = -1;
+    return est == MLGPU_OK ? est : gfail(g, est, "graph_process: the events object refused the block (see its last error)");
   }
 
   int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
@@ -1348,21 +1439,9 @@ extern "C"
     if (T == 0) return MLGPU_OK;
     GraphArgs a;
     if (const int st = signalArgs(g, a, "graph_process", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
-    a.t0 = g->vectorCount;
-    for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-      a.out[o] = makeView(d_outputs[o], outLayout, g->desc.outputGroup[o] ? g->desc.V / (size_t)g->desc.outputGroup[o] : g->desc.V, T);
-    // outputs that are mixdowns: the kernel writes the rows of 64-voice group sums into the engine's mixdown scratch (one region per
-    // such output), the later stages follow the launch
-    const size_t mixGroups = (g->desc.V + 63) / 64, mixRegion = (mixGroups + (mixGroups + 63) / 64) * T * 64;
-    size_t nMix = 0;
-    for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-      if (g->desc.outputMix[o])
-      {
-        a.out[o] = makeView(g->e->d_mixScratch.get() + nMix * mixRegion, MLGPU_LAYOUT_QUAD, g->desc.V, T);
-        ++nMix;
-      }
-    if (nMix * mixRegion > g->e->mixScratchFloats)
-      return gfail(g, MLGPU_ERR_INVALID, "graph_process: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (mlgpu_mixdown_reserve's scratch; process calls do not allocate)");
+    if (const int st = outputViews(g, a, T, d_outputs, outLayout, g->desc.V, 0,
+                                   "graph_process: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (mlgpu_mixdown_reserve's scratch; process calls do not allocate)"))
+      return st;
     if (g->e->recording)
     {
       if (g->desc.autotune && !g->tuned) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph that is still tuning cannot be recorded into a sequence");
@@ -1371,57 +1450,13 @@ extern "C"
           return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with a DOWNSAMPLE_2X region counts DSPVectors and cannot be recorded into a sequence");
     }
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
-    // online tuning: launches big enough to time take turns through the variants (3 runs each, the first one discarded)
-    mlgpu_graph::Variant* trial = nullptr;
-    if (g->desc.autotune && !g->tuned && g->desc.V * T * MLGPU_FLOATS_PER_DSPVECTOR >= ((size_t)1 << 22))
-    {
-      for (mlgpu_graph::Variant& v : g->variants)
-        if (!v.failed && v.runs < 3 && (!trial || v.runs < trial->runs)) trial = &v;
-      if (trial && !trial->fn)
-      {
-        std::string src, log;
-        std::vector<char> code;
-        if (generateBudgeted(g->desc, g->build->plan, KernelForm{trial->vl, trial->unroll, 0}, src, code, log)) trial->fn = mlgpu_jit_function(g->e->device, src, "mlgpu_graph_kernel", log);
-        if (!trial->fn)
-        {
-          trial->failed = true;
-          trial = nullptr;
-        }
-      }
-      if (!trial)
-      {
-        // every variant has its runs: keep the fastest; the default form stays unless another one is at least 3 % faster
-        // (two timed launches per form are a coarse measurement)
-        const mlgpu_graph::Variant* best = nullptr;
-        for (const mlgpu_graph::Variant& v : g->variants)
-        {
-          if (v.failed || !v.fn || v.runs < 2) continue;
-          const float handicap = (v.fn == g->fn) ? 0.97f : 1.0f;
-          if (!best || v.bestMs * handicap < best->bestMs * ((best->fn == g->fn) ? 0.97f : 1.0f)) best = &v;
-        }
-        if (best)
-        {
-          g->fn = best->fn;
-          g->activeForm = KernelForm{best->vl, best->unroll, 0};
-        }
-        g->tuned = true;
-      }
-    }
+    mlgpu_graph::Variant* const trial = tuningTrial(g, T);
     const hipFunction_t fn = trial ? trial->fn : g->fn;
     const int vl = trial ? trial->vl : g->activeForm.voicesPerLane;
     if (trial && !g->tuneEv0 && (allocate(g->tuneEv0) != hipSuccess || allocate(g->tuneEv1) != hipSuccess))
       return gfail(g, MLGPU_ERR_HIP, "graph_process: hipEventCreate");
-    // event rows: the host half of the EventsToSignals block (routing the block's events into records, their upload) goes first,
-    // on the same stream; the kernel then walks the records itself
     void* eventStaging = nullptr;
-    if (g->desc.hasEventRows)
-    {
-      if (!g->events) return gfail(g, MLGPU_ERR_INVALID, "graph_process: the graph has event rows but no events object (graph_bind_events)");
-      if (g->eventOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with event rows is run with mlgpu_graph_process_events");
-      const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, &a.events, &eventStaging);
-      g->eventOffset = -1;
-      if (est != MLGPU_OK) return gfail(g, est, "graph_process: the events object refused the block (see its last error)");
-    }
+    if (const int st = prepareEvents(g, T, a, &eventStaging)) return st;
     if (trial) hipEventRecord(g->tuneEv0.get(), g->e->stream());
     const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->desc.V + (size_t)vl - 1) / (size_t)vl, g->e->stream());
     if (err != hipSuccess)
@@ -1430,41 +1465,24 @@ extern "C"
       return gfail(g, MLGPU_ERR_HIP, std::string("graph_process launch: ") + hipGetErrorString(err));
     }
     if (eventStaging)
-    {
-      const int est = mlgpu_events_launched_by_graph(g->events, eventStaging);
-      if (est != MLGPU_OK) return gfail(g, est, "graph_process: events bookkeeping after the launch");
-    }
-    for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
-      if (g->desc.outputMix[o])
-      {
-        const hipError_t merr = g->desc.outputMixShard[o]
-                                    ? mlgpu_launch_mixdown_rows_partial(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], mlgpu_mixdown_shard_level(g->desc.V) - 1, g->e->stream(), g->e->kflags)
-                                    : mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream(), g->e->kflags);
-        if (merr != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "graph_process: the mixdown's later stages");
-        ++r;
-      }
-    if (trial)
-    {
-      hipEventRecord(g->tuneEv1.get(), g->e->stream());
-      float ms = 0.f;
-      if (hipEventSynchronize(g->tuneEv1.get()) == hipSuccess && hipEventElapsedTime(&ms, g->tuneEv0.get(), g->tuneEv1.get()) == hipSuccess)
-      {
-        if (trial->runs >= 1) trial->bestMs = std::min(trial->bestMs, ms / (float)T);
-        trial->runs++;
-      }
-      else
-        trial->failed = true;
-    }
+      if (const int est = mlgpu_events_launched_by_graph(g->events, eventStaging)) return gfail(g, est, "graph_process: events bookkeeping after the launch");
+    if (const int st = mixdownStages(g, T, d_outputs, g->desc.V, "graph_process")) return st;
+    if (trial) tuningRecord(g, trial, T);
     g->vectorCount += T;
     return MLGPU_OK;
   }
 
-  // ---- voice lists: run only the listed voices (mlgpu_voice_list keeps the list, the listed form of the generated kernel runs it) ----
-  static int listsReady(mlgpu_graph* g, const char* who)
+  // ---- voice lists: run only the listed voices (mlgpu_voice_list keeps the list, the listed form of the generated kernel runs it);
+  // `planned`: the call wants the listed form that goes by the host's lane plan (voice_list.hpp; the group-summed outputs summed by
+  // instrument), else any listed form ----
+  static int listsReady(mlgpu_graph* g, const char* who, bool planned = false)
   {
     if (!g) return MLGPU_ERR_INVALID;
     if (g->job) return MLGPU_ERR_BUSY;
-    if (!g->desc.voiceLists) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph has no listed form - mlgpu_graph_enable_voice_lists(g, 1) before compile");
+    if (!(planned ? g->desc.voiceListGroups : g->desc.voiceLists))
+      return gfail(g, MLGPU_ERR_INVALID,
+                   std::string(who) + (planned ? ": the graph's listed form does not go by a lane plan - mlgpu_graph_enable_voice_list_groups(g, 1) before compile"
+                                               : ": the graph has no listed form - mlgpu_graph_enable_voice_lists(g, 1) before compile"));
     if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": compile first");
     return MLGPU_OK;
   }
@@ -1493,20 +1511,13 @@ extern "C"
     GraphArgs a;
     if (const int st = signalArgs(g, a, "graph_process_listed", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     const size_t K = g->list.size;
-    a.t0 = g->vectorCount;  // (not advanced here; no listed graph has a region that reads it)
     a.voiceList = g->list.d_list.get();
     a.listed = K;
     a.peaks = d_peak;
-    // outputs by list position: K rows each; a mixed-down output is the tree of a K-voice graph, its first stage's rows in the scratch
-    const size_t mixGroups = (K + 63) / 64, mixRegion = (mixGroups + (mixGroups + 63) / 64) * T * 64;
-    size_t nMix = 0;
-    for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-    {
-      if (g->desc.outputMix[o]) a.out[o] = makeView(g->e->d_mixScratch.get() + nMix++ * mixRegion, MLGPU_LAYOUT_QUAD, K, T);
-      else a.out[o] = makeView(d_outputs[o], outLayout, K, T);
-    }
-    if (nMix * mixRegion > g->e->mixScratchFloats)
-      return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)");
+    // outputs by list position: K rows each; a mixed-down output is the tree of a K-voice graph
+    if (const int st = outputViews(g, a, T, d_outputs, outLayout, K, 0,
+                                   "graph_process_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)"))
+      return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
     if (K == 0)  // (nothing to launch; the sum of no voices: +0.0)
     {
@@ -1517,29 +1528,13 @@ extern "C"
     }
     const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream());
     if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed launch: ") + hipGetErrorString(err));
-    for (size_t o = 0, r = 0; o < g->desc.outputs.size(); ++o)
-      if (g->desc.outputMix[o])
-      {
-        if (mlgpu_launch_mixdown_rows(mixGroups, T, g->e->d_mixScratch.get() + r * mixRegion, d_outputs[o], g->e->stream(), g->e->kflags) != hipSuccess)
-          return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: the mixdown's later stages");
-        ++r;
-      }
-    return MLGPU_OK;
+    return mixdownStages(g, T, d_outputs, K, "graph_process_listed");
   }
 
   // ---- the listed voices with the group-summed outputs summed by instrument (voice_list.hpp plans the lanes, the planned form of the generated kernel runs them) ----
-  static int listGroupsReady(mlgpu_graph* g, const char* who)
-  {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (!g->desc.voiceListGroups)
-      return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph's listed form does not go by a lane plan - mlgpu_graph_enable_voice_list_groups(g, 1) before compile");
-    if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": compile first");
-    return MLGPU_OK;
-  }
   int mlgpu_graph_reserve_voice_list_groups(mlgpu_graph* g, size_t maxListed)
   {
-    if (const int st = listGroupsReady(g, "graph_reserve_voice_list_groups")) return st;
+    if (const int st = listsReady(g, "graph_reserve_voice_list_groups", true)) return st;
     int G = 0;  // (planGraph: every group-summed output has this size, and there is one)
     for (size_t o = 0; o < g->desc.outputs.size(); ++o) G = g->desc.outputGroup[o] ? g->desc.outputGroup[o] : G;
     const int st = g->list.reserve(g->e, maxListed, "graph_reserve_voice_list_groups", G);
@@ -1550,18 +1545,15 @@ extern "C"
   {
     if (!g) return MLGPU_ERR_INVALID;
     if (g->job) return MLGPU_ERR_BUSY;
-    const size_t J = g->list.planGroups;
-    if (J == 0) return MLGPU_OK;
-    if (!h_groups) return gfail(g, MLGPU_ERR_INVALID, "graph_listed_groups: null array");
-    if (capacity < J) return gfail(g, MLGPU_ERR_RANGE, "graph_listed_groups: the array is shorter than mlgpu_graph_listed_group_count");
-    memcpy(h_groups, g->list.groups.data(), sizeof(uint32_t) * J);
-    return MLGPU_OK;
+    std::string err;
+    const int st = g->list.copyGroups(h_groups, capacity, "graph", err);
+    return st == MLGPU_OK ? st : gfail(g, st, err);
   }
 
   int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
                                         int outLayout, uint32_t* d_peak)
   {
-    if (const int st = listGroupsReady(g, "graph_process_listed_groups")) return st;
+    if (const int st = listsReady(g, "graph_process_listed_groups", true)) return st;
     if (g->e->recording)
       return gfail(g, MLGPU_ERR_INVALID,
                    "graph_process_listed_groups: not while recording a sequence - the launch's lane count and its rows go with the list's contents, not "
@@ -1573,12 +1565,11 @@ extern "C"
     if (const int st = signalArgs(g, a, "graph_process_listed_groups", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     const size_t K = g->list.size, N = g->list.planLanes, J = g->list.planGroups;
     if (K == 0) return MLGPU_OK;  // (no listed instrument: no row to write)
-    a.t0 = g->vectorCount;  // (not advanced here; no listed graph has a region that reads it)
     a.listed = N;
     a.lanePlan = g->list.d_plan.get();
     a.peaks = d_peak;
-    // a group-summed output: J rows, one per listed instrument; every other output: K rows by list position
-    for (size_t o = 0; o < g->desc.outputs.size(); ++o) a.out[o] = makeView(d_outputs[o], outLayout, g->desc.outputGroup[o] ? J : K, T);
+    // a group-summed output: J rows, one per listed instrument; every other output: K rows by list position (none is mixed down: planGraph)
+    if (const int st = outputViews(g, a, T, d_outputs, outLayout, K, J, "")) return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
     const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream());
     if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed_groups launch: ") + hipGetErrorString(err));

@@ -12,6 +12,7 @@
 
 #include "../../include/mlgpu.h"
 #include "launch_parts.hpp"
+#include "mixdown_tree.hpp"
 #include "mlgpu_device_args.hpp"
 #include "param_updates.hpp"
 #include "staging_turns.hpp"
@@ -99,6 +100,14 @@ struct mlgpu_engine
   bool strictSvf{false};  // banks and graphs made from now on get kernels compiled with MLGPU_SVF_STRICT 1 (mlgpu_engine_set_strict_svf)
   DeviceBuffer<float> d_mixScratch;  // mixdown partial sums, grown on demand
   size_t mixScratchFloats{0};
+  // Region `r` of `n` regions for the mixdown tree of V voices over T DSPVectors (mixdown_tree.hpp), or null where the scratch does
+  // not hold the n: what a call hands its first stage before the launch and walks after it. The refusal's words are the caller's.
+  // (A tree of no voices needs no floats and fits a scratch never reserved, which is null too: callers with V == 0 do not ask.)
+  float* mixdownRegion(size_t V, size_t T, size_t r = 0, size_t n = 1) const
+  {
+    const size_t floats = mlmix::regionFloats(V, T);
+    return n * floats > mixScratchFloats ? nullptr : d_mixScratch.get() + r * floats;
+  }
   DeviceBuffer<unsigned long long> d_validate;  // {count, first index} of mlgpu_validate, allocated with the engine
   uint32_t kflags{0};  // MLGPU_KFLAG_* handed to every arithmetic kernel (mlgpu_engine_set_flush_denormals)
   bool recording{false};  // between mlgpu_engine_begin_recording and _end_recording: launches are captured, not run
@@ -293,8 +302,8 @@ hipError_t mlgpu_launch_rows_index(float* out, size_t rowsPerGroup, size_t group
 hipError_t mlgpu_launch_mixdown(const float* sig, int layout, size_t V, size_t T, const float* gains, float* partial, float* out,
                                 hipStream_t stream, uint32_t flags);
 int mlgpu_mixdown_reserve_floats(mlgpu_engine* e, size_t floats);  // capi.hip: the mixdown scratch grown to at least that
-hipError_t mlgpu_launch_mixdown_rows(size_t groups, size_t T, float* partial, float* out, hipStream_t stream, uint32_t flags);
-hipError_t mlgpu_launch_mixdown_rows_partial(size_t groups, size_t T, float* partial, float* out, int reductions, hipStream_t stream, uint32_t flags);
+// (reductions: mlmix::kToTheEnd, or the exact 64-to-1 passes of a shard's hand-over)
+hipError_t mlgpu_launch_mixdown_rows(size_t groups, size_t T, float* partial, float* out, int reductions, hipStream_t stream, uint32_t flags);
 hipError_t mlgpu_launch_mixdown_stage1(const float* sig, int layout, size_t V, size_t T, const float* gains, float* partial, hipStream_t stream, uint32_t flags);
 hipError_t mlgpu_launch_mixdown_groups(const float* sig, int layout, size_t groups, size_t P, size_t T, float* out, int outLayout, hipStream_t stream, uint32_t flags);
 hipError_t mlgpu_launch_route(bool demux, bool linear, const float* sel, size_t selElems, const float* const* ins, float* const* outs, int n,
@@ -367,6 +376,8 @@ struct mlgpu_voice_list
   // newOutGroup: -1 keeps the plan's group size (and resizes its buffers with the list's), 0 turns the plan off, 2 / 4 / 8 / 16 set it
   int reserve(mlgpu_engine* e, size_t maxListed, const char* who, int newOutGroup = -1);
   int set(mlgpu_engine* e, size_t nVoices, const uint32_t* h_voices, size_t n, const char* who);
+  // the listed instruments M[0 .. J) of the list in force into h_groups[capacity]: MLGPU_OK, or the refusal's status with `err` = who + ...
+  int copyGroups(uint32_t* h_groups, size_t capacity, const char* who, std::string& err) const;
 };
 
 // coeffs.cpp

@@ -907,67 +907,40 @@ hipError_t mlgpu_launch_mixdown_groups(const float* sig, int layout, size_t grou
 hipError_t mlgpu_launch_mixdown(const float* sig, int layout, size_t V, size_t T, const float* gains, float* partial, float* out,
                                 hipStream_t stream, uint32_t flags)
 {
-  const size_t groups = (V + 63) / 64;
+  const size_t groups = mlmix::groupsOf(V);
   hipLaunchKernelGGL(mixdown_stage1_kernel, dim3((unsigned)((groups * T + 3) / 4)), dim3(256), 0, stream, makeView(sig, layout, V, T), V, T, gains, partial, flags);
-  return mlgpu_launch_mixdown_rows(groups, T, partial, out, stream, flags);
+  return mlgpu_launch_mixdown_rows(groups, T, partial, out, mlmix::kToTheEnd, stream, flags);
 }
 
 hipError_t mlgpu_launch_mixdown_stage1(const float* sig, int layout, size_t V, size_t T, const float* gains, float* partial, hipStream_t stream, uint32_t flags)
 {
-  const size_t groups = (V + 63) / 64;
+  const size_t groups = mlmix::groupsOf(V);
   hipLaunchKernelGGL(mixdown_stage1_kernel, dim3((unsigned)((groups * T + 3) / 4)), dim3(256), 0, stream, makeView(sig, layout, V, T), V, T, gains, partial, flags);
   return hipGetLastError();
 }
 
-// the later stages alone: `partial` holds the rows of 64-voice group sums (the first stage's output, or a voice kernel's that made
-// them itself - chain_mix_kernel)
-hipError_t mlgpu_launch_mixdown_rows(size_t groups, size_t T, float* partial, float* out, hipStream_t stream, uint32_t flags)
+// The later stages: `partial` is a tree's scratch region (mixdown_tree.hpp) whose first part holds the rows of 64-voice group sums -
+// the first stage's output, or a voice kernel's that made them itself (chain_mix_kernel). reductions == mlmix::kToTheEnd: down to
+// the one row in `out`. reductions == n: n passes of 64 rows -> 1 (each exact: the caller guarantees groups is a multiple of
+// 64^n), the last one into `out` - what one SHARD of a voice bank hands to the host, which finishes the same tree over the shards'
+// rows (mlgpu_mixdown_finish); 0: the group sums themselves.
+hipError_t mlgpu_launch_mixdown_rows(size_t groups, size_t T, float* partial, float* out, int reductions, hipStream_t stream, uint32_t flags)
 {
   const size_t nQuads = T * 16;
-  // the rows of group sums (in `partial`), 64 at a time, until one is left; the passes alternate between the two parts of the
-  // scratch (mlgpu_mixdown_reserve: the second holds the first pass's rows / 64), the last one writes `out`
-  float4* a = (float4*)partial;
-  float4* b = a + groups * nQuads;
-  size_t rows = groups;
-  do
-  {
-    if (rows <= 4096)
+  float4* const part[3] = {(float4*)partial, (float4*)(partial + mlmix::secondPartFloats(groups, T)), (float4*)out};
+  for (const mlmix::Pass& p : mlmix::passes(groups, reductions))
+    switch (p.kernel)
     {
-      hipLaunchKernelGGL(mixdown_rows_last2_kernel, dim3((unsigned)((nQuads + 15) / 16)), dim3(16, (unsigned)((rows + 63) / 64)), 0, stream, (const float4*)a, rows,
-                         nQuads, (float4*)out, flags);
-      break;
+      case mlmix::kCopy: return hipMemcpyAsync(out, partial, sizeof(float4) * p.rowsIn * nQuads, hipMemcpyDeviceToDevice, stream);
+      case mlmix::kLast2:
+        hipLaunchKernelGGL(mixdown_rows_last2_kernel, dim3((unsigned)((nQuads + 15) / 16)), dim3(16, (unsigned)((p.rowsIn + 63) / 64)), 0, stream,
+                           (const float4*)part[p.from], p.rowsIn, nQuads, part[p.to], flags);
+        break;
+      case mlmix::kRows64:
+        hipLaunchKernelGGL(mixdown_rows64_kernel, dim3((unsigned)((nQuads + 63) / 64), (unsigned)p.rowsOut), dim3(64), 0, stream, (const float4*)part[p.from],
+                           p.rowsIn, nQuads, part[p.to], flags);
+        break;
     }
-    const size_t rowsOut = (rows + 63) / 64;
-    hipLaunchKernelGGL(mixdown_rows64_kernel, dim3((unsigned)((nQuads + 63) / 64), (unsigned)rowsOut), dim3(64), 0, stream, (const float4*)a, rows, nQuads,
-                       rowsOut == 1 ? (float4*)out : b, flags);
-    float4* t = a;
-    a = b;
-    b = t;
-    rows = rowsOut;
-  } while (rows > 1);
-  return hipGetLastError();
-}
-
-// The later stages up to a level: `reductions` passes of 64 rows -> 1 (each exact: the caller guarantees groups is a multiple of
-// 64^reductions), the last one into `out` - what one SHARD of a voice bank hands to the host, which finishes the same tree over the
-// shards' rows (mlgpu_mixdown_finish). reductions == 0: the group sums themselves.
-hipError_t mlgpu_launch_mixdown_rows_partial(size_t groups, size_t T, float* partial, float* out, int reductions, hipStream_t stream, uint32_t flags)
-{
-  const size_t nQuads = T * 16;
-  float4* a = (float4*)partial;
-  float4* b = a + groups * nQuads;
-  size_t rows = groups;
-  if (reductions == 0) return hipMemcpyAsync(out, partial, sizeof(float4) * groups * nQuads, hipMemcpyDeviceToDevice, stream);
-  for (int r = 0; r < reductions; ++r)
-  {
-    const size_t rowsOut = (rows + 63) / 64;
-    hipLaunchKernelGGL(mixdown_rows64_kernel, dim3((unsigned)((nQuads + 63) / 64), (unsigned)rowsOut), dim3(64), 0, stream, (const float4*)a, rows, nQuads,
-                       r + 1 == reductions ? (float4*)out : b, flags);
-    float4* t = a;
-    a = b;
-    b = t;
-    rows = rowsOut;
-  }
   return hipGetLastError();
 }
 

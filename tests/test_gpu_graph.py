@@ -1193,6 +1193,61 @@ def test_graph_output_mixdown_next_to_a_plain_output_and_delay_rings(eng):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("V,listed", [(777, False), (262144 + 4096 + 77, False), (777, True)])
+def test_graph_two_mixdown_outputs_share_the_scratch(eng, V, listed):
+    """Two mixed-down outputs of one graph, x + x and x * x, next to a plain one: each has its own region of the engine's mixdown
+    scratch, assigned before the launch and walked after it. 777 voices: 13 groups, a ragged last wavefront; 262144 + 4096 + 77:
+    4162 groups, where a region's second part is written too (4162 + 66 rows a region). Each mixed output equals, bit for bit,
+    mlgpu_mixdown of that output of the same graph built without the mixdown; the plain output is untouched. listed: the same through
+    mlgpu_graph_process_listed with every third voice listed - K = 259, five groups with the last one ragged - against mlgpu_mixdown
+    of the listed voices' rows."""
+    import madronalib_amd as ml
+    T = 2
+    L = np.arange(0, V, 3, dtype=np.uint32)
+    x = lcg_noise(np.arange(V, dtype=np.uint32) + 11, 64 * T)
+    d_x = eng.to_device(x)
+
+    def run(mixed):
+        g = ml.Graph(eng, V, voice_lists=listed)
+        g.add("x", "input")
+        g.add("sum", "op", Op.ADD, ["x", "x"])
+        g.add("sq", "op", Op.MULTIPLY, ["x", "x"])
+        for name in ("sum", "sq", "x"):
+            g.add_output(name)
+        if mixed:
+            g.set_output_mixdown(0)
+            g.set_output_mixdown(1)
+        g.compile()
+        if mixed:
+            g.reserve_mixdown(T)
+        rows = L.size if (listed and mixed) else V
+        d_out = [eng.alloc(4 * (1 if (mixed and o < 2) else rows) * T * 64) for o in range(3)]
+        if listed and mixed:
+            g.set_voice_list(L)
+            g.process_listed(T, [d_x], d_out, Layout.VOICE_MAJOR, Layout.VOICE_MAJOR)
+        else:
+            g.process(T, [d_x], d_out, Layout.VOICE_MAJOR, Layout.VOICE_MAJOR)
+        got = [b.download(np.float32).copy() for b in d_out]
+        g.close()
+        return got
+
+    voices = [o.reshape(V, 64 * T) for o in run(False)]
+    mixed = run(True)
+    K = L.size if listed else V
+    eng.mixdown_reserve(K, T)
+    d_m = eng.alloc(4 * 64 * T)
+    for o, name in enumerate(("x + x", "x * x")):
+        rows = np.ascontiguousarray(voices[o][L] if listed else voices[o])
+        eng.mixdown(eng.to_device(rows), Layout.VOICE_MAJOR, K, T, d_m)
+        want = d_m.download(np.float32, 64 * T)
+        assert np.isfinite(want).all() and np.abs(want).max() > 0.1, name
+        assert_bits_equal(mixed[o], want, True, f"mixed output {name}")
+    assert not np.array_equal(mixed[0], mixed[1])
+    assert_bits_equal(mixed[2].reshape(K, 64 * T), voices[2][L] if listed else voices[2], True, "the plain output")
+    assert_bits_equal(voices[2], x, True, "the plain output is the input")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("V", [256, 777])
 def test_early_ring_reads_next_to_a_mixdown_output(eng, V):
     """Ring layout 0 with the reads of a sample issued together (graph.hip: earlyRows - LDS landing slots per wavefront) in one kernel
