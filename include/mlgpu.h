@@ -291,19 +291,23 @@ int mlgpu_engine_get_cascade_lanes(mlgpu_engine* e);
  * slots that finish early stay empty until the whole launch has retired and the next is dispatched. A bank's voices are independent,
  * and consecutive mlgpu_bank_process calls on one bank depend on each other only through each voice's own state. So such a call may
  * go out as two kernels, one per contiguous part of the voices: the first on the engine's stream, the second on a side stream the
- * engine owns. Each part is serial on its own stream and overlaps the other part's launch boundary. Results are bit-identical.
+ * engine owns. Each part is serial on its own stream and overlaps the other part's launch boundary. Each stream's part may be cut
+ * once more, into two kernels one after the other on that stream (four kernels a call, issued main, side, main, side): the chip then
+ * holds smaller kernels, which cost less per voice, whether or not the streams run in step. Results are bit-identical.
  * The streams meet again lazily: the next call on the engine goes ahead without a join only if it is another such launch of the
  * same bank whose output is exactly a pending one (same address, layout and DSPVectors) or apart from every pending one. Before
  * anything else - another bank or form, any op, graph, events, resample or update launch, a copy, sync, timer, fence, free,
  * destroy, or recording a sequence - the engine's stream first waits for the side stream, so stream order is what it always was.
- *   parts = 0 (the default): in two parts where each part still puts a workgroup on every CU of the device;
+ *   parts = 0 (the default): in two parts where each part still puts a workgroup on every CU of the device, and each of them in two
+ *     again where that still holds of every kernel and each works on at least 2^26 voice-samples (65 536 voices x 16 DSPVectors);
  *   parts = 1: always one launch;
- *   parts = 2: two parts whenever the form allows and the bank is more than 2048 voices (for tests).
+ *   parts = 2: two parts, one per stream, whenever the form allows and the bank is more than 2048 voices (for tests);
+ *   parts = 3: as 2, and each stream's part in two again whenever it is more than 2048 voices (for tests).
  * The form allows it for mlgpu_bank_process of a fused chain kernel, ahead-of-time or generated (not an SVF cascade, not a bank that
  * runs processor by processor), on a launch-constant input; never for the mixdown, group and listed calls, a streamed input, while
  * recording a sequence, on an engine made on a caller's stream (mlgpu_engine_create_on_stream), or once mlgpu_engine_stream has
  * handed the engine's stream to the caller (mlgpu_engine_launch_parts_possible says which of the last two holds).
- * mlgpu_engine_launch_stats: how many launches went out in two parts and how often the streams met, since the engine was made. */
+ * mlgpu_engine_launch_stats: how many launches (calls, not kernels) went out in parts and how often the streams met, since the engine was made. */
 int mlgpu_engine_set_launch_parts(mlgpu_engine* e, int parts);
 int mlgpu_engine_get_launch_parts(mlgpu_engine* e);
 /* 1 while this engine may still launch in parts at all, 0 once it cannot whatever `parts` says: it was made on a caller's stream, or

@@ -248,7 +248,8 @@ class Engine(_Handle):
 
     def set_launch_parts(self, parts):
         """How a plain launch of a large bank goes out (mlgpu_engine_set_launch_parts): 0 = in two parts on two streams where the bank
-        is large enough (the default), 1 = always one launch, 2 = two parts whenever the form allows (tests). Same bits either way."""
+        is large enough, each in two again where it is larger still and the launch long enough (the default), 1 = always one launch,
+        2 = two parts whenever the form allows, 3 = and each of them in two again (tests). Same bits either way."""
         self._check(self.L.mlgpu_engine_set_launch_parts(self.h, int(parts)))
 
     def get_launch_parts(self):
@@ -259,7 +260,7 @@ class Engine(_Handle):
         return bool(self.L.mlgpu_engine_launch_parts_possible(self.h))
 
     def launch_stats(self):
-        """(launches that went out in two parts, times the two streams met again) since the engine was made."""
+        """(calls that went out in parts, times the two streams met again) since the engine was made."""
         split, joins = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.L.mlgpu_engine_launch_stats(self.h, ctypes.byref(split), ctypes.byref(joins)))
         return split.value, joins.value

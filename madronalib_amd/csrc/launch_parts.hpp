@@ -1,11 +1,12 @@
-// launch_parts.hpp — the HOST bookkeeping of a bank launch that goes out in two parts ("Launch parts"): where a
-// bank's voices are cut, and what the engine remembers of the part that runs on its side stream until the two streams meet again.
+// launch_parts.hpp — the HOST bookkeeping of a bank launch that goes out in parts ("Launch parts"): where a
+// bank's voices are cut, and what the engine remembers of the parts that run on its side stream until the two streams meet again.
 // Plain C++ that never touches a device: built and tested without any HIP header; capi.hip is the caller.
 //
 // A plain launch of a bank's V voices may go out as two kernels, voices [0, v0) on the engine's stream and [v0, V) on a side stream.
 // Consecutive launches of the bank depend on each other only through each voice's own state, so each part is serial on its own
 // stream and the parts need not meet while the host keeps making such launches of the same bank. The engine JOINS the streams
-// lazily: before anything else it enqueues. What decides "anything else" is here.
+// lazily: before anything else it enqueues. What decides "anything else" is here. Each stream's window of voices may be cut once
+// more (splitPlan): up to four kernels, two per stream, which write between them exactly the addresses the two wrote.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -16,18 +17,40 @@ namespace mlparts
 // count is a multiple of 8 keeps that remap whole. 8 workgroups of 256 lanes:
 constexpr size_t kSplitUnit = 8 * 256;
 constexpr size_t kMaxPendingOutputs = 8;
+constexpr int kMaxParts = 4;
+// More than two kernels per launch only where the smallest of them still works on this many voice-samples (automatic mode). From the
+// two shapes measured (profiles/bank_launch_plan.md): quarters of 65 536 voices x 30 DSPVectors (2^26.9 voice-samples each) ran 7 %
+// faster than halves, quarters of 262 144 voices x 1 DSPVector (2^24) 13 % slower; nothing in between was measured, so the threshold
+// is the power of two next to the shape that gained.
+constexpr size_t kMinSamplesPerQuarter = (size_t)1 << 26;
 
 // mlgpu_engine_set_launch_parts
 enum Mode
 {
-  kAuto = 0,   // two parts when each still puts a workgroup on every CU
+  kAuto = 0,   // by size: two parts, or four, when each still puts a workgroup on every CU (four: and has kMinSamplesPerQuarter)
   kNever = 1,  // one launch, always
-  kHalves = 2  // two parts whenever there is a second part to make (tests)
+  kHalves = 2,   // two parts whenever there is a second part to make (tests)
+  kQuarters = 3  // ... and each stream's part cut once more whenever it has a second unit, sizes notwithstanding (tests)
 };
+inline bool validMode(int mode) { return mode >= kAuto && mode <= kQuarters; }
 
 // Where a launch of V voices is cut: v0, a multiple of kSplitUnit with 0 < v0 < V, or 0 for "one launch".
 // The first part is the whole units of V / 2 (at least one), the second part the rest, ragged or not.
+// (kQuarters cuts the streams where kHalves does.)
 size_t splitPoint(size_t V, int mode, size_t cuCount, size_t lanesPerWorkgroup);
+
+// The kernels of one launch of V voices over T DSPVectors: part i is voices [cut[i], cut[i + 1]); parts [0, firstSide) go on the
+// engine's stream, parts [firstSide, n) on the side stream. n == 1 (firstSide == 1) is one launch. The boundary between the streams,
+// cut[firstSide], is splitPoint(V, mode, ...), whatever else the plan does: the side stream writes what it writes in two parts. A
+// stream's window is cut once more at the whole units of half its size (at least one) if it has more than one unit and, in the
+// automatic mode, if each resulting kernel still has a workgroup for every CU and kMinSamplesPerQuarter voice-samples to work on.
+struct Plan
+{
+  size_t cut[kMaxParts + 1];
+  int n;
+  int firstSide;
+};
+Plan splitPlan(size_t V, size_t T, int mode, size_t cuCount, size_t lanesPerWorkgroup);
 
 // An output signal a pending launch writes: [base, base + bytes) in some layout over T DSPVectors. Two launches of the same bank
 // with the same base, layout and T write, part by part, exactly the same addresses.

@@ -9,13 +9,20 @@
   (d) (--product) the V-voice bank on an engine whose launch parts are left at their default: the library's own two-part launch.
 Every other engine here is set to one launch per call (Engine.set_launch_parts(1)), so (a), (b) and (c) are what they say; against a
 library from before launch parts existed - the decision run of step 0 - there is nothing to set and (d) is not to be had.
+  (--plan) three routes that cut the voices once more, into kernels of one wavefront per SIMD at config 3's size:
+  (e) four V/4-voice banks on ONE engine, launched in turn: what a quarter-size launch costs by itself;
+  (f) four V/4-voice banks on TWO engines, quarters 0 and 1 on the first and 2 and 3 on the second, issued q0, q2, q1, q3;
+  (g) two V/4-voice banks on the first engine and one V/2-voice bank on the second, issued q0, half, q1: the first stream's kernel
+      boundary falls in the middle of the second stream's kernel even when the streams start together.
 The modes alternate ROUNDS times; each run is STEPS steps after WARMUP untimed ones, host wall clock from a sync of every engine to
 the next sync of every engine. One JSON line per run on stdout; the verdict of the decision rule (every (b) below every (a) and the gap
-between the ranges wider than (a)'s own range) on the last line.
+between the ranges wider than (a)'s own range) on the last line, and with it the same rule for (f) and (g) against (d): a four-kernel
+plan is built only if every run of it lies below every run of (d) by at least (d)'s own range.
 
-  python tools/launch_parts_probe.py [--voices V] [--vectors T] [--launches L] [--steps N] [--warmup W] [--rounds R] [--serial] [--product] [--only a|b|c|d] [--raw FILE]
+  python tools/launch_parts_probe.py [--voices V] [--vectors T] [--launches L] [--steps N] [--warmup W] [--rounds R] [--serial] [--product] [--plan] [--only a|b|c|d|e|f|g]
+                                      [--raw FILE]
 
-`--only b --rounds 1` is the shape to run under `rocprofv3 --kernel-trace` (a run of its own, no counters): the trace shows whether the
+`--only b --rounds 1` (or f, or g) is the shape to run under `rocprofv3 --kernel-trace` (a run of its own, no counters): the trace shows whether the
 two halves' kernels overlap in time."""
 import argparse
 import json
@@ -37,13 +44,14 @@ ap.add_argument("--launches", type=int, default=25)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--only", choices=["a", "b", "c", "d"])
+ap.add_argument("--only", choices=["a", "b", "c", "d", "e", "f", "g"])
 ap.add_argument("--serial", action="store_true", help="also run (c)")
 ap.add_argument("--product", action="store_true", help="also run (d)")
+ap.add_argument("--plan", action="store_true", help="also run (e), (f) and (g)")
 ap.add_argument("--raw", help="append the JSON lines to this file as well")
 args = ap.parse_args()
 V, T, L = args.voices, args.vectors, args.launches
-assert V % 2 == 0
+assert V % 4 == 0
 
 
 def bank_of(eng, lo, hi):
@@ -75,6 +83,16 @@ if args.product or args.only == "d":
     assert HAS_PARTS, "(d) needs a library with mlgpu_engine_set_launch_parts"
     engines["d"] = [ml.Engine(0)]
     banks["d"] = [bank_of(engines["d"][0], 0, V)]
+Q = V // 4
+if args.plan or args.only == "e":
+    engines["e"] = [engA]
+    banks["e"] = [bank_of(engA, q * Q, (q + 1) * Q) for q in range(4)]
+if args.plan or args.only == "f":
+    e0, e1 = engines["f"] = engines["b"]
+    banks["f"] = [bank_of(e, q * Q, (q + 1) * Q) for e, q in ((e0, 0), (e1, 2), (e0, 1), (e1, 3))]
+if args.plan or args.only == "g":
+    e0, e1 = engines["g"] = engines["b"]
+    banks["g"] = [bank_of(e0, 0, Q), bank_of(e1, V // 2, V), bank_of(e0, Q, 2 * Q)]
 count = {m: 0 for m in banks}
 
 
@@ -112,7 +130,7 @@ for r in range(args.rounds):
             continue
         ms = run(mode)
         results[mode].append(ms)
-        line = json.dumps({"round": r, "mode": mode, "banks": len(banks[mode]), "voices_per_bank": V // len(banks[mode]), "vectors": T,
+        line = json.dumps({"round": r, "mode": mode, "banks": len(banks[mode]), "voices_per_bank": [b.V for b, _ in banks[mode]], "vectors": T,
                            "launches_per_step": L, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
                            "us_per_launch": ms * 1e3 / L, "device": name})
         print(line, flush=True)
@@ -126,9 +144,16 @@ if results["a"] and results["b"]:
     verdict = {"a_ms": [min(a), float(np.median(a)), max(a)], "b_ms": [min(b), float(np.median(b)), max(b)],
                "gap_between_ranges_ms": gap, "a_range_ms": spread, "b_over_a_median": float(np.median(b) / np.median(a)),
                "build_the_rest": bool(gap > 0 and gap > spread)}
-    for m in ("c", "d"):
+    for m in ("c", "d", "e", "f", "g"):
         if results.get(m):
             verdict[m + "_ms"] = [min(results[m]), float(np.median(results[m])), max(results[m])]
+    d = results.get("d")
+    for m in ("f", "g"):
+        if d and results.get(m):
+            gap_d, spread_d = min(d) - max(results[m]), max(d) - min(d)
+            verdict[m + "_against_d"] = {"gap_between_ranges_ms": gap_d, "d_range_ms": spread_d,
+                                         "median_over_d": float(np.median(results[m]) / np.median(d)),
+                                         "build_it": bool(gap_d > 0 and gap_d >= spread_d)}
     line = json.dumps({"verdict": verdict})
     print(line, flush=True)
     if raw:

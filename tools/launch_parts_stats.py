@@ -3,7 +3,7 @@ launch parts at --parts (default 0: by size), runs two steps of its launches and
 times the streams met) - for the launches and, apart, for the set-up; then the same for the real-time case (bench.py's rt_case), whose
 free-running leg of plain process calls comes before its paced blocks. One JSON line per workload.
 
-  python tools/launch_parts_stats.py [--parts 0|1|2]"""
+  python tools/launch_parts_stats.py [--parts 0|1|2|3]"""
 import json
 import os
 import sys
