@@ -1314,6 +1314,36 @@ int mlgpu_mixdown_finish(const float* h_rows, size_t n_rows, size_t n_vectors, i
  * kernel), after which mlgpu_bank_process_mixdown serves it too - any chain of bank processors, fused or not. MLGPU_OK at once where the
  * form is there already. */
 int mlgpu_bank_prepare_mixdown(mlgpu_bank* bank);
+/* The voices' sum once per CHANNEL - a stereo bus with a pan per voice (Synth::processVector accumulates into every row of `outputs`,
+ * source/app/MLSynth.h:43-57). d_gains [n_channels][voices] (channel-major, REQUIRED; the channel stride is the bank's voice count, so
+ * the listed form finds a gain by voice index, as mlgpu_bank_process_listed_mixdown does); d_out [n_channels][64 * n_vectors],
+ * channel-major. The voices advance ONCE; state and coefficients afterwards are those after one one-channel call.
+ * Bits: channel c is exactly what mlgpu_bank_process_mixdown(bank, n_vectors, d_in, in_layout, d_gains + c * voices, out_c) gives from
+ *   the same starting state - one float multiply y * g_c per sample and channel, the same 64-voice tree and later stages, spare lanes
+ *   of a last wavefront as +0, the engine's flush-denormals mode applied. d_peak of the listed form is taken before any gain; with an
+ *   empty list every channel is +0.0.
+ * n_channels == 1 is the one-channel call, unchanged (d_gains may then be NULL). n_channels == 2 runs the two-channel form of the
+ *   fused voice chains' kernel (chain_mix_channels_kernel: one LDS strip per channel and wavefront; the voices' signals never reach
+ *   memory). Any other count: MLGPU_ERR_UNSUPPORTED.
+ * mlgpu_mixdown_reserve_channels: the scratch for max_channels trees, once, at setup (a channels call needs n_channels regions of
+ *   its (voices, vectors): MLGPU_ERR_INVALID without; mlgpu_mixdown_reserve(.., ..) is the same as max_channels = 1).
+ * mlgpu_mixdown_channels: the same for a signal in memory - n_channels passes of mlgpu_mixdown, one per channel, each reading the
+ *   signal again. It is the comparator of the bank calls and the route for banks without them, NOT a hot path.
+ * _channels_shard: d_rows [n_channels][mlgpu_mixdown_shard_rows(voices)][64 * n_vectors]; the host finishes each channel's rows
+ *   with mlgpu_mixdown_finish, as after mlgpu_bank_process_mixdown_shard.
+ * Errors, in this order: MLGPU_ERR_UNSUPPORTED for n_channels other than 1 or 2; MLGPU_ERR_INVALID for null gains, a null output, a
+ *   bad layout, signals not 16-byte or gains / peaks not 4-byte aligned; MLGPU_ERR_UNSUPPORTED for a bank without the ahead-of-time
+ *   summing form (an SVF cascade, a bank served only through mlgpu_bank_prepare_mixdown: use mlgpu_bank_process, then
+ *   mlgpu_mixdown_channels); MLGPU_ERR_INVALID for a reservation that is too small. Recorded into a sequence like the one-channel calls. */
+int mlgpu_mixdown_reserve_channels(mlgpu_engine* e, size_t max_voices, size_t max_vectors, int max_channels);
+int mlgpu_mixdown_channels(mlgpu_engine* e, const float* d_signal, int layout, size_t n_voices, size_t n_vectors, int n_channels,
+                           const float* d_gains, float* d_out);
+int mlgpu_bank_process_mixdown_channels(mlgpu_bank* bank, size_t n_vectors, const float* d_in, int in_layout, int n_channels,
+                                        const float* d_gains, float* d_out);
+int mlgpu_bank_process_mixdown_channels_shard(mlgpu_bank* bank, size_t n_vectors, const float* d_in, int in_layout, int n_channels,
+                                              const float* d_gains, float* d_rows);
+int mlgpu_bank_process_listed_mixdown_channels(mlgpu_bank* bank, size_t n_vectors, const float* d_in, int in_layout, int n_channels,
+                                               const float* d_gains, float* d_out, uint32_t* d_peak);
 
 /* Sum every `group_size` consecutive voices into one: out voice g = ((0 + v[g*P]) + v[g*P+1]) + ... in voice order — the
  * `outputs[c] += ...` accumulation of Synth::processVector (source/app/MLSynth.h:43-57), bit for bit. The result is a signal

@@ -642,6 +642,27 @@ class VoiceBank
     eng_.check(mlgpu_bank_process_mixdown_shard(b_, vectors, nullptr, MLGPU_LAYOUT_QUAD, gains, rows));
   }
 
+  // ... and once per CHANNEL - a stereo bus, a pan per voice (mlgpu_bank_process_mixdown_channels; mlgpu_mixdown_reserve_channels at
+  // setup): gains [channels][voices] on the device, required; mix [channels][64 * vectors]. The voices advance once; channel c has
+  // the bits of mixdown(vectors, mix_c, gains + c * voices). Two channels (one: mixdown itself).
+  void mixdownChannels(size_t vectors, int channels, const float* gains, float* mix)
+  {
+    commit();
+    eng_.check(mlgpu_bank_process_mixdown_channels(b_, vectors, nullptr, MLGPU_LAYOUT_QUAD, channels, gains, mix));
+  }
+  void mixdownChannels(const DeviceSignal& in, int channels, const float* gains, float* mix)
+  {
+    if (in.voices() != voices_) throw Error(MLGPU_ERR_INVALID, "VoiceBank: signal shape mismatch");
+    commit();
+    eng_.check(mlgpu_bank_process_mixdown_channels(b_, in.vectors(), in.data(), in.layout(), channels, gains, mix));
+  }
+  // (rows [channels][mlgpu_mixdown_shard_rows(voices)][64 * vectors]: each channel's rows go to mlgpu_mixdown_finish)
+  void mixdownChannelsShard(size_t vectors, int channels, const float* gains, float* rows)
+  {
+    commit();
+    eng_.check(mlgpu_bank_process_mixdown_channels_shard(b_, vectors, nullptr, MLGPU_LAYOUT_QUAD, channels, gains, rows));
+  }
+
   // ... and when the voices belong together in groups of adjacent voices (mlgpu_bank_process_groups; groups of 1, 2, 4, 8, 16):
   // `in` (or nullptr: the per-voice constant input, inGroup 1) has one row per inGroup voices - a filter bank's shared excitation -
   // and `out` one channel per outGroup voices, their sum in voice order (Synth::processVector's `outputs += voice` per instrument,

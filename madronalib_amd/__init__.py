@@ -406,6 +406,17 @@ class Engine(_Handle):
         g = lambda x: None if x is None else ctypes.c_void_p(x.ptr if hasattr(x, "ptr") else int(x))  # noqa: E731
         self._check(self.L.mlgpu_mixdown(self.h, g(d_signal), int(layout), int(n_voices), int(n_vectors), g(d_gains), g(d_out)))
 
+    def mixdown_reserve_channels(self, max_voices, max_vectors, max_channels):
+        """Scratch for max_channels mixdown trees - what the *_channels calls need: once, at setup (mlgpu_mixdown_reserve_channels)."""
+        self._check(self.L.mlgpu_mixdown_reserve_channels(self.h, int(max_voices), int(max_vectors), int(max_channels)))
+
+    def mixdown_channels(self, d_signal, layout, n_voices, n_vectors, n_channels, d_gains, d_out):
+        """mixdown once per channel: d_gains [n_channels][n_voices], d_out [n_channels][64 * n_vectors]. n_channels passes over the
+        signal - the comparator of Bank.process_mixdown_channels and the route for banks without it, not a hot path
+        (mlgpu_mixdown_channels)."""
+        g = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self._check(self.L.mlgpu_mixdown_channels(self.h, g(d_signal), int(layout), int(n_voices), int(n_vectors), int(n_channels), g(d_gains), g(d_out)))
+
     def mixdown_shard(self, d_signal, layout, n_voices, n_vectors, d_rows, d_gains=None):
         """This engine's SHARD of a larger bank: its voices' mixdown up to the hand-over level, shard_rows(n_voices) rows of 64 * n_vectors
         floats for mixdown_finish (mlgpu_mixdown_shard)."""
@@ -1019,6 +1030,19 @@ class Bank(_Handle):
         pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
         self.engine._check(self.L.mlgpu_bank_process_mixdown_shard(self.h, int(n_vectors), pin, int(in_layout), pg, pout))
 
+    def process_mixdown_channels(self, n_vectors, n_channels, d_gains, d_out, d_in=None, in_layout=Layout.QUAD):
+        """process_mixdown once per channel in one launch, the voices advancing once: d_gains [n_channels][V] per-voice gains
+        (required), d_out [n_channels][64 * n_vectors]; channel c has the bits of process_mixdown with d_gains[c]. Two channels (one:
+        process_mixdown itself); needs Engine.mixdown_reserve_channels (mlgpu_bank_process_mixdown_channels)."""
+        p = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self.engine._check(self.L.mlgpu_bank_process_mixdown_channels(self.h, int(n_vectors), p(d_in), int(in_layout), int(n_channels), p(d_gains), p(d_out)))
+
+    def process_mixdown_channels_shard(self, n_vectors, n_channels, d_gains, d_rows, d_in=None, in_layout=Layout.QUAD):
+        """process_mixdown_channels for a bank that is one engine's shard of a larger one: d_rows [n_channels][shard_rows(V)][64 *
+        n_vectors], each channel's rows finished on the host by mixdown_finish (mlgpu_bank_process_mixdown_channels_shard)."""
+        p = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self.engine._check(self.L.mlgpu_bank_process_mixdown_channels_shard(self.h, int(n_vectors), p(d_in), int(in_layout), int(n_channels), p(d_gains), p(d_rows)))
+
     def process_groups(self, n_vectors, d_out, out_group, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, in_group=1, d_gains=None):
         """process with the voices in groups of adjacent voices (1, 2, 4, 8 or 16), in one launch (mlgpu_bank_process_groups): d_in
         has one row per in_group voices, d_out one channel per out_group voices - ((0 + y0) + y1) + ... in voice order, the bits
@@ -1062,6 +1086,13 @@ class Bank(_Handle):
         pg = None if d_gains is None else ctypes.c_void_p(d_gains.ptr if hasattr(d_gains, "ptr") else int(d_gains))
         pp = None if d_peak is None else ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
         self.engine._check(self.L.mlgpu_bank_process_listed_mixdown(self.h, int(n_vectors), pin, int(in_layout), pg, pout, pp))
+
+    def process_listed_mixdown_channels(self, n_vectors, n_channels, d_gains, d_out, d_in=None, in_layout=Layout.QUAD, d_peak=None):
+        """process_listed_mixdown once per channel: d_gains [n_channels][V] is indexed by voice, d_out [n_channels][64 * n_vectors],
+        d_peak [K] by list position and taken before any gain; an empty list gives +0.0 in every channel
+        (mlgpu_bank_process_listed_mixdown_channels)."""
+        p = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self.engine._check(self.L.mlgpu_bank_process_listed_mixdown_channels(self.h, int(n_vectors), p(d_in), int(in_layout), int(n_channels), p(d_gains), p(d_out), p(d_peak)))
 
     def reserve_voice_list_groups(self, max_listed, out_group):
         """Setup: reserve_voice_list(max_listed), and the bank's voices are instruments of out_group (2, 4, 8, 16) adjacent voices -

@@ -176,6 +176,11 @@ ChainEntry makeMixEntry(const char* name)
   e.launch[kFormMix][0] = &launchChain<chain_mix_kernel<Chain<KS...>, false>>;
   e.launch[kFormListedMix][1] = &launchChain<chain_listed_mix_kernel<Chain<KS...>, true>>;
   e.launch[kFormListedMix][0] = &launchChain<chain_listed_mix_kernel<Chain<KS...>, false>>;
+  // ... and once per channel (mlgpu_bank_process_mixdown_channels): two channels; another count is another pair of forms
+  e.launch[kFormMixChannels][1] = &launchChain<chain_mix_channels_kernel<Chain<KS...>, true, kMixChannels>>;
+  e.launch[kFormMixChannels][0] = &launchChain<chain_mix_channels_kernel<Chain<KS...>, false, kMixChannels>>;
+  e.launch[kFormListedMixChannels][1] = &launchChain<chain_listed_mix_channels_kernel<Chain<KS...>, true, kMixChannels>>;
+  e.launch[kFormListedMixChannels][0] = &launchChain<chain_listed_mix_channels_kernel<Chain<KS...>, false, kMixChannels>>;
   return e;
 }
 

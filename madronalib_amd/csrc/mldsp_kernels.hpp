@@ -78,6 +78,20 @@ struct MixStrips<true>
   }
 };
 
+// the strips of the forms that sum the voices once per channel (chain_mix_channels_kernel): C strips per wavefront, channel c's at
+// mine() + c * kMixStrip. One strip per channel rather than one strip taken in turns: the turns would hold three unscaled quads in
+// registers from one store cadence to the next (12 VGPRs across the head's code), the strips cost LDS only - C = 2: 43 008 bytes
+// per workgroup, three workgroups (three wavefronts per SIMD) of a CU's 160 KiB (profiles/mixdown_channels.md).
+template <int C>
+struct MixChannelStrips
+{
+  static __device__ __forceinline__ float* mine()
+  {
+    __shared__ __attribute__((aligned(16))) float lds[(256 / 64) * C * kMixStrip];
+    return lds + (threadIdx.x >> 6) * (C * kMixStrip);
+  }
+};
+
 // ---- the streaming loop of one voice, the same for every form of the chain kernel ----
 // T DSPVectors, 16 quads each, one 16-byte access per quad. The forms differ in two places only: which row of a.in the voice reads
 // (vin >> inShift: the voice, and the input group's shift or 0) and what becomes of a finished quad (the SINK, below).
@@ -199,6 +213,46 @@ struct MixSink
     }
     mix64_park(strip, q & 3, y);
     if ((q & 3) == 3) mix64_sum_store(strip, a.mix + ((v >> 6) * a.T + t) * 64 + (size_t)(q & ~3) * 4);
+  }
+};
+
+// ... summed once per CHANNEL (chain_mix_channels_kernel, chain_listed_mix_channels_kernel; mlgpu_bank_process_mixdown_channels): the
+// finished quad times the voice's gain for channel c - one multiply per sample and channel, MixSink<true>'s - goes through channel
+// c's strip to channel c's rows of group sums, a.mix + c * a.mixChannelStride. Each channel is MixSink<true>'s tree with
+// a.mixGains + c * (the bank's voices), bit for bit: the same park, the same sum and store every fourth quad, the same fence and
+// barrier around it. The gains are required (no form without the multiply), so there is one loop. LISTED: the bank's voice count,
+// the stride between the channels' gains, is a.tableStride - a.V is the list's length there.
+template <int C, bool LISTED>
+struct MixChannelsSink
+{
+  static constexpr bool kTrips = true;
+  float* strip;
+  size_t v, vin;
+  float gain[C];
+  bool live;
+  __device__ __forceinline__ MixChannelsSink(float* strip_, size_t v_, size_t vin_, bool live_) : strip(strip_), v(v_), vin(vin_), live(live_)
+  {
+#pragma unroll
+    for (int c = 0; c < C; ++c) gain[c] = 1.f;
+  }
+  __device__ __forceinline__ void start(const ChainArgs& a)
+  {
+    const size_t bankVoices = LISTED ? a.tableStride : a.V;
+#pragma unroll
+    for (int c = 0; c < C; ++c) gain[c] = a.mixGains[(size_t)c * bankVoices + vin];
+  }
+  __device__ __forceinline__ void vector(const ChainArgs&, size_t) {}
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t t, int q, f32x4 y)
+  {
+    float* const row = a.mix + ((v >> 6) * a.T + t) * 64 + (size_t)(q & ~3) * 4;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+    {
+      f32x4 yc = {y.x * gain[c], y.y * gain[c], y.z * gain[c], y.w * gain[c]};
+      if (!live) yc = f32x4{0.f, 0.f, 0.f, 0.f};  // (a voice the bank does not have counts as +0)
+      mix64_park(strip + c * kMixStrip, q & 3, yc);
+      if ((q & 3) == 3) mix64_sum_store(strip + c * kMixStrip, row + (size_t)c * a.mixChannelStride);
+    }
   }
 };
 
@@ -369,14 +423,18 @@ __device__ __forceinline__ int choose_head(float xc)
 // Coefficients, state, the input constant, the gain and the streamed input row are the voice's (vs); the output row, the mix row and
 // the peak are the lane's (i). The list is ascending, which is what keeps the gathered 4-byte table loads and 16-byte input loads
 // of a wavefront nearly coalesced: 64 ascending voices touch at most as many cache lines as they span, each once.
-template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0, bool LISTED = false>
+// MIX_C > 1: the summing form once per channel (chain_mix_channels_kernel, chain_listed_mix_channels_kernel; MixChannelsSink)
+template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0, bool LISTED = false, int MIX_C = 1>
 __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
 {
   static_assert(!(MIX && OUT_G), "one summing form at a time");
   static_assert(!(LISTED && OUT_G), "no group form of a voice list");
+  static_assert(MIX_C >= 1 && (MIX || MIX_C == 1), "channels are channels of the summing form");
   apply_fp_mode(a.flags);
   const float* const ldsTable = staged_impulse_table<CH>(a);
-  float* const strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
+  float* strip;
+  if constexpr (MIX_C > 1) strip = MixChannelStrips<MIX_C>::mine();
+  else strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
   size_t v = remapped_block() * kChainBlock + threadIdx.x;
   bool live = true;
   if constexpr (MIX)
@@ -420,6 +478,11 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
       GroupSink<OUT_G, false> sink(strip, v);
       stream_voice_as<CH, HAS_SIGNAL, false>(head, ch, a, v, a.inGroupShift, xc, sink);
     }
+  }
+  else if constexpr (MIX && MIX_C > 1)
+  {
+    MixChannelsSink<MIX_C, LISTED> sink(strip, v, vs, live);
+    pk = stream_voice_as<CH, HAS_SIGNAL, LISTED>(head, ch, a, vs, 0, xc, sink);
   }
   else if constexpr (MIX)
   {
@@ -474,6 +537,19 @@ template <class CH, bool HAS_SIGNAL>
 __global__ __launch_bounds__(kChainBlock) void chain_listed_mix_kernel(const ChainArgs a)
 {
   chain_kernel_body<CH, HAS_SIGNAL, true, 0, true>(a);
+}
+
+// the voices' sum once per channel, every voice scaled by its C gains (mlgpu_bank_process_mixdown_channels and its listed form): a
+// template on C of which C = 2 is instantiated (chains.hip: makeMixEntry) - another C is another instantiation
+template <class CH, bool HAS_SIGNAL, int C>
+__global__ __launch_bounds__(kChainBlock) void chain_mix_channels_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, true, 0, false, C>(a);
+}
+template <class CH, bool HAS_SIGNAL, int C>
+__global__ __launch_bounds__(kChainBlock) void chain_listed_mix_channels_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, true, 0, true, C>(a);
 }
 
 // the same voices in groups: input row v >> a.inGroupShift, one output channel per OUT_G adjacent voices (see GroupSink);

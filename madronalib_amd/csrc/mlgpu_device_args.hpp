@@ -56,6 +56,11 @@ struct ChainArgs
   // A segment - the listed voices of one instrument - never crosses a multiple of 64 lanes. coeffs / state / inConst / mixGains are
   // read at the voice, `in` at row voice >> inGroupShift, tableStride is the bank's voice count. Else unused.
   const uint32_t* lanePlan = nullptr;
+  // chain_mix_channels_kernel / chain_listed_mix_channels_kernel (mlgpu_bank_process_mixdown_channels; MixChannelsSink): the voices'
+  // sum once per channel, each voice scaled by its gain for that channel. mixGains is then [mixChannels][voices of the bank]
+  // (required), channel c's rows of group sums are at mix + c * mixChannelStride floats. Else unused.
+  uint32_t mixChannels = 1;
+  size_t mixChannelStride = 0;
 };
 
 // EventsToSignals settings the device needs (events.hip, mldsp_events.hpp)

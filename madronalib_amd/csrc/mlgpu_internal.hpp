@@ -254,8 +254,11 @@ enum ChainForm
   kFormListed,        // chain_listed_kernel (the voices of a list): where kFormGroups is
   kFormListedMix,     // chain_listed_mix_kernel: where kFormMix is
   kFormListedGroups,  // chain_listed_group_kernel (the listed voices summed by instrument): where kFormGroups is
+  kFormMixChannels,        // chain_mix_channels_kernel<.., 2> (the voices' sum once per channel, two channels): where kFormMix is
+  kFormListedMixChannels,  // chain_listed_mix_channels_kernel<.., 2>: where kFormMix is
   kChainForms
 };
+constexpr int kMixChannels = 2;  // the channel count the two channel forms are instantiated for (the calls refuse any other but 1)
 // outGroup: the group size of kFormGroups, which picks the instantiation; no other form reads it
 typedef hipError_t (*ChainLauncher)(const ChainArgs& a, hipStream_t stream, int outGroup);
 
