@@ -620,6 +620,33 @@ size_t mlgpu_bank_listed_group_count(mlgpu_bank* b);
 int mlgpu_bank_listed_groups(mlgpu_bank* b, uint32_t* h_groups, size_t capacity);
 int mlgpu_bank_process_listed_groups(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
                                      const float* d_gains, float* d_out, int out_layout, uint32_t* d_peak);
+/* The group sums once per CHANNEL - a stereo instrument, a pan gain per voice (Synth::processVector clears every row of `outputs` and
+ * each voice accumulates into all of them, source/app/MLSynth.h:43-57). mlgpu_bank_process_groups / _listed_groups with
+ *   d_gains  [n_channels][n_voices], channel-major, REQUIRED when n_channels > 1. The channel stride is the bank's voice count, in the
+ *            listed form too: a gain is found by voice index, as in mlgpu_bank_process_listed_mixdown_channels.
+ *   d_out    n_channels signals one after the other, each of R rows in `out_layout`: R = n_voices / out_group in the plain call, R = J
+ *            (the listed instruments) in the listed one. Channel c starts at d_out + c * 64 * n_vectors * R floats. Each channel is
+ *            written once; with J = 0 nothing is written.
+ * Bits: from the same starting state, channel c is exactly what the one-channel call gives with d_gains + c * n_voices - one float32
+ *   multiply y * g_c per sample and channel, then ((0 + .) + .) + ... in voice order, in the engine's floating-point mode; a lone -0.0
+ *   product gives +0.0. The voices advance ONCE: state and coefficients afterwards are those after one one-channel call. d_peak[K] is
+ *   taken before any gain, unlisted voices are neither read nor written, and any split of n_vectors into launches gives the bits of
+ *   one launch. The lane plan of mlgpu_bank_set_voice_list is the same for both channel counts.
+ * n_channels == 1 is the one-channel call, unchanged (d_gains may then be NULL). n_channels == 2 runs the two-channel forms of the fused
+ *   voice chains' kernels (chain_group_channels_kernel, chain_listed_group_channels_kernel: the voices' signals never reach memory).
+ *   out_group is then one of 2, 4, 8, 16 - in the listed call the G of mlgpu_bank_reserve_voice_list_groups; in_group as in the
+ *   one-channel calls.
+ * Errors, in this order: MLGPU_ERR_UNSUPPORTED for n_channels other than 1 or 2, and for out_group == 1 with two channels (there is
+ *   nothing to sum); then the one-channel call's own checks in its order and with its words - for the listed call a sequence being
+ *   recorded and a missing groups reserve first, then the group sizes, whole groups and an input group's input, then MLGPU_ERR_INVALID
+ *   for null gains, then output, layouts and alignment -; last MLGPU_ERR_UNSUPPORTED, with nothing launched and the state untouched,
+ *   for a bank whose chain has no group form per channel (a single processor, an SVF cascade, a generated or processor-by-processor
+ *   bank): such a bank is built as a graph with two group-summed outputs (mlgpu_graph_set_output_group_sum on each).
+ * Neither call allocates. The plain call can be recorded into a sequence like mlgpu_bank_process_groups; the listed call cannot. */
+int mlgpu_bank_process_groups_channels(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
+                                       int n_channels, const float* d_gains, int out_group, float* d_out, int out_layout);
+int mlgpu_bank_process_listed_groups_channels(mlgpu_bank* b, size_t n_vectors, const float* d_in, int in_layout, int in_group,
+                                              int n_channels, const float* d_gains, float* d_out, int out_layout, uint32_t* d_peak);
 /* 1 if the chain maps to a single fused kernel, 0 if it runs processor by processor. */
 int mlgpu_bank_is_fused(mlgpu_bank* b);
 /* Name of the device kernel that dominates mlgpu_bank_process (for profile lookup). */

@@ -677,6 +677,21 @@ class VoiceBank
                                          out.data(), out.layout()));
   }
 
+  // ... and once per CHANNEL - a stereo instrument, a pan per voice (mlgpu_bank_process_groups_channels): gains [channels][voices] on
+  // the device, required for two channels; the voices advance once and channel c has the bits of processGroups with
+  // gains + c * voices. `out` has the memory of channels * voices / outGroup rows: channel c is the signal of voices / outGroup rows in
+  // out.layout() at out.data() + c * out.size() / channels - in MLGPU_LAYOUT_VOICE_MAJOR rows c R .. c R + R - 1 of `out` itself, in
+  // the other layouts a signal of its own. Two channels and groups of 2, 4, 8, 16 (one channel: processGroups itself).
+  void processGroupsChannels(const DeviceSignal* in, int inGroup, int channels, const float* gains, int outGroup, DeviceSignal& out)
+  {
+    if (inGroup < 1 || outGroup < 1 || channels < 1 || out.voices() * (size_t)outGroup != voices_ * (size_t)channels ||
+        (in && (in->voices() * (size_t)inGroup != voices_ || in->vectors() != out.vectors())))
+      throw Error(MLGPU_ERR_INVALID, "VoiceBank: signal shape mismatch");
+    commit();
+    eng_.check(mlgpu_bank_process_groups_channels(b_, out.vectors(), in ? in->data() : nullptr, in ? in->layout() : MLGPU_LAYOUT_QUAD, inGroup, channels, gains,
+                                                  outGroup, out.data(), out.layout()));
+  }
+
   // raw state (checkpoint / resume)
   std::vector<uint32_t> state(int proc, int idx) const
   {

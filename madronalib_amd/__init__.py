@@ -1121,6 +1121,25 @@ class Bank(_Handle):
         self.engine._check(self.L.mlgpu_bank_process_listed_groups(self.h, int(n_vectors), pin, int(in_layout), int(in_group), pg, pout,
                                                                    int(out_layout), pp))
 
+    def process_groups_channels(self, n_vectors, d_out, out_group, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, in_group=1, n_channels=2,
+                                d_gains=None):
+        """process_groups once per channel in one launch, the voices advancing once - a stereo instrument, a pan per voice: d_gains
+        [n_channels][V] (required for two channels), d_out n_channels signals of V / out_group rows in out_layout one after the other;
+        channel c has the bits of process_groups with d_gains[c]. Two channels and groups of 2, 4, 8, 16 (one channel: process_groups
+        itself); Status.ERR_UNSUPPORTED for a bank that is not one of the fused voice chains (mlgpu_bank_process_groups_channels)."""
+        p = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self.engine._check(self.L.mlgpu_bank_process_groups_channels(self.h, int(n_vectors), p(d_in), int(in_layout), int(in_group), int(n_channels), p(d_gains),
+                                                                     int(out_group), p(d_out), int(out_layout)))
+
+    def process_listed_groups_channels(self, n_vectors, d_out, out_layout=Layout.QUAD, d_in=None, in_layout=Layout.QUAD, in_group=1, n_channels=2,
+                                       d_gains=None, d_peak=None):
+        """process_listed_groups once per channel: d_gains [n_channels][V] is indexed by voice, d_out n_channels signals of J =
+        len(listed_groups) rows one after the other, d_peak [K] by list position and taken before any gain; the lane plan is the one
+        process_listed_groups runs by. Not while recording a sequence (mlgpu_bank_process_listed_groups_channels)."""
+        p = lambda b: None if b is None else ctypes.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+        self.engine._check(self.L.mlgpu_bank_process_listed_groups_channels(self.h, int(n_vectors), p(d_in), int(in_layout), int(in_group), int(n_channels),
+                                                                            p(d_gains), p(d_out), int(out_layout), p(d_peak)))
+
     def process_groups_host(self, n_vectors, out_group, in_signal=None, in_group=1, gains=None, layout=Layout.QUAD, in_layout=None):
         """Test convenience beside process_host: in_signal [V / in_group][64T] and the result [V / out_group][64T] are VOICE_MAJOR
         numpy, gains [V] numpy or None; the kernel writes `layout` and reads `in_layout` (default: the same)."""

@@ -49,6 +49,20 @@ hipError_t launchChainGroups(const ChainArgs& a, hipStream_t stream, int outGrou
   }
 }
 
+// ... once per channel (mlgpu_bank_process_groups_channels): two channels, groups of 2, 4, 8, 16 (a group of 1 has nothing to sum)
+template <bool HAS_SIGNAL, int... KS>
+hipError_t launchChainGroupsChannels(const ChainArgs& a, hipStream_t stream, int outGroup)
+{
+  switch (outGroup)
+  {
+    case 2: return launchChain<chain_group_channels_kernel<Chain<KS...>, HAS_SIGNAL, 2, kMixChannels>>(a, stream, 0);
+    case 4: return launchChain<chain_group_channels_kernel<Chain<KS...>, HAS_SIGNAL, 4, kMixChannels>>(a, stream, 0);
+    case 8: return launchChain<chain_group_channels_kernel<Chain<KS...>, HAS_SIGNAL, 8, kMixChannels>>(a, stream, 0);
+    case 16: return launchChain<chain_group_channels_kernel<Chain<KS...>, HAS_SIGNAL, 16, kMixChannels>>(a, stream, 0);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // How many wavefront lanes share one channel of a head-less SVF cascade (cascade_lanes_kernel). One lane per channel is the
 // cheapest per sample, but a bank needs ~49 000 channels before its wavefronts (two per SIMD at ~190 VGPRs) fill the chip;
 // smaller banks are spread over 2 or 4 lanes per channel (4 or 6 wavefronts per SIMD). Thresholds from
@@ -181,6 +195,11 @@ ChainEntry makeMixEntry(const char* name)
   e.launch[kFormMixChannels][0] = &launchChain<chain_mix_channels_kernel<Chain<KS...>, false, kMixChannels>>;
   e.launch[kFormListedMixChannels][1] = &launchChain<chain_listed_mix_channels_kernel<Chain<KS...>, true, kMixChannels>>;
   e.launch[kFormListedMixChannels][0] = &launchChain<chain_listed_mix_channels_kernel<Chain<KS...>, false, kMixChannels>>;
+  // ... and the sums by instrument once per channel (mlgpu_bank_process_groups_channels, _listed_groups_channels)
+  e.launch[kFormGroupsChannels][1] = &launchChainGroupsChannels<true, KS...>;
+  e.launch[kFormGroupsChannels][0] = &launchChainGroupsChannels<false, KS...>;
+  e.launch[kFormListedGroupsChannels][1] = &launchChain<chain_listed_group_channels_kernel<Chain<KS...>, true, kMixChannels>>;
+  e.launch[kFormListedGroupsChannels][0] = &launchChain<chain_listed_group_channels_kernel<Chain<KS...>, false, kMixChannels>>;
   return e;
 }
 

@@ -328,6 +328,85 @@ struct GroupSink
   }
 };
 
+// ... summed once per CHANNEL (chain_group_channels_kernel; mlgpu_bank_process_groups_channels): a stereo instrument, a pan per
+// voice. Channel c is GroupSink<OUT_G, true> with a.mixGains + c * a.V, bit for bit - one float32 multiply y * g_c per sample and
+// channel, then GroupSink's sum - written to channel c's region of the output, a.mixChannelStride floats behind channel c - 1's.
+// OUT_G = 2, 4, 8: the quad is scaled once per channel and goes through the lane-shift chain once per channel. OUT_G = 16: the
+// multiply is on the SUMMING side. The quad is parked unscaled, once, in the one strip GroupSink has; the wavefront's gains
+// ([C][64] by lane, parked once in start()) lie behind the strip, and lane (g, s) multiplies each entry by its voice's gain on the
+// way (mldsp_math.hpp: group16_sum_store_channels) - the same multiply in another lane. A strip per channel instead (scale, park and
+// sum twice) doubles the LDS to 41 472 bytes a workgroup, which leaves three wavefronts per SIMD where GroupSink runs four, and
+// measured 7 to 8 % slower (profiles/groups_channels.md). The gains are required (no form without the multiply), and there is
+// nothing to sum at OUT_G = 1, which the call refuses.
+template <int OUT_G, int C>
+struct GroupChannelStrips
+{
+  static __device__ __forceinline__ float* mine() { return nullptr; }
+};
+template <int C>
+struct GroupChannelStrips<16, C>
+{
+  static constexpr int kFloats = kGroup16Strip + C * 64;  // the strip, then the wavefront's gains [C][64]
+  static __device__ __forceinline__ float* mine()
+  {
+    __shared__ __attribute__((aligned(16))) float lds[(256 / 64) * kFloats];
+    return lds + (threadIdx.x >> 6) * kFloats;
+  }
+};
+
+template <int OUT_G, int C>
+struct GroupChannelsSink
+{
+  static_assert(OUT_G == 2 || OUT_G == 4 || OUT_G == 8 || OUT_G == 16, "group_sum_in_order's sizes");
+  static constexpr bool kTrips = false;  // (as GroupSink)
+  float* strip;
+  size_t v;
+  float gain[C];  // (OUT_G == 16: dead after start(), they are in LDS)
+  StoreSink row;
+  bool lastOfGroup;
+  __device__ __forceinline__ GroupChannelsSink(float* strip_, size_t v_) : strip(strip_), v(v_), row(0), lastOfGroup(false)
+  {
+#pragma unroll
+    for (int c = 0; c < C; ++c) gain[c] = 1.f;
+  }
+  __device__ __forceinline__ void start(const ChainArgs& a)
+  {
+#pragma unroll
+    for (int c = 0; c < C; ++c) gain[c] = a.mixGains[(size_t)c * a.V + v];
+    row = StoreSink(v / OUT_G);
+    row.start(a);
+    lastOfGroup = (threadIdx.x & (OUT_G - 1)) == OUT_G - 1;
+    if constexpr (OUT_G == 16)
+    {
+      // (read after the first sum's fence and barrier; the lanes past the last voice are whole groups that nobody adds up)
+#pragma unroll
+      for (int c = 0; c < C; ++c) strip[kGroup16Strip + c * 64 + (threadIdx.x & 63u)] = gain[c];
+    }
+  }
+  __device__ __forceinline__ void vector(const ChainArgs& a, size_t t) { row.vector(a, t); }
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t, int q, f32x4 y)
+  {
+    if constexpr (OUT_G == 16)
+    {
+      group16_park(strip, q & 3, y);
+      if ((q & 3) == 3) group16_sum_store_channels<C>(strip, strip + kGroup16Strip, row.po + (size_t)(q - 3) * row.outQ, row.outQ, a.mixChannelStride);
+    }
+    else
+    {
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+      {
+        f32x4 yc = {y.x * gain[c], y.y * gain[c], y.z * gain[c], y.w * gain[c]};
+        yc.x = group_sum_in_order<OUT_G>(yc.x);
+        yc.y = group_sum_in_order<OUT_G>(yc.y);
+        yc.z = group_sum_in_order<OUT_G>(yc.z);
+        yc.w = group_sum_in_order<OUT_G>(yc.w);
+        if (lastOfGroup) __builtin_nontemporal_store(yc, (f32x4*)((float*)(row.po + (size_t)q * row.outQ) + (size_t)c * a.mixChannelStride));
+      }
+    }
+  }
+};
+
 // the listed voices of one instrument - a segment of the wavefront's lanes, its size data of the host's lane plan - summed through
 // the segment strip (chain_listed_group_kernel): the gain, then mldsp_math.hpp's segment_park / segment_sum_store; every fourth quad
 // the segment's last lane stores four quads to the segment's row (consecutive segments, consecutive rows: in the QUAD layout a
@@ -363,6 +442,49 @@ struct SegmentSink
     }
     segment_park(strip, q & 3, y);
     if ((q & 3) == 3) segment_sum_store(strip, rank, length, longest, row.po + (size_t)(q - 3) * row.outQ, row.outQ);
+  }
+};
+
+// ... summed once per CHANNEL (chain_listed_group_channels_kernel; mlgpu_bank_process_listed_groups_channels): channel c is
+// SegmentSink with the gains a.mixGains + c * a.tableStride (the bank's voices: a gain is found by voice), written to channel c's
+// rows, a.mixChannelStride floats behind channel c - 1's. The multiply is on the summing side, as in GroupChannelsSink<16, C>: the
+// quad is parked unscaled, once, in SegmentSink's strip; the wavefronts' gains ([wavefront][C][64] by lane, parked once in start())
+// lie behind the workgroup's strips and their tail, kSegmentGainsTail floats readable behind the last; the segment's last lane
+// multiplies each entry by its lane's gain on the way (mldsp_math.hpp: segment_sum_store_channels). A pad lane parks neither quad nor
+// gain, and nobody adds its entries. A strip per channel instead measured 3 to 11 % slower (profiles/groups_channels.md). The gains
+// are required.
+constexpr int kSegmentStrips = (kChainBlock / 64) * kSegmentStrip + kSegmentTail;  // the workgroup's strips and their tail, floats
+constexpr int kSegmentGainsTail = 16;                                              // a sum reads up to 16 gains from its first lane's on
+template <int C>
+constexpr int kSegmentChannelsLds = kSegmentStrips + (kChainBlock / 64) * C * 64 + kSegmentGainsTail;
+template <int C>
+struct SegmentChannelsSink
+{
+  static constexpr bool kTrips = true;
+  float* strip;
+  float* gains;  // the wavefront's [C][64]
+  size_t vs;
+  StoreSink row;
+  unsigned rank, length;
+  int longest;
+  // (ldsStrips: the workgroup's kSegmentChannelsLds<C> floats)
+  __device__ __forceinline__ SegmentChannelsSink(float* ldsStrips, size_t vs_, size_t j, unsigned rank_, unsigned length_, int longest_)
+      : strip(ldsStrips + (threadIdx.x >> 6) * kSegmentStrip), gains(ldsStrips + kSegmentStrips + (threadIdx.x >> 6) * (C * 64)), vs(vs_), row(j), rank(rank_),
+        length(length_), longest(longest_)
+  {
+    __builtin_assume(length_ != 0u);  // (as SegmentSink)
+  }
+  __device__ __forceinline__ void start(const ChainArgs& a)
+  {
+#pragma unroll
+    for (int c = 0; c < C; ++c) gains[c * 64 + (threadIdx.x & 63u)] = a.mixGains[(size_t)c * a.tableStride + vs];  // (read after the first sum's fence and barrier)
+    row.start(a);
+  }
+  __device__ __forceinline__ void vector(const ChainArgs& a, size_t t) { row.vector(a, t); }
+  __device__ __forceinline__ void quad(const ChainArgs& a, size_t, int q, f32x4 y)
+  {
+    segment_park(strip, q & 3, y);
+    if ((q & 3) == 3) segment_sum_store_channels<C>(strip, gains, rank, length, longest, row.po + (size_t)(q - 3) * row.outQ, row.outQ, a.mixChannelStride);
   }
 };
 
@@ -423,17 +545,19 @@ __device__ __forceinline__ int choose_head(float xc)
 // Coefficients, state, the input constant, the gain and the streamed input row are the voice's (vs); the output row, the mix row and
 // the peak are the lane's (i). The list is ascending, which is what keeps the gathered 4-byte table loads and 16-byte input loads
 // of a wavefront nearly coalesced: 64 ascending voices touch at most as many cache lines as they span, each once.
-// MIX_C > 1: the summing form once per channel (chain_mix_channels_kernel, chain_listed_mix_channels_kernel; MixChannelsSink)
+// MIX_C > 1: the summing form once per channel (chain_mix_channels_kernel, chain_listed_mix_channels_kernel; MixChannelsSink), or
+// with OUT_G the group form once per channel (chain_group_channels_kernel; GroupChannelsSink)
 template <class CH, bool HAS_SIGNAL, bool MIX = false, int OUT_G = 0, bool LISTED = false, int MIX_C = 1>
 __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
 {
   static_assert(!(MIX && OUT_G), "one summing form at a time");
   static_assert(!(LISTED && OUT_G), "no group form of a voice list");
-  static_assert(MIX_C >= 1 && (MIX || MIX_C == 1), "channels are channels of the summing form");
+  static_assert(MIX_C >= 1 && (MIX || OUT_G > 1 || MIX_C == 1), "channels are channels of a summing form");
   apply_fp_mode(a.flags);
   const float* const ldsTable = staged_impulse_table<CH>(a);
   float* strip;
-  if constexpr (MIX_C > 1) strip = MixChannelStrips<MIX_C>::mine();
+  if constexpr (MIX_C > 1 && OUT_G != 0) strip = GroupChannelStrips<OUT_G, MIX_C>::mine();
+  else if constexpr (MIX_C > 1) strip = MixChannelStrips<MIX_C>::mine();
   else strip = OUT_G ? GroupStrips<OUT_G>::mine() : MixStrips<MIX>::mine();
   size_t v = remapped_block() * kChainBlock + threadIdx.x;
   bool live = true;
@@ -466,7 +590,12 @@ __device__ __forceinline__ void chain_kernel_body(const ChainArgs& a)
   const VoiceMem mem{a.coeffs + vs, a.state + vs, stride};
   const float xc = load_voice<CH, HAS_SIGNAL>(ch, a, mem, vs, ldsTable);
   const int head = choose_head<CH, HAS_SIGNAL>(xc);
-  if constexpr (OUT_G != 0)
+  if constexpr (OUT_G != 0 && MIX_C > 1)
+  {
+    GroupChannelsSink<OUT_G, MIX_C> sink(strip, v);
+    stream_voice_as<CH, HAS_SIGNAL, false>(head, ch, a, v, a.inGroupShift, xc, sink);
+  }
+  else if constexpr (OUT_G != 0)
   {
     if (a.mixGains != nullptr)  // (the same in all lanes: a kernel argument)
     {
@@ -559,6 +688,13 @@ __global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArg
 {
   chain_kernel_body<CH, HAS_SIGNAL, false, OUT_G>(a);
 }
+// ... and one output channel per OUT_G adjacent voices and CHANNEL, every voice scaled by its C gains (mlgpu_bank_process_groups_channels;
+// GroupChannelsSink): a template on C of which C = 2 is instantiated for OUT_G = 2, 4, 8, 16 (chains.hip: makeMixEntry)
+template <class CH, bool HAS_SIGNAL, int OUT_G, int C>
+__global__ __launch_bounds__(kChainBlock) void chain_group_channels_kernel(const ChainArgs a)
+{
+  chain_kernel_body<CH, HAS_SIGNAL, false, OUT_G, false, C>(a);
+}
 
 // ---- the listed voices summed by instrument (chain_listed_group_kernel, mlgpu_bank_process_listed_groups) ----
 // chain_listed_kernel's voices, chain_group_kernel's output: row j of a.out is ((0 + g y[a0]) + g y[a1]) + ... over the listed voices
@@ -574,12 +710,13 @@ __global__ __launch_bounds__(kChainBlock) void chain_group_kernel(const ChainArg
 // 3. The lanes of the last wavefront at or past N have no plan entry: they are pads without reading one. Whole wavefronts at or
 //    past N leave like chain_kernel's.
 // A pad lane loads nothing, runs nothing and stores nothing: no table word, no peak, no output, no strip entry.
-template <class CH, bool HAS_SIGNAL>
+// C > 1: once per channel (chain_listed_group_channels_kernel; SegmentChannelsSink) - the same lanes, the same plan, the gains in LDS.
+template <class CH, bool HAS_SIGNAL, int C = 1>
 __device__ __forceinline__ void chain_listed_group_body(const ChainArgs& a)
 {
   apply_fp_mode(a.flags);
   const float* const ldsTable = staged_impulse_table<CH>(a);
-  __shared__ __attribute__((aligned(16))) float ldsStrips[(kChainBlock / 64) * kSegmentStrip + kSegmentTail];
+  __shared__ __attribute__((aligned(16))) float ldsStrips[C > 1 ? kSegmentChannelsLds<C> : kSegmentStrips];
   float* const strip = ldsStrips + (threadIdx.x >> 6) * kSegmentStrip;
   const size_t l = remapped_block() * kChainBlock + threadIdx.x;
   if (l >= a.V) return;
@@ -594,8 +731,17 @@ __device__ __forceinline__ void chain_listed_group_body(const ChainArgs& a)
   const int head = choose_head<CH, HAS_SIGNAL>(xc);  // (over the lanes that are voices)
   // the wavefront's longest segment, rounded up to a size segment_sum_store has the reads of
   const int longest = __builtin_amdgcn_ballot_w64(length > 8u) ? 16 : (__builtin_amdgcn_ballot_w64(length > 4u) ? 8 : (__builtin_amdgcn_ballot_w64(length > 2u) ? 4 : 2));
-  SegmentSink sink(strip, vs, plan.z, rank, length, longest);
-  const uint32_t pk = stream_voice_as<CH, HAS_SIGNAL, true>(head, ch, a, vs, a.inGroupShift, xc, sink);
+  uint32_t pk;
+  if constexpr (C > 1)
+  {
+    SegmentChannelsSink<C> sink(ldsStrips, vs, plan.z, rank, length, longest);
+    pk = stream_voice_as<CH, HAS_SIGNAL, true>(head, ch, a, vs, a.inGroupShift, xc, sink);
+  }
+  else
+  {
+    SegmentSink sink(strip, vs, plan.z, rank, length, longest);
+    pk = stream_voice_as<CH, HAS_SIGNAL, true>(head, ch, a, vs, a.inGroupShift, xc, sink);
+  }
   ch.store(mem);
   if (a.peaks != nullptr) a.peaks[plan.y] = pk;  // (the same in all lanes: a kernel argument)
 }
@@ -604,6 +750,11 @@ template <class CH, bool HAS_SIGNAL>
 __global__ __launch_bounds__(kChainBlock) void chain_listed_group_kernel(const ChainArgs a)
 {
   chain_listed_group_body<CH, HAS_SIGNAL>(a);
+}
+template <class CH, bool HAS_SIGNAL, int C>
+__global__ __launch_bounds__(kChainBlock) void chain_listed_group_channels_kernel(const ChainArgs a)
+{
+  chain_listed_group_body<CH, HAS_SIGNAL, C>(a);
 }
 
 // ---------------------------------------------------------------------------------------------

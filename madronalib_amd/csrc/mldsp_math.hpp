@@ -164,6 +164,35 @@ MLD void group16_sum_store(const float* strip, group16_f32x4* outQuad0, size_t s
   __builtin_amdgcn_wave_barrier();
 }
 
+// ... once per CHANNEL, the multiply on the summing side (mldsp_kernels.hpp: GroupChannelsSink): the strip holds the UNSCALED quads,
+// `gains` the wavefront's [C][64] gains by lane; lane (g, s) multiplies each entry by its voice's gain for channel c on the way - the
+// float32 multiply the parking lane would have made, kept apart from the add by -ffp-contract=off - and stores channel c's float
+// channelStride floats behind channel c - 1's. Per channel the bits of group16_sum_store on a strip of scaled quads.
+template <int C>
+MLD void group16_sum_store_channels(const float* strip, const float* gains, group16_f32x4* outQuad0, size_t strideQ, size_t channelStride)
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const unsigned l = threadIdx.x & 63u, s = l & 15u, qq = s >> 2, k = s & 3u;
+  const float* p = strip + qq * kGroup16Quad + (l >> 4) * 80u + k;
+  const float* g = gains + (l >> 4) * 16u;
+  float acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.f + p[0] * g[c * 64];
+#pragma unroll
+  for (int v = 1; v < 16; ++v)
+  {
+    const float x = p[v * 4];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = acc[c] + x * g[c * 64 + v];
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) __builtin_nontemporal_store(acc[c], (float*)(outQuad0 + (size_t)qq * strideQ) + k + (size_t)c * channelStride);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // The same sums over SEGMENTS of a wavefront's lanes: runs of 1 .. 16 consecutive lanes that start anywhere (the listed voices of
 // one instrument, laid out by the host: voice_list.hpp, mlvl::planGroups), which no row of 16 confines - hence LDS, not the lane
 // shifts. Every lane that takes part parks its quads for four consecutive quads at its own place of the wavefront's strip,
@@ -247,6 +276,83 @@ MLD void segment_sum_store(const float* strip, unsigned rank, unsigned length, i
       segment_sum_store_n<8>(first, length, outQuad0, strideQ);
     else
       segment_sum_store_n<16>(first, length, outQuad0, strideQ);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ... once per CHANNEL, the multiply on the summing side (mldsp_kernels.hpp: SegmentChannelsSink): the strip holds the UNSCALED
+// quads, `gains` the wavefront's [C][64] gains by lane with 16 floats readable behind the last. The segment's last lane reads its
+// entries' gains with the entries - `g` is the gain of the segment's first entry for channel 0 - and adds entry * gain per channel:
+// per channel the bits of segment_sum_store on a strip of scaled quads. A read past the segment's end, of an entry or of a gain, is
+// never used.
+template <int N, int C>
+MLD void segment_sum_quad_channels(const group16_f32x4* p, const float* g, unsigned length, group16_f32x4 (&acc)[C])
+{
+  constexpr int B = N < 8 ? N : 8;
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = group16_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int b = 0; b < N; b += B)
+  {
+    group16_f32x4 x[B];
+    float gg[C][B];
+#pragma unroll
+    for (int d = 0; d < B; ++d) x[d] = p[b + d];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int d = 0; d < B; ++d) gg[c][d] = g[c * 64 + b + d];
+#pragma unroll
+    for (int d = 0; d < B; ++d)
+    {
+      if ((unsigned)(b + d) < length)
+      {
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+        {
+          acc[c].x = acc[c].x + x[d].x * gg[c][d];
+          acc[c].y = acc[c].y + x[d].y * gg[c][d];
+          acc[c].z = acc[c].z + x[d].z * gg[c][d];
+          acc[c].w = acc[c].w + x[d].w * gg[c][d];
+        }
+      }
+    }
+    if (b + B < N) __builtin_amdgcn_sched_barrier(0);
+  }
+}
+template <int N, int C>
+MLD void segment_sum_store_channels_n(const float* first, const float* g, unsigned length, group16_f32x4* outQuad0, size_t strideQ, size_t channelStride)
+{
+#pragma unroll 1
+  for (int qq = 0; qq < 4; ++qq)
+  {
+    group16_f32x4 acc[C];
+    segment_sum_quad_channels<N, C>((const group16_f32x4*)(first + qq * kSegmentQuad), g, length, acc);
+#pragma unroll
+    for (int c = 0; c < C; ++c) __builtin_nontemporal_store(acc[c], (group16_f32x4*)((float*)(outQuad0 + (size_t)qq * strideQ) + (size_t)c * channelStride));
+  }
+}
+template <int C>
+MLD void segment_sum_store_channels(const float* strip, const float* gains, unsigned rank, unsigned length, int longest, group16_f32x4* outQuad0, size_t strideQ,
+                                    size_t channelStride)
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (rank + 1u == length)
+  {
+    const unsigned firstLane = (threadIdx.x & 63u) - rank;
+    const float* first = strip + firstLane * 4u;
+    const float* g = gains + firstLane;
+    if (longest <= 2)
+      segment_sum_store_channels_n<2, C>(first, g, length, outQuad0, strideQ, channelStride);
+    else if (longest <= 4)
+      segment_sum_store_channels_n<4, C>(first, g, length, outQuad0, strideQ, channelStride);
+    else if (longest <= 8)
+      segment_sum_store_channels_n<8, C>(first, g, length, outQuad0, strideQ, channelStride);
+    else
+      segment_sum_store_channels_n<16, C>(first, g, length, outQuad0, strideQ, channelStride);
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();

@@ -58,7 +58,10 @@ struct ChainArgs
   const uint32_t* lanePlan = nullptr;
   // chain_mix_channels_kernel / chain_listed_mix_channels_kernel (mlgpu_bank_process_mixdown_channels; MixChannelsSink): the voices'
   // sum once per channel, each voice scaled by its gain for that channel. mixGains is then [mixChannels][voices of the bank]
-  // (required), channel c's rows of group sums are at mix + c * mixChannelStride floats. Else unused.
+  // (required); mixChannelStride is the stride between the channels' regions of whatever the form sums into, in floats: channel
+  // c's rows of group sums are at mix + c * mixChannelStride. chain_group_channels_kernel / chain_listed_group_channels_kernel
+  // (mlgpu_bank_process_groups_channels, _listed_groups_channels; GroupChannelsSink, SegmentChannelsSink) read both the same way:
+  // channel c's signal of rows is at out.base + c * mixChannelStride. Else unused.
   uint32_t mixChannels = 1;
   size_t mixChannelStride = 0;
 };

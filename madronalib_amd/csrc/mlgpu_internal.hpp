@@ -256,9 +256,11 @@ enum ChainForm
   kFormListedGroups,  // chain_listed_group_kernel (the listed voices summed by instrument): where kFormGroups is
   kFormMixChannels,        // chain_mix_channels_kernel<.., 2> (the voices' sum once per channel, two channels): where kFormMix is
   kFormListedMixChannels,  // chain_listed_mix_channels_kernel<.., 2>: where kFormMix is
+  kFormGroupsChannels,        // chain_group_channels_kernel<.., 2, 4, 8 or 16, 2> (the sums by instrument once per channel): where kFormMix is
+  kFormListedGroupsChannels,  // chain_listed_group_channels_kernel<.., 2>: where kFormMix is
   kChainForms
 };
-constexpr int kMixChannels = 2;  // the channel count the two channel forms are instantiated for (the calls refuse any other but 1)
+constexpr int kMixChannels = 2;  // the channel count the channel forms are instantiated for (the calls refuse any other but 1)
 // outGroup: the group size of kFormGroups, which picks the instantiation; no other form reads it
 typedef hipError_t (*ChainLauncher)(const ChainArgs& a, hipStream_t stream, int outGroup);
 
