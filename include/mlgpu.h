@@ -967,7 +967,7 @@ int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h
  *   wavefront's neighbouring voices of one 256-voice block (layout 0, the rows, is served: mlgpu_graph_set_delay_layout(g, 0));
  *   an output group sum (mlgpu_graph_set_output_group_sum) without mlgpu_graph_enable_voice_list_groups (below), with it a mixdown of
  *   all voices in either form and outputs summed by groups of different sizes or none at all; the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2));
- *   event rows (mlgpu_graph_add_event_row: the events object goes by lane); a MLGPU_REGION_DOWNSAMPLE_2X region (it pairs DSPVectors
+ *   event rows (mlgpu_graph_add_event_row) without mlgpu_graph_enable_voice_list_events (VOICE LISTS FOR GRAPHS WITH EVENT ROWS); a MLGPU_REGION_DOWNSAMPLE_2X region (it pairs DSPVectors
  *   2k and 2k + 1 by the graph's count, not by a voice's).
  * Input groups, UPSAMPLE_2X regions, feedback nodes, controls, live constants, const vectors, routes and impulse tables are served.
  *
@@ -1208,6 +1208,68 @@ int mlgpu_events_reserve_for_graph(mlgpu_events* ev, size_t max_vectors);
 size_t mlgpu_events_graph_reserve_bytes(mlgpu_events* ev, size_t max_vectors);
 int mlgpu_graph_process_events(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
                                const float* const* d_controls, float* const* d_outputs, int out_layout);
+
+/* VOICE LISTS FOR GRAPHS WITH EVENT ROWS: the instrument bank runs, in one fused launch, only the voices that sound.
+ *
+ * mlgpu_graph_enable_voice_list_events(g, 1) is a build call like mlgpu_graph_enable_voice_lists and turns that on too
+ * (mlgpu_graph_enable_voice_lists(g, 0) turns it off with the rest). Without it nothing changes: both kernels' text, and the refusal
+ * of voice lists on a graph with event rows. With it a graph with event rows gets whichever listed form it has - the plain one, or the
+ * lane plan's with mlgpu_graph_enable_voice_list_groups as well -, its CtlVoice loaded with the gathered voice: the 16-byte control
+ * record, the two side signals and the drift glide's words are addressed by voice index. Every other refusal of the listed forms
+ * stays. With it, event rows also no longer ask a graph with a mixed-down output for whole wavefronts: the last wavefront's spare lanes
+ * run the last voice again, event rows included.
+ *
+ * mlgpu_graph_process_events_listed / _listed_groups: mlgpu_graph_process_events for the voices of the list.
+ *   The events object belongs to ALL voices. Its host half (routing, record upload) and the control kernel run for every lane in every
+ *   call, also in a call with an empty list, which launches no voice kernel: note state, pitch and bend glides and the drift random walk
+ *   advance for listed and unlisted voices alike.
+ *   The voice kernel runs for the listed voices only, under the rule of mlgpu_graph_process_listed / _listed_groups: plain outputs are K
+ *   rows by list position, a mixed-down output is the K-voice tree, a group-summed output is J rows, d_peak has K words; unlisted
+ *   voices' coefficient, state, param, feedback and ring words are neither read nor written; any split of n_vectors into several
+ *   launches gives the bits of one launch; the graph's DSPVector count is not advanced.
+ *   Bits: for a listed voice the pitch and gate node values are those of CtlVoice run on that voice's control records and drift-glide
+ *   words. The gate row always has the bits of mlgpu_events_process. The pitch row has them when the drift amount is 0 (up to the sign
+ *   of a pitch sample that is exactly zero) or when the voice has been listed in every launch since the object was cleared.
+ *   The one thing that does not advance for an unlisted voice is the drift LinearGlide the voice kernel owns (glide 5 of the events
+ *   state: mCurrVec and five words). Those words are neither read nor written; a relisted voice glides from where it stood to the
+ *   current drift value. (Exact would cost 8 bytes per unlisted voice-sample - what the list exists to avoid.)
+ *   After listed blocks a block may still be processed by mlgpu_events_process or mlgpu_graph_process_events; with drift amount 0 the
+ *   bits are those of never having used lists.
+ *   Statuses, all before the router consumes the block's events: MLGPU_ERR_INVALID naming the switch on a graph built without it; the
+ *   refusals of mlgpu_graph_process_events (nothing bound, negative offset, MLGPU_ERR_UNSUPPORTED under MPE, MLGPU_ERR_RANGE for a
+ *   block longer than mlgpu_events_reserve_for_graph); those of the listed call it mirrors (a missing reserve, misaligned peaks,
+ *   recording a sequence). Neither call allocates after the reserves. mlgpu_graph_process_listed[_groups] on a graph with event rows
+ *   answers MLGPU_ERR_INVALID and names these calls.
+ *
+ * LETTING THE HOST MAKE THE LIST. Voice allocation, stealing, unison and the pedal are decided by the host router inside the process
+ * call - after the list had to be set. mlgpu_events_route_ahead(ev, n_vectors, start_offset) does the router's work of the coming launch
+ * now. The next mlgpu_events_process / mlgpu_graph_process_events* call on the object must pass the same n_vectors and start_offset; it
+ * uses the routed records instead of routing again. A call with other values, mlgpu_events_add_event(s) and a second route_ahead get
+ * MLGPU_ERR_INVALID while a routed launch is pending; nothing is consumed and the routed launch stays pending. route_ahead makes the
+ * checks a process call makes before routing (sample rate, recording, the controller reserve, the reserve-for-graph length where one
+ * was made). mlgpu_events_clear cancels a pending launch.
+ * mlgpu_events_sounding_voices(ev, h_voices, capacity, &n) is valid after a route (ahead, or a process call) until the next. It
+ * writes, ascending, every voice index v (instrument * polyphony + voice: the graph's voice index) for which the routed launch holds at
+ * least one record, or whose held velocity is non-zero at the launch's end - so every voice whose gate row is non-zero anywhere in the
+ * launch is in the set. *n is the set's size; MLGPU_ERR_RANGE (with *n set, nothing written) when capacity is smaller;
+ * MLGPU_ERR_UNSUPPORTED under MPE. No device access, no allocation; it costs the words of a bitmap over the voices, not a walk over them.
+ *
+ * The intended block:
+ *   1. mlgpu_events_add_events                       the block's events
+ *   2. mlgpu_events_route_ahead(ev, T, off)
+ *   3. mlgpu_events_sounding_voices
+ *   4. the host unions them with its tails: voices listed earlier whose d_peak has not died away yet (profiles/voice_list.md)
+ *   5. mlgpu_graph_set_voice_list
+ *   6. mlgpu_graph_process_events_listed[_groups](g, T, off, ...)
+ *   7. mlgpu_events_clear_events at the block's end
+ * A note-on that lands on a voice the host did not list is not an error: the events object has it, the voice is silent until listed. */
+int mlgpu_graph_enable_voice_list_events(mlgpu_graph* g, int on);
+int mlgpu_graph_process_events_listed(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
+                                      const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
+int mlgpu_graph_process_events_listed_groups(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
+                                             const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
+int mlgpu_events_route_ahead(mlgpu_events* ev, size_t n_vectors, int start_offset);
+int mlgpu_events_sounding_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n);
 
 /* ------------------------------------------------------------------------- */
 /* published signals                                                         */

@@ -677,6 +677,20 @@ class Events(_Handle):
         arr = (ctypes.c_void_p * 8)(*[None if b is None else b.ptr for b in d_outputs])
         self.engine._check(self.L.mlgpu_events_process(self.h, int(n_vectors), int(start_offset), arr, int(layout)))
 
+    def route_ahead(self, n_vectors, start_offset):
+        """The router's work of the coming launch, now (mlgpu_events_route_ahead): sounding_voices() then tells which voices that launch
+        makes sound. The next process call on this object must pass the same n_vectors and start_offset."""
+        self.engine._check(self.L.mlgpu_events_route_ahead(self.h, int(n_vectors), int(start_offset)))
+
+    def sounding_voices(self):
+        """The voices (instrument * polyphony + voice, ascending, uint32) that the routed launch holds a record for or that hold a
+        non-zero velocity at its end - every voice whose gate is non-zero anywhere in it (mlgpu_events_sounding_voices). No device access."""
+        if getattr(self, "_sounding", None) is None:
+            self._sounding = np.zeros(self.V, np.uint32)
+        n = ctypes.c_size_t()
+        self.engine._check(self.L.mlgpu_events_sounding_voices(self.h, _np_ptr(self._sounding), self._sounding.size, ctypes.byref(n)))
+        return self._sounding[:n.value].copy()
+
     def reserve_for_graph(self, max_vectors):
         """Setup-time reserve of the control records and side signals a graph bound to this object needs for blocks of up to max_vectors
         DSPVectors (mlgpu_events_reserve_for_graph): from then on Graph.process_events never allocates and refuses longer blocks."""
@@ -1212,7 +1226,8 @@ class Graph(_Handle):
     _destroy = "mlgpu_graph_destroy"
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
-                 live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False):
+                 live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False,
+                 voice_list_events=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1235,6 +1250,8 @@ class Graph(_Handle):
             self.enable_voice_lists()
         if voice_list_groups:   # ... and the listed form goes by the lane plan: reserve_voice_list_groups / process_listed_groups
             self.enable_voice_list_groups()
+        if voice_list_events:   # ... and a graph with event rows has a listed form: process_events_listed / process_events_listed_groups
+            self.enable_voice_list_events()
         if description is not None:
             for n in description:
                 self.add(**n)
@@ -1346,6 +1363,34 @@ class Graph(_Handle):
         pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
         pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
         self._check(self.L.mlgpu_graph_process_listed_groups(self.h, int(n_vectors), pi, int(in_layout), pc, po, int(out_layout), pp))
+
+    def enable_voice_list_events(self, on=True):
+        """Before compile: voice lists, also for a graph with event rows - its listed kernel expands the control records of the gathered
+        voice (mlgpu_graph_enable_voice_list_events). enable_voice_lists(False) turns it off with the rest."""
+        self._check(self.L.mlgpu_graph_enable_voice_list_events(self.h, 1 if on else 0))
+
+    def _process_events_listed(self, fn, n_vectors, start_offset, d_inputs, d_outputs, in_layout, out_layout, d_controls, d_peak):
+        raw = lambda b: b.ptr if hasattr(b, "ptr") else int(b)  # noqa: E731
+        pi = (ctypes.c_void_p * max(1, len(d_inputs)))(*[raw(b) for b in d_inputs])
+        po = (ctypes.c_void_p * max(1, len(d_outputs)))(*[raw(b) for b in d_outputs])
+        pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
+        pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
+        self._check(fn(self.h, int(n_vectors), int(start_offset), pi, int(in_layout), pc, po, int(out_layout), pp))
+
+    def process_events_listed(self, n_vectors, start_offset, d_inputs, d_outputs, in_layout=Layout.QUAD, out_layout=Layout.QUAD, d_controls=(),
+                              d_peak=None):
+        """process_events for the listed voices: the bound Events object advances for all its voices (also with an empty list), the
+        voice kernel runs the listed ones under process_listed's rule (mlgpu_graph_process_events_listed). The block: add_events,
+        Events.route_ahead, Events.sounding_voices() united with the host's tails, set_voice_list, this call, clear_events."""
+        self._process_events_listed(self.L.mlgpu_graph_process_events_listed, n_vectors, start_offset, d_inputs, d_outputs, in_layout, out_layout,
+                                    d_controls, d_peak)
+
+    def process_events_listed_groups(self, n_vectors, start_offset, d_inputs, d_outputs, in_layout=Layout.QUAD, out_layout=Layout.QUAD,
+                                     d_controls=(), d_peak=None):
+        """process_events_listed under process_listed_groups' rule: a group-summed output has one row per listed instrument
+        (mlgpu_graph_process_events_listed_groups)."""
+        self._process_events_listed(self.L.mlgpu_graph_process_events_listed_groups, n_vectors, start_offset, d_inputs, d_outputs, in_layout,
+                                    out_layout, d_controls, d_peak)
 
     def _id(self, ref):
         return self.ids[ref] if isinstance(ref, str) else int(ref)

@@ -1088,10 +1088,25 @@ extern "C"
   size_t mlgpu_events_num_voices(mlgpu_events* ev) { return ev ? ev->router.instruments() * (size_t)ev->router.polyphony() : 0; }
   int mlgpu_events_newest_voice(mlgpu_events* ev, size_t instrument) { return (ev && instrument < ev->router.instruments()) ? ev->router.newestVoice(instrument) - 1 : -2; }
 
+  // a launch routed ahead (mlgpu_events_route_ahead) is pending: the object takes no events and no other launch until that one is made
+  static const char* const kAheadPending =
+      "events: a launch routed ahead (mlgpu_events_route_ahead) is pending - the next process call takes its n_vectors and start_offset, and events are added after it";
+  // What every call that routes - mlgpu_events_process, mlgpu_events_prepare_for_graph, mlgpu_events_route_ahead - refuses before the
+  // router consumes a block's events: one list for the three
+  static int checkBeforeRouting(mlgpu_events* ev, size_t nVectors)
+  {
+    if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events route on the host: not while recording a sequence");
+    if (ev->sr == 0) return efail(ev, MLGPU_ERR_INVALID, "events: no sample rate (the reference does nothing, :385)");
+    if (!ev->router.watched().empty() && nVectors > ev->ctlMaxVectors)
+      return efail(ev, MLGPU_ERR_RANGE, "events_process: more DSPVectors than events_watch_controllers reserved the controller signals for");
+    return MLGPU_OK;
+  }
+
   int mlgpu_events_add_event(mlgpu_events* ev, size_t instrument, const mlgpu_event* e)  // addEvent, :367-372
   {
     if (!ev || !e) return MLGPU_ERR_INVALID;
     if (instrument >= ev->router.instruments()) return efail(ev, MLGPU_ERR_RANGE, "events_add_event: instrument out of range");
+    if (ev->router.aheadPending()) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     ev->router.addEvent(instrument, *e);
     return MLGPU_OK;
   }
@@ -1100,6 +1115,7 @@ extern "C"
     if (!ev || (n && (!instruments || !events))) return MLGPU_ERR_INVALID;
     for (size_t i = 0; i < n; ++i)
       if (instruments[i] >= ev->router.instruments()) return efail(ev, MLGPU_ERR_RANGE, "events_add_events: instrument out of range");
+    if (n && ev->router.aheadPending()) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     for (size_t i = 0; i < n; ++i) ev->router.addEvent(instruments[i], events[i]);
     return MLGPU_OK;
   }
@@ -1163,9 +1179,9 @@ extern "C"
   {
     mlgpu_engine* e = ev->e;
     EventRouter& router = ev->router;
-    if (!router.watched().empty() && nVectors > ev->ctlMaxVectors)
-      return efail(ev, MLGPU_ERR_RANGE, "events_process: more DSPVectors than events_watch_controllers reserved the controller signals for");
-    router.route(nVectors, startOffset);  // (before the wait below: block k + 1 is routed while block k runs)
+    // (the callers have made checkBeforeRouting's checks)
+    // (before the wait below: block k + 1 is routed while block k runs; a launch routed ahead keeps its records)
+    if (!router.route(nVectors, startOffset)) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     sgOut = ev->stage.take();
     if (!sgOut) return efail(ev, MLGPU_ERR_HIP, "events_process: waiting for the launch before last");
@@ -1217,8 +1233,7 @@ extern "C"
     if (!ev || !d_outputs) return MLGPU_ERR_INVALID;
     mlgpu_engine* e = ev->e;
     if (nVectors == 0) return MLGPU_OK;
-    if (e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_process routes events on the host: not while recording a sequence");
-    if (ev->sr == 0) return efail(ev, MLGPU_ERR_INVALID, "events_process: no sample rate (the reference does nothing, :385)");
+    if (const int st = checkBeforeRouting(ev, nVectors)) return st;
     if (layout < 0 || layout > MLGPU_LAYOUT_VOICE_MAJOR) return efail(ev, MLGPU_ERR_INVALID, "events_process: bad layout");
     // everything that can be refused is refused BEFORE the router consumes the block's note events: after this point the
     // host-side voice allocator (keys, creatorKeyIdx, sustain pedal, lastFreeVoiceFound) has advanced, and an error return
@@ -1229,6 +1244,7 @@ extern "C"
       if (d_outputs[r] && ((uintptr_t)d_outputs[r] & 15)) return efail(ev, MLGPU_ERR_INVALID, "events_process: misaligned output");
       if (d_outputs[r] && !((ev->rowMask >> r) & 1u)) return efail(ev, MLGPU_ERR_INVALID, "events_process: an output was passed for a row outside events_set_wanted_rows");
     }
+    if (ev->router.aheadPending() && !ev->router.aheadIs(nVectors, startOffset)) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     EventsDev dev;
     mlgpu_events::Staging* sg = nullptr;
     const int pst = prepare(ev, nVectors, startOffset, dev, sg);
@@ -1301,9 +1317,9 @@ extern "C"
   {
     if (!ev || !dev || !staging) return MLGPU_ERR_INVALID;
     if (nVectors == 0) return MLGPU_OK;
-    if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events route on the host: not while recording a sequence");
-    if (ev->sr == 0) return efail(ev, MLGPU_ERR_INVALID, "events: no sample rate (the reference does nothing, :385)");
+    if (const int st = checkBeforeRouting(ev, nVectors)) return st;
     if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
+    if (ev->router.aheadPending() && !ev->router.aheadIs(nVectors, startOffset)) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     mlgpu_engine* e = ev->e;
     const size_t lanes = ev->router.lanes();
     // the control records and the two side signals of e2s_ctl_kernel: sized by mlgpu_events_reserve_for_graph at setup. An object that
@@ -1336,7 +1352,32 @@ extern "C"
     dev->rowG = (const float4*)ev->d_rowG.get();
     return MLGPU_OK;
   }
-  // the graph's voice kernel (which consumes the ranges) could not be launched after prepare_for_graph had succeeded
+  // The router's work of the coming launch, now: the host reads mlgpu_events_sounding_voices and makes its voice list before the
+  // launch. Every check a process call makes before it routes is made here, so the launch that follows has nothing left to refuse
+  // in this object but other values than these.
+  int mlgpu_events_route_ahead(mlgpu_events* ev, size_t nVectors, int startOffset)
+  {
+    if (!ev) return MLGPU_ERR_INVALID;
+    if (nVectors == 0) return efail(ev, MLGPU_ERR_INVALID, "events_route_ahead: no DSPVectors (a process call of none routes nothing)");
+    if (startOffset < 0) return efail(ev, MLGPU_ERR_INVALID, "events_route_ahead: negative frame offset");
+    if (ev->router.aheadPending()) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
+    if (const int st = checkBeforeRouting(ev, nVectors)) return st;
+    if (ev->ctlRecReserved && nVectors > ev->ctlRecVectors)
+      return efail(ev, MLGPU_ERR_RANGE, "events_route_ahead: more DSPVectors than mlgpu_events_reserve_for_graph reserved the control records for");
+    ev->router.routeAhead(nVectors, startOffset);
+    return MLGPU_OK;
+  }
+  int mlgpu_events_sounding_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n)
+  {
+    if (!ev || !n || (capacity && !h_voices)) return MLGPU_ERR_INVALID;
+    *n = 0;
+    if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events_sounding_voices: MIDI protocol only (a voice index is a lane)");
+    if (!ev->router.soundingVoices(h_voices, capacity, n))
+      return efail(ev, MLGPU_ERR_RANGE, "events_sounding_voices: " + std::to_string(*n) + " voices sound, the caller's memory holds " + std::to_string(capacity));
+    return MLGPU_OK;
+  }
+  // the graph's voice kernel could not be launched after prepare_for_graph had succeeded (e2s_ctl_kernel has consumed the lanes' record
+  // ranges by then, or will: abandonRanges puts back whatever it has not, stream-ordered, and submits the staging set's turn)
   int mlgpu_events_abandoned_by_graph(mlgpu_events* ev, void* staging)
   {
     if (!ev || !staging) return MLGPU_ERR_INVALID;

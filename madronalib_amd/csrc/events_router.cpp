@@ -48,6 +48,7 @@ struct Router  // one instrument, one vector
     {
       hv.creatorKeyIdx = (size_t)keyIdx;
       hv.currentVelocity = e.value2;
+      er.setHeld(instIdx, v, e.value2 != 0.f);
       hv.nextFrame = dest;
       push(v, makeRec(vec, type == MLGPU_EVENT_NOTE_ON ? REC_NOTE_ON : REC_NOTE_RETRIG, e.time, (doGlide ? 1u : 0u) | (doReset ? 2u : 0u) | rewind, e.value1, e.value2));
     }
@@ -55,6 +56,7 @@ struct Router  // one instrument, one vector
     {
       hv.creatorKeyIdx = 0;
       hv.currentVelocity = 0.f;
+      er.setHeld(instIdx, v, false);
       hv.nextFrame = dest;
       push(v, makeRec(vec, REC_NOTE_OFF, e.time, rewind, 0.f, 0.f));
     }
@@ -233,6 +235,8 @@ EventRouter::EventRouter(size_t nInstruments, int polyphony) : inst(nInstruments
   int pow2 = 1;
   while (pow2 < polyphony + 1) pow2 <<= 1;
   laneRecs.resize(nInstruments * (size_t)pow2);
+  held.assign((nInstruments * (size_t)polyphony + 63) / 64, 0);
+  sounding.assign(held.size(), 0);
   unwatch();
   setProtocol(false);
   clear();  // setPolyphony calls clear() (:316-321)
@@ -262,13 +266,24 @@ void EventRouter::clear()
     for (HostVoice& v : in.voices) v = HostVoice();
     in.lastFreeVoiceFound = 0;
   }
+  std::fill(held.begin(), held.end(), (uint64_t)0);
+  ahead_ = false;
+  // the routed launch goes with the rest: its lane indices are the protocol's that routed it (setProtocol is followed by clear), and
+  // soundingVoices reads them
+  for (uint32_t l : dirtyLanes) laneRecs[l].clear();
+  dirtyLanes.clear();
+  for (uint32_t l : ctlDirty) ctlLaneRecs[l].clear();
+  ctlDirty.clear();
+  nRecs = nCtlRecs = 0;
 }
 
-void EventRouter::addEvent(size_t instrument, const mlgpu_event& e)
+bool EventRouter::addEvent(size_t instrument, const mlgpu_event& e)
 {
+  if (ahead_) return false;
   Instrument& in = inst[instrument];
   in.awake = true;
   in.events.insert(std::lower_bound(in.events.begin(), in.events.end(), e, soonerThan), e);
+  return true;
 }
 
 void EventRouter::clearEvents()
@@ -293,8 +308,41 @@ void EventRouter::watch(const int* numbers, int n)
   ctlLaneRecs.resize(ctlLanes());
 }
 
-void EventRouter::route(size_t nVectors, int startOffset)
+bool EventRouter::routeAhead(size_t nVectors, int startOffset)
 {
+  if (ahead_) return false;
+  route(nVectors, startOffset);
+  ahead_ = true;
+  aheadVectors = nVectors;
+  aheadOffset = startOffset;
+  return true;
+}
+
+bool EventRouter::soundingVoices(uint32_t* voices, size_t capacity, size_t* n) const
+{
+  *n = 0;
+  if (mpe_) return false;
+  sounding = held;  // (same size: no allocation)
+  const size_t nVoices = inst.size() * (size_t)polyphony_;  // (MIDI: a lane is a voice index; nothing else is ever set)
+  for (uint32_t l : dirtyLanes)
+    if (l < nVoices) sounding[l >> 6] |= (uint64_t)1 << (l & 63);
+  size_t count = 0;
+  for (uint64_t w : sounding) count += (size_t)__builtin_popcountll(w);
+  *n = count;
+  if (count > capacity) return false;
+  for (size_t i = 0; i < sounding.size(); ++i)
+    for (uint64_t w = sounding[i]; w; w &= w - 1) *voices++ = (uint32_t)(i * 64 + (size_t)__builtin_ctzll(w));
+  return true;
+}
+
+bool EventRouter::route(size_t nVectors, int startOffset)
+{
+  if (ahead_)  // routed already: the records stand as routeAhead left them
+  {
+    if (!aheadIs(nVectors, startOffset)) return false;
+    ahead_ = false;
+    return true;
+  }
   for (uint32_t l : dirtyLanes) laneRecs[l].clear();
   dirtyLanes.clear();
   for (uint32_t l : ctlDirty) ctlLaneRecs[l].clear();
@@ -329,6 +377,7 @@ void EventRouter::route(size_t nVectors, int startOffset)
   nRecs = nCtlRecs = 0;
   for (uint32_t l : dirtyLanes) nRecs += laneRecs[l].size();
   for (uint32_t l : ctlDirty) nCtlRecs += ctlLaneRecs[l].size();
+  return true;
 }
 
 void EventRouter::pack(Rec* dst, LaneRange* lanes) const

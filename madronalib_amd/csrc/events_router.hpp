@@ -67,7 +67,8 @@ class EventRouter
   void setModCC(int cc) { voiceModCC = cc; }
   void clear();  // EventsToSignals::clear, :330-340
 
-  void addEvent(size_t instrument, const mlgpu_event& e);  // addEvent, :367-372; instrument < instruments()
+  // addEvent, :367-372; instrument < instruments(). false, and nothing added: a launch routed ahead is pending (routeAhead)
+  bool addEvent(size_t instrument, const mlgpu_event& e);
   void clearEvents();
   int newestVoice(size_t instrument) const { return inst[instrument].newestVoice; }  // voices[] index (1..polyphony), -1: none yet
 
@@ -79,12 +80,25 @@ class EventRouter
 
   // Everything of processVector (:376-466) that happens on the host for nVectors DSPVectors starting at frame startOffset of the
   // event times: the block's events routed into per-lane records. Afterwards, until the next route():
-  void route(size_t nVectors, int startOffset);
+  // false, and nothing consumed: a launch routed ahead is pending and these are not its values (with them: its records stay, the
+  // launch is no longer pending).
+  bool route(size_t nVectors, int startOffset);
+  // route() now, for the launch to come: the host reads the records' consequences (soundingVoices) before that launch is made. Until
+  // a route() with the same values has taken the records over, addEvent and a second routeAhead are refused (false, nothing changed).
+  bool routeAhead(size_t nVectors, int startOffset);
+  bool aheadPending() const { return ahead_; }
+  bool aheadIs(size_t nVectors, int startOffset) const { return ahead_ && nVectors == aheadVectors && startOffset == aheadOffset; }
   size_t recordCount() const { return nRecs; }
   size_t dirtyLaneCount() const { return dirtyLanes.size(); }
   void pack(Rec* dst, LaneRange* lanes) const;  // recordCount() records grouped by lane, lanes ascending; dirtyLaneCount() ranges
   size_t ctlRecordCount() const { return nCtlRecs; }
   void packControllers(CtlRec* dst, uint32_t* recStart) const;  // ctlRecordCount() records; recStart[ctlLanes() + 1]
+  // The voices that sound in the routed launch, ascending, as voice indices instrument * polyphony + voice (MIDI protocol: the lane):
+  // every voice the launch holds a record for, and every voice whose held velocity is non-zero at the launch's end - so every voice
+  // whose gate is non-zero anywhere in the launch. The held voices are a bitmap kept where a note writes a velocity; the query costs
+  // the bitmap's words and the launch's lanes with records, not a walk over the voices. *n: the set's size, also when it is larger than
+  // `capacity` (false then, and nothing written). MIDI protocol only (false under MPE with *n = 0).
+  bool soundingVoices(uint32_t* voices, size_t capacity, size_t* n) const;
 
   void initialVoiceState(std::vector<uint32_t>& st) const;       // [kStateWords][lanes()]: freshly constructed / reset voices
   void initialControllerState(std::vector<uint32_t>& st) const;  // [kCtlWords][ctlLanes()]: smoothers settled on the current inputs
@@ -102,6 +116,18 @@ class EventRouter
   std::vector<std::vector<CtlRec>> ctlLaneRecs;
   std::vector<uint32_t> ctlDirty;
   size_t nRecs{0}, nCtlRecs{0};
+  bool ahead_{false};  // routeAhead's launch has not been taken over by route() yet
+  size_t aheadVectors{0};
+  int aheadOffset{0};
+  std::vector<uint64_t> held;             // bit v: HostVoice::currentVelocity of voice index v is non-zero
+  mutable std::vector<uint64_t> sounding;  // soundingVoices' scratch: held, and the lanes with records
+  void setHeld(size_t instrument, int voice, bool on)  // voices[] index 1..polyphony
+  {
+    if (voice < 1 || voice > polyphony_) return;
+    const size_t v = instrument * (size_t)polyphony_ + (size_t)(voice - 1);
+    if (on) held[v >> 6] |= (uint64_t)1 << (v & 63);
+    else held[v >> 6] &= ~((uint64_t)1 << (v & 63));
+  }
   void pushCtl(size_t instrument, int slot, uint32_t vec, uint32_t kind, float value)
   {
     const size_t l = (size_t)slot * inst.size() + instrument;

@@ -161,9 +161,11 @@ TestHooks readTestHooks()
 // 32 registers of LDS reads next to the voice's state every fourth quad, a spill there is paid in the loop, and its launches are the
 // sounding voices of a bank, not the bank (the config-5 voice, K = V / 8: 397 us at p50 bounded to four wavefronts with 168 bytes of
 // scratch, 278 us unbounded - profiles/graph_voice_list_groups.md).
+// So does either listed form of a graph with event rows (mlgpu_graph_enable_voice_list_events), for the second reason: its launches are
+// the voices that sound.
 bool generateBudgeted(const GraphDesc& d, const GraphPlan& p, KernelForm form, std::string& source, std::vector<char>& code, std::string& log)
 {
-  const long maxScratch = form.planned ? 0 : 640;
+  const long maxScratch = (form.planned || (form.listed && d.hasEventRows)) ? 0 : 640;
   form.minWaves = std::max(0, p.minWavesHook);
   source = generateGraphSource(d, p, form);
   if (!mlgpu_jit_code(source, code, log)) return false;
@@ -1196,7 +1198,16 @@ extern "C"
   {
     if (const int st = checkEditable(g, "graph_enable_voice_lists: before mlgpu_graph_compile")) return st;
     g->desc.voiceLists = on != 0;
-    if (!on) g->desc.voiceListGroups = false;
+    if (!on) g->desc.voiceListGroups = g->desc.voiceListEvents = false;
+    return MLGPU_OK;
+  }
+  // ... and a graph with event rows has a listed form as well (mlgpu_graph_process_events_listed[_groups]): CtlVoice of the gathered
+  // voice. on = 1 turns voice lists on too; mlgpu_graph_enable_voice_lists(g, 0) turns it off with the rest.
+  int mlgpu_graph_enable_voice_list_events(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_voice_list_events: before mlgpu_graph_compile")) return st;
+    g->desc.voiceListEvents = on != 0;
+    if (on) g->desc.voiceLists = true;
     return MLGPU_OK;
   }
   // ... and the listed form goes by the host's lane plan: the graph's group-summed outputs get one row per listed instrument
@@ -1340,9 +1351,9 @@ extern "C"
   static int signalArgs(mlgpu_graph* g, GraphArgs& a, const char* who, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls,
                         float* const* d_outputs, int outLayout)
   {
-    const std::string w = who;
-    if (inLayout < 0 || inLayout > MLGPU_LAYOUT_BROADCAST || outLayout < 0 || outLayout > MLGPU_LAYOUT_VOICE_MAJOR) return gfail(g, MLGPU_ERR_INVALID, w + ": bad layout");
-    if ((g->desc.nInputs && !d_inputs) || (g->desc.nControls && !d_controls) || !d_outputs) return gfail(g, MLGPU_ERR_INVALID, w + ": null signal list");
+    const auto name = [who] { return std::string(who); };  // (made where a refusal needs it: the success path allocates nothing)
+    if (inLayout < 0 || inLayout > MLGPU_LAYOUT_BROADCAST || outLayout < 0 || outLayout > MLGPU_LAYOUT_VOICE_MAJOR) return gfail(g, MLGPU_ERR_INVALID, name() + ": bad layout");
+    if ((g->desc.nInputs && !d_inputs) || (g->desc.nControls && !d_controls) || !d_outputs) return gfail(g, MLGPU_ERR_INVALID, name() + ": null signal list");
     memset(&a, 0, sizeof(a));
     a.coeffs = g->d_coeffs.get();
     a.state = g->d_state.get();
@@ -1356,17 +1367,17 @@ extern "C"
     a.impulseTable = g->e->d_impulseTable.get();
     for (int i = 0; i < g->desc.nInputs; ++i)
     {
-      if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, w + ": null / misaligned input");
+      if (!d_inputs[i] || ((uintptr_t)d_inputs[i] & 15)) return gfail(g, MLGPU_ERR_INVALID, name() + ": null / misaligned input");
       const int lay = (g->inLayoutOverride[i] >= 0) ? g->inLayoutOverride[i] : inLayout;
       a.in[i] = makeView(d_inputs[i], lay, g->desc.inputGroup[i] > 1 ? g->desc.V / (size_t)g->desc.inputGroup[i] : g->desc.V, T);
     }
     for (int i = 0; i < g->desc.nControls; ++i)
     {
-      if (!d_controls[i]) return gfail(g, MLGPU_ERR_INVALID, w + ": null control signal");
+      if (!d_controls[i]) return gfail(g, MLGPU_ERR_INVALID, name() + ": null control signal");
       a.ctl[i] = d_controls[i];
     }
     for (size_t o = 0; o < g->desc.outputs.size(); ++o)
-      if (!d_outputs[o] || ((uintptr_t)d_outputs[o] & 15)) return gfail(g, MLGPU_ERR_INVALID, w + ": null / misaligned output");
+      if (!d_outputs[o] || ((uintptr_t)d_outputs[o] & 15)) return gfail(g, MLGPU_ERR_INVALID, name() + ": null / misaligned output");
     return MLGPU_OK;
   }
 
@@ -1500,35 +1511,97 @@ extern "C"
   }
   size_t mlgpu_graph_voice_list_size(mlgpu_graph* g) { return (g && !g->job) ? g->list.size : 0; }
 
-  int mlgpu_graph_process_listed(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
-                                 int outLayout, uint32_t* d_peak)
+  // The events of a listed launch. The events object belongs to ALL voices: its host half and e2s_ctl_kernel run for every lane in
+  // every call - note state, the pitch and bend glides and the drift random walk advance for listed and unlisted voices alike -, the
+  // voice kernel then expands the control records of the listed voices only. eventOffset < 0: the call is not an events call.
+  // Before anything else of the call: what it refuses without looking at the block.
+  static int listedEventsReady(mlgpu_graph* g, const char* who0, int eventOffset)
   {
-    if (const int st = listsReady(g, "graph_process_listed")) return st;
+    const auto who = [who0] { return std::string(who0); };  // (made where a refusal needs it: the success path allocates nothing)
+    if (eventOffset < 0)
+      return g->desc.hasEventRows ? gfail(g, MLGPU_ERR_INVALID, who() + ": a graph with event rows is run with mlgpu_graph_process_events_listed[_groups]") : MLGPU_OK;
+    if (!g->events) return gfail(g, MLGPU_ERR_INVALID, who() + ": the graph has event rows but no events object (graph_bind_events)");
+    if (!mlgpu_events_is_midi(g->events)) return gfail(g, MLGPU_ERR_UNSUPPORTED, who() + ": events as graph source nodes: MIDI protocol only (one lane per voice)");
+    return MLGPU_OK;
+  }
+  // The first checks of the two events calls: the switch, the graph's event rows, the offset
+  static int listedEventsCall(mlgpu_graph* g, const char* who, int startOffset)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->desc.voiceListEvents)
+      return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph's event rows have no listed form - mlgpu_graph_enable_voice_list_events(g, 1) before compile");
+    if (!g->desc.hasEventRows) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": the graph has no event rows");
+    if (startOffset < 0) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": negative frame offset");
+    return MLGPU_OK;
+  }
+  // ... and once nothing of the call can be refused any more: the host half and e2s_ctl_kernel, on the engine's stream
+  static int listedEventsPrepare(mlgpu_graph* g, const char* who0, size_t T, int eventOffset, GraphArgs& a, void** staging)
+  {
+    const auto who = [who0] { return std::string(who0); };
+    *staging = nullptr;
+    if (eventOffset < 0) return MLGPU_OK;
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, &a.events, staging);
+    return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
+  }
+  // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)
+  static int listedEventsLaunched(mlgpu_graph* g, const char* who0, void* staging, hipError_t err)
+  {
+    const auto who = [who0] { return std::string(who0); };
+    if (staging && err != hipSuccess) mlgpu_events_abandoned_by_graph(g->events, staging);
+    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, who() + " launch: " + hipGetErrorString(err));
+    if (staging)
+      if (const int est = mlgpu_events_launched_by_graph(g->events, staging)) return gfail(g, est, who() + ": events bookkeeping after the launch");
+    return MLGPU_OK;
+  }
+
+  static int processListed(mlgpu_graph* g, const char* who, size_t T, int eventOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                           float* const* d_outputs, int outLayout, uint32_t* d_peak)
+  {
+    const auto w = [who] { return std::string(who); };  // (made where a refusal needs it: the success path allocates nothing)
+    if (const int st = listsReady(g, who)) return st;
     if (g->desc.voiceListGroups)
-      return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: the graph's listed kernel goes by the lane plan (mlgpu_graph_enable_voice_list_groups): mlgpu_graph_process_listed_groups runs it");
-    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed: misaligned peaks");
+      return gfail(g, MLGPU_ERR_INVALID, w() + ": the graph's listed kernel goes by the lane plan (mlgpu_graph_enable_voice_list_groups): mlgpu_" + w() + "_groups runs it");
+    if (const int st = listedEventsReady(g, who, eventOffset)) return st;
+    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, w() + ": misaligned peaks");
     if (T == 0) return MLGPU_OK;
+    if (eventOffset >= 0 && g->e->recording) return gfail(g, MLGPU_ERR_INVALID, w() + ": events route on the host: not while recording a sequence");
     GraphArgs a;
-    if (const int st = signalArgs(g, a, "graph_process_listed", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
+    if (const int st = signalArgs(g, a, who, T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     const size_t K = g->list.size;
     a.voiceList = g->list.d_list.get();
     a.listed = K;
     a.peaks = d_peak;
     // outputs by list position: K rows each; a mixed-down output is the tree of a K-voice graph
     if (const int st = outputViews(g, a, T, d_outputs, outLayout, K, 0,
-                                   "graph_process_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)"))
+                                   eventOffset < 0 ? "graph_process_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)"
+                                                   : "graph_process_events_listed: call mlgpu_graph_reserve_mixdown(graph, max vectors) at setup (process calls do not allocate)"))
       return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
-    if (K == 0)  // (nothing to launch; the sum of no voices: +0.0)
+    void* eventStaging = nullptr;
+    if (const int st = listedEventsPrepare(g, who, T, eventOffset, a, &eventStaging)) return st;
+    if (K == 0)  // (no voice kernel to launch; the sum of no voices: +0.0)
     {
+      if (const int st = listedEventsLaunched(g, who, eventStaging, hipSuccess)) return st;
       for (size_t o = 0; o < g->desc.outputs.size(); ++o)
         if (g->desc.outputMix[o] && hipMemsetAsync(d_outputs[o], 0, sizeof(float) * 64 * T, g->e->stream()) != hipSuccess)
-          return gfail(g, MLGPU_ERR_HIP, "graph_process_listed: clearing a mixed-down output");
+          return gfail(g, MLGPU_ERR_HIP, w() + ": clearing a mixed-down output");
       return MLGPU_OK;
     }
-    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream());
-    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed launch: ") + hipGetErrorString(err));
-    return mixdownStages(g, T, d_outputs, K, "graph_process_listed");
+    if (const int st = listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream()))) return st;
+    return mixdownStages(g, T, d_outputs, K, who);
+  }
+  int mlgpu_graph_process_listed(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
+                                 int outLayout, uint32_t* d_peak)
+  {
+    return processListed(g, "graph_process_listed", T, -1, d_inputs, inLayout, d_controls, d_outputs, outLayout, d_peak);
+  }
+  // a listed graph with event rows (mlgpu_graph_enable_voice_list_events): mlgpu_graph_process_events for the listed voices
+  int mlgpu_graph_process_events_listed(mlgpu_graph* g, size_t T, int startOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                                        float* const* d_outputs, int outLayout, uint32_t* d_peak)
+  {
+    if (const int st = listedEventsCall(g, "graph_process_events_listed", startOffset)) return st;
+    return processListed(g, "graph_process_events_listed", T, startOffset, d_inputs, inLayout, d_controls, d_outputs, outLayout, d_peak);
   }
 
   // ---- the listed voices with the group-summed outputs summed by instrument (voice_list.hpp plans the lanes, the planned form of the generated kernel runs them) ----
@@ -1550,30 +1623,44 @@ extern "C"
     return st == MLGPU_OK ? st : gfail(g, st, err);
   }
 
-  int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
-                                        int outLayout, uint32_t* d_peak)
+  static int processListedGroups(mlgpu_graph* g, const char* who, size_t T, int eventOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                                 float* const* d_outputs, int outLayout, uint32_t* d_peak)
   {
-    if (const int st = listsReady(g, "graph_process_listed_groups", true)) return st;
+    const auto w = [who] { return std::string(who); };  // (made where a refusal needs it: the success path allocates nothing)
+    if (const int st = listsReady(g, who, true)) return st;
     if (g->e->recording)
       return gfail(g, MLGPU_ERR_INVALID,
-                   "graph_process_listed_groups: not while recording a sequence - the launch's lane count and its rows go with the list's contents, not "
-                   "only its length, so a recorded launch could not follow a later list");
-    if (g->list.outGroup == 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed_groups: call mlgpu_graph_reserve_voice_list_groups(graph, max listed voices) at setup");
-    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, "graph_process_listed_groups: misaligned peaks");
+                   w() + ": not while recording a sequence - the launch's lane count and its rows go with the list's contents, not "
+                       "only its length, so a recorded launch could not follow a later list");
+    if (const int st = listedEventsReady(g, who, eventOffset)) return st;
+    if (g->list.outGroup == 0) return gfail(g, MLGPU_ERR_INVALID, w() + ": call mlgpu_graph_reserve_voice_list_groups(graph, max listed voices) at setup");
+    if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, w() + ": misaligned peaks");
     if (T == 0) return MLGPU_OK;
     GraphArgs a;
-    if (const int st = signalArgs(g, a, "graph_process_listed_groups", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
+    if (const int st = signalArgs(g, a, who, T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     const size_t K = g->list.size, N = g->list.planLanes, J = g->list.planGroups;
-    if (K == 0) return MLGPU_OK;  // (no listed instrument: no row to write)
+    if (K == 0 && eventOffset < 0) return MLGPU_OK;  // (no listed instrument: no row to write)
     a.listed = N;
     a.lanePlan = g->list.d_plan.get();
     a.peaks = d_peak;
     // a group-summed output: J rows, one per listed instrument; every other output: K rows by list position (none is mixed down: planGraph)
     if (const int st = outputViews(g, a, T, d_outputs, outLayout, K, J, "")) return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
-    const hipError_t err = mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream());
-    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, std::string("graph_process_listed_groups launch: ") + hipGetErrorString(err));
-    return MLGPU_OK;
+    void* eventStaging = nullptr;
+    if (const int st = listedEventsPrepare(g, who, T, eventOffset, a, &eventStaging)) return st;
+    if (K == 0) return listedEventsLaunched(g, who, eventStaging, hipSuccess);  // (the events object advanced; no voice kernel)
+    return listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream()));
+  }
+  int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
+                                        int outLayout, uint32_t* d_peak)
+  {
+    return processListedGroups(g, "graph_process_listed_groups", T, -1, d_inputs, inLayout, d_controls, d_outputs, outLayout, d_peak);
+  }
+  int mlgpu_graph_process_events_listed_groups(mlgpu_graph* g, size_t T, int startOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                                               float* const* d_outputs, int outLayout, uint32_t* d_peak)
+  {
+    if (const int st = listedEventsCall(g, "graph_process_events_listed_groups", startOffset)) return st;
+    return processListedGroups(g, "graph_process_events_listed_groups", T, startOffset, d_inputs, inLayout, d_controls, d_outputs, outLayout, d_peak);
   }
 }
 

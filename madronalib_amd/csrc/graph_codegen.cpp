@@ -512,6 +512,14 @@ struct GraphEmitter
         for (int in : R.ins)
           for (int l = 0; l < VL; ++l) s << "  float prev" << in << sfx(l) << " = 0.f;\n";
     // EventsToSignals rows made here from the control records of e2s_ctl_kernel: one CtlVoice per voice (lane == voice index: MIDI protocol)
+    // The listed forms (mlgpu_graph_enable_voice_list_events): v is the gathered voice - the control record, the two side signals and the
+    // drift glide's words are all addressed by it. Pads and lanes past the plan's or the list's end have left before CtlVoice's
+    // wave-uniform ballots. The spare lanes of a last wavefront (partialWaves: they run the list's - or the bank's - last voice again)
+    // are NOT masked: their CtlVoice stores are the last voice's own words with the same bits. Read from mldsp_events.hpp: every word
+    // CtlVoice stores (setGlideWord in quad() and store()) is a function of the words it loaded for voice v and of kernel arguments; the
+    // spare lanes sit in the last voice's wavefront and take every branch it takes (fetch, moving, rows are the same per-voice values), so
+    // a word's loads and stores are issued by the same instructions for all of them; and within a launch no word is loaded after it was
+    // stored except by a LATER instruction that wants the stored value (slot 63 and the first quad's slots at the next begin_vector).
     if (g.hasEventRows)
       for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
     // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
@@ -905,7 +913,8 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   // (three rings: layout 2 fits but leaves a CU one workgroup, and layout 1 is 9 % faster - profiles/r05_ring_layouts.txt)
   // a bank whose last wavefront is not full: its spare lanes run the last voice again (GraphEmitter) - not where voices are
   // summed in groups inside the kernel or read event records, which go by lane
-  bool groupedOrEvents = g.hasEventRows;
+  // (mlgpu_graph_enable_voice_list_events: the event rows go by voice - CtlVoice below - and a spare lane's are the last voice's)
+  bool groupedOrEvents = g.hasEventRows && !g.voiceListEvents;
   for (size_t o = 0; o < g.outputs.size(); ++o) groupedOrEvents = groupedOrEvents || g.outputGroup[o] != 0;
   const bool partialOk = g.V % 64 == 0 || !groupedOrEvents;
   if (p.rings == RingLayout::TRANSPOSED && p.totalRings && !partialOk)
@@ -987,7 +996,8 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
         return fail(MLGPU_ERR_UNSUPPORTED, who + "an output group sum (mlgpu_graph_set_output_group_sum) has no listed form without the lane plan: mlgpu_graph_enable_voice_list_groups(g, 1)");
       if (g.outputMixShard[o]) return fail(MLGPU_ERR_UNSUPPORTED, who + "the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2)) has no listed form");
     }
-    if (g.hasEventRows) return fail(MLGPU_ERR_UNSUPPORTED, who + "event rows (mlgpu_graph_add_event_row) go by lane, not by voice: no listed form");
+    if (g.hasEventRows && !g.voiceListEvents)
+      return fail(MLGPU_ERR_UNSUPPORTED, who + "event rows (mlgpu_graph_add_event_row) go by lane, not by voice: no listed form (mlgpu_graph_enable_voice_list_events(g, 1) makes one)");
     for (const Region& R : g.regions)
       if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X)
         return fail(MLGPU_ERR_UNSUPPORTED, who + "a DOWNSAMPLE_2X region pairs DSPVectors by the graph's count, not by a voice's: no listed form");

@@ -105,6 +105,7 @@ struct GraphDesc
   bool autotune{false};
   bool voiceLists{false};        // a compile makes the listed form of the kernel too (mlgpu_graph_enable_voice_lists)
   bool voiceListGroups{false};   // ... and that form goes by the host's lane plan, its group-summed outputs one row per listed instrument (mlgpu_graph_enable_voice_list_groups)
+  bool voiceListEvents{false};   // ... and a graph with event rows has it too: CtlVoice of the gathered voice (mlgpu_graph_enable_voice_list_events)
 };
 
 // Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them by planGraph)
