@@ -1195,17 +1195,49 @@ int mlgpu_graph_reserve_mixdown(mlgpu_graph* g, size_t max_vectors);
  * the block's frame offset (what mlgpu_events_process takes), then mlgpu_events_clear_events as usual. A block may be processed
  * by either call: both leave the state the other expects (rows a call does not compute keep their glides where they are, as
  * with mlgpu_events_set_wanted_rows).
+ *
+ * THE ROWS vox, z, x, y AND mod (2..6) are source nodes the same way: what a voice reads that follows the mod wheel, aftertouch, the
+ * x / y controllers or its voice number. For every voice and sample the node has the bits of the same row of mlgpu_events_process on an
+ * object in the same state: vox is the voice's number in its instrument (present before the first event too); z, x, y and mod are the
+ * 20 ms LinearGlides of the reference (z with the velocity-0 rule of :246-250 and, MIDI protocol, the smoothed channel pressure added),
+ * zero while the instrument is not awake. The CONTROL kernel owns these glides: it runs them once per voice and DSPVector, writes one
+ * held value per row - and the 64 frames of a row to that row's side signal for the ~15 vectors after a controller event in which the
+ * glide moves -, and the voice kernel only reads. A glide is advanced by a call only if its row is a node of the graph that makes the
+ * call (rows the graph does not have keep their glides where they are); either form hands over to the other in the middle of a moving
+ * glide with the bits of never having switched. The elapsed-time row (7) moves every sample and is refused (MLGPU_ERR_UNSUPPORTED), a
+ * row added twice is MLGPU_ERR_INVALID. A graph whose only event rows are among 2..6 is an events graph like any other
+ * (mlgpu_graph_bind_events, mlgpu_graph_process_events, the refusal of mlgpu_graph_process).
  */
-int mlgpu_graph_add_event_row(mlgpu_graph* g, int row /* 0 pitch, 1 gate */, const char* name); /* before compile; node id */
+typedef enum mlgpu_event_row /* VoiceOutputSignals, MLEventsToSignals.h:15-26: the order of mlgpu_events_process' outputs */
+{
+  MLGPU_EVENT_ROW_PITCH = 0,
+  MLGPU_EVENT_ROW_GATE = 1,
+  MLGPU_EVENT_ROW_VOX = 2,
+  MLGPU_EVENT_ROW_Z = 3,
+  MLGPU_EVENT_ROW_X = 4,
+  MLGPU_EVENT_ROW_Y = 5,
+  MLGPU_EVENT_ROW_MOD = 6,
+  MLGPU_EVENT_ROW_TIME = 7 /* not a source node */
+} mlgpu_event_row;
+int mlgpu_graph_add_event_row(mlgpu_graph* g, int row /* mlgpu_event_row, 0..6 */, const char* name); /* before compile; node id */
 int mlgpu_graph_bind_events(mlgpu_graph* g, mlgpu_events* ev);
 /* Device memory of the two-launch form, per voice and DSPVector of the longest block: a 16-byte control record + 2 x 256 bytes of side
  * signal (only the flagged vectors' frames are ever written or read, but the buffers are addressed [vector][voice]) = 528 bytes:
- * 2.2 GB for 262 144 voices x 16 DSPVectors (mlgpu_events_graph_reserve_bytes says it for an object). Reserve it at SETUP with
+ * 2.2 GB for 262 144 voices x 16 DSPVectors (mlgpu_events_graph_reserve_bytes says it for an object). Each of the rows z, x, y, mod a
+ * graph reads adds 4 bytes (its held value) + 256 bytes (its side signal) = 260; vox adds nothing. Reserve it at SETUP with
  * mlgpu_events_reserve_for_graph(ev, longest block in DSPVectors): from then on mlgpu_graph_process_events never allocates and
  * answers MLGPU_ERR_RANGE to a longer block (before the router consumes its events). Without a reserve the first block - and any
- * longer one later - waits for the stream and allocates inside the process call (fine for tools and tests, not for an audio thread). */
+ * longer one later, or one of a graph with more rows - waits for the stream and allocates inside the process call (fine for tools and
+ * tests, not for an audio thread).
+ * The _rows forms take the rows the bound graphs will read: bit r of row_mask = row r; bits 0 and 1 are always implied; a mask with
+ * bit 7 or a higher one is MLGPU_ERR_UNSUPPORTED (reserve_bytes_rows: 0). The forms without a mask are those of mask 3. After a
+ * reserve, a process call of a graph with a row outside the reserved mask answers MLGPU_ERR_INVALID and names the row - like the
+ * MLGPU_ERR_RANGE of a longer block before the router consumes the block's events (mlgpu_events_route_ahead cannot know the graph and
+ * does not make this check: the routed launch stays pending for a graph the reserve covers). */
 int mlgpu_events_reserve_for_graph(mlgpu_events* ev, size_t max_vectors);
 size_t mlgpu_events_graph_reserve_bytes(mlgpu_events* ev, size_t max_vectors);
+int mlgpu_events_reserve_for_graph_rows(mlgpu_events* ev, size_t max_vectors, unsigned row_mask);
+size_t mlgpu_events_graph_reserve_bytes_rows(mlgpu_events* ev, size_t max_vectors, unsigned row_mask);
 int mlgpu_graph_process_events(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
                                const float* const* d_controls, float* const* d_outputs, int out_layout);
 
@@ -1233,6 +1265,9 @@ int mlgpu_graph_process_events(mlgpu_graph* g, size_t n_vectors, int start_offse
  *   The one thing that does not advance for an unlisted voice is the drift LinearGlide the voice kernel owns (glide 5 of the events
  *   state: mCurrVec and five words). Those words are neither read nor written; a relisted voice glides from where it stood to the
  *   current drift value. (Exact would cost 8 bytes per unlisted voice-sample - what the list exists to avoid.)
+ *   The rows vox, z, x, y and mod are NOT like that: their glides belong to the control kernel, which runs for every lane in every call,
+ *   and the voice kernel only reads them. A relisted voice's rows 2..6 have the exact bits of never having used lists from its first
+ *   listed vector on, whatever the drift amount.
  *   After listed blocks a block may still be processed by mlgpu_events_process or mlgpu_graph_process_events; with drift amount 0 the
  *   bits are those of never having used lists.
  *   Statuses, all before the router consumes the block's events: MLGPU_ERR_INVALID naming the switch on a graph built without it; the

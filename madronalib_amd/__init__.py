@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .constants import FLOATS_PER_DSPVECTOR, Layout, Op, Proc, Region, Route, RowOp, RowsRule, Status, UpdateTarget, Vop
+from .constants import FLOATS_PER_DSPVECTOR, EventRow, Layout, Op, Proc, Region, Route, RowOp, RowsRule, Status, UpdateTarget, Vop
 
 __all__ = ["Engine", "Bank", "Graph", "Update", "UpdateTarget", "DSPBuffer", "ProcessBuffer", "Resampler", "Events", "Event", "EventType", "jit_selftest", "DeviceBuffer", "MlgpuError", "Layout", "Op", "Proc", "RowOp", "Status", "Vop", "Route", "RowsRule", "Allpass1", "FractionalDelay", "LinearGlide", "SampleAccurateLinearGlide",
            "Lopass", "Hipass", "Bandpass", "LoShelf", "HiShelf", "Bell", "OnePole", "DCBlocker", "ADSR",
@@ -691,13 +691,20 @@ class Events(_Handle):
         self.engine._check(self.L.mlgpu_events_sounding_voices(self.h, _np_ptr(self._sounding), self._sounding.size, ctypes.byref(n)))
         return self._sounding[:n.value].copy()
 
-    def reserve_for_graph(self, max_vectors):
+    def reserve_for_graph(self, max_vectors, rows=None):
         """Setup-time reserve of the control records and side signals a graph bound to this object needs for blocks of up to max_vectors
-        DSPVectors (mlgpu_events_reserve_for_graph): from then on Graph.process_events never allocates and refuses longer blocks."""
-        self.engine._check(self.L.mlgpu_events_reserve_for_graph(self.h, int(max_vectors)))
+        DSPVectors (mlgpu_events_reserve_for_graph): from then on Graph.process_events never allocates and refuses longer blocks.
+        rows: the event rows (constants.EventRow) the bound graphs read (mlgpu_events_reserve_for_graph_rows; pitch and gate are always
+        implied): a graph with a row outside them is refused too. None: pitch and gate only."""
+        if rows is None:
+            self.engine._check(self.L.mlgpu_events_reserve_for_graph(self.h, int(max_vectors)))
+        else:
+            self.engine._check(self.L.mlgpu_events_reserve_for_graph_rows(self.h, int(max_vectors), sum(1 << int(r) for r in set(rows))))
 
-    def graph_reserve_bytes(self, max_vectors):
-        return int(self.L.mlgpu_events_graph_reserve_bytes(self.h, int(max_vectors)))
+    def graph_reserve_bytes(self, max_vectors, rows=None):
+        if rows is None:
+            return int(self.L.mlgpu_events_graph_reserve_bytes(self.h, int(max_vectors)))
+        return int(self.L.mlgpu_events_graph_reserve_bytes_rows(self.h, int(max_vectors), sum(1 << int(r) for r in set(rows))))
 
     def watch_controllers(self, numbers, max_vectors):
         """The smoothed controller signals (AudioContext::getInputController) to make from now on, one per instrument per number,
@@ -1453,7 +1460,7 @@ class Graph(_Handle):
         if type == "control":
             self.controls.append(name)
             return self._ret(self.L.mlgpu_graph_add_control(self.h, bname), name)
-        if type == "event_row":   # kind: 0 pitch, 1 gate of the Events object bound with bind_events()
+        if type == "event_row":   # kind: constants.EventRow, 0 pitch .. 6 mod, of the Events object bound with bind_events()
             return self._ret(self.L.mlgpu_graph_add_event_row(self.h, int(kind), bname), name)
         if type == "vop":
             return self._ret(self.L.mlgpu_graph_add_vop(self.h, int(kind), arr, len(ins), bname), name)

@@ -23,6 +23,17 @@ class Layout:
     BROADCAST = 3    # [S] one voice's stream read by every voice (inputs only)
 
 
+class EventRow:      # mlgpu_event_row: the rows of Events.process, and - all but TIME - the kinds of a graph's "event_row" node
+    PITCH = 0
+    GATE = 1
+    VOX = 2
+    Z = 3
+    X = 4
+    Y = 5
+    MOD = 6
+    TIME = 7
+
+
 class _RingTargets:   # the targets of mlgpu_update_target that write delay-ring memory beside the tables
     CLEAR_RINGS = 5   # MLGPU_UPDATE_CLEAR + 1
 

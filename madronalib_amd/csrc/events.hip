@@ -579,12 +579,66 @@ struct E2SCtlArgs
   uint32_t* ctl;   // [T][kCtlRecWords][lanes]
   float4* rowP;    // QUAD [16 T][lanes][4], written for CF_ROWS vectors only
   float4* rowG;
+  // ROWS: the controller rows a graph reads (EventsDev::held / rowC / ctlRowMask: bits 3..6)
+  uint32_t* held;  // [T][rows of rowMask, ascending][lanes]
+  float4* rowC[4]; // z, x, y, mod: QUAD, written for CF_ROW(r) vectors only
+  uint32_t rowMask;
   size_t lanes, T;
   uint32_t flags;
   E2SSettings s;
 };
 
-__global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
+// The 64 frames of a glide that moves inside the vector, into its row's side signal (what e2s_kernel's glideRow writes to the row
+// itself). Out of line: it runs for the few vectors after a controller event, and inlined four times its address arithmetic took
+// e2s_ctl_rows_kernel's per-vector path past every register there is.
+__device__ __noinline__ void ctl_glide_frames(const Glide& gl, uint32_t* gs, size_t ln, float4* out)
+{
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  f32x4* o = (f32x4*)out;
+  float nx[4] = {0.f, 0.f, 0.f, 0.f};
+  gl.preload(gs, ln, 0, nx);
+#pragma unroll 1
+  for (int q = 0; q < 16; ++q, o += ln)
+  {
+    const float cur[4] = {nx[0], nx[1], nx[2], nx[3]};
+    if (q < 15) gl.preload(gs, ln, q + 1, nx);
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = gl.nextWith(gs, ln, q * 4 + k, cur[k]);
+    __builtin_nontemporal_store(v, o);
+  }
+}
+// ... and of z: its own glide plus the smoothed channel pressure (:437-445, MIDI protocol), as e2s_kernel adds them
+__device__ __noinline__ void ctl_z_frames(const Glide& gz, const Glide& gp, uint32_t* gsz, uint32_t* gsp, size_t ln, float4* out)
+{
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  f32x4* o = (f32x4*)out;
+#pragma unroll 1
+  for (int q = 0; q < 16; ++q, o += ln)
+  {
+    float cz4[4] = {0.f, 0.f, 0.f, 0.f}, cp4[4] = {0.f, 0.f, 0.f, 0.f};
+    gz.preload(gsz, ln, q, cz4);
+    gp.preload(gsp, ln, q, cp4);
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      float z = gz.nextWith(gsz, ln, q * 4 + k, cz4[k]);
+      const float press = gp.nextWith(gsp, ln, q * 4 + k, cp4[k]);
+      z = z + press;
+      v[k] = z;
+    }
+    __builtin_nontemporal_store(v, o);
+  }
+}
+
+// ROWS: the graph reads some of the rows z, x, y, mod (a.rowMask). Their glides - 1 mod, 2 x, 3 y, 4 z with 6, the smoothed channel
+// pressure - are run here as e2s_kernel's glideRow runs them, once per vector and lane: a glide that is held gives ONE word (the plane
+// a.held), one that moves inside the vector its 64 frames in the row's side signal and CF_ROW(r) in the vector's flags. A row outside
+// a.rowMask keeps its glide where it is (mlgpu_events_set_wanted_rows' rule). The instance without ROWS is the kernel of a graph
+// that reads pitch and gate only: none of this is in its code.
+template <bool ROWS>
+__device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
 {
   apply_fp_mode(a.flags);
   size_t blk = blockIdx.x;
@@ -606,6 +660,30 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
   int32_t driftCounter = (int32_t)SW(S_DRIFT_COUNTER), driftNext = (int32_t)SW(S_DRIFT_NEXT);
   float driftValue = u2f(SW(S_DRIFT_VALUE));
   // controller values that only pass through (their rows are not computed by this form): kept current as mlgpu_events_set_wanted_rows does
+  // (ROWS: they feed this vector's glides, so they live in registers and go back to memory at the end)
+  [[maybe_unused]] float mod = 0.f, cx = 0.f, cy = 0.f, chanPress = 0.f;
+  if constexpr (ROWS)
+  {
+    mod = u2f(SW(S_MOD)), cx = u2f(SW(S_X)), cy = u2f(SW(S_Y)), chanPress = u2f(SW(S_CHANPRESS));
+  }
+#define GS(i) (S + (size_t)(S_GLIDES + (i) * kGlideWords) * ln)
+  [[maybe_unused]] const int nHeld = ROWS ? ctl_row_count(a.rowMask) : 0;
+  // ROWS: the wanted rows' glides (1 mod, 2 x, 3 y, 4 z, 6 channel pressure) live in registers for the whole launch, as the bend glide
+  // does: one load and one store per launch, where a load per vector stands behind the vector's stores and waits out their
+  // acknowledgement. (A moving glide's mCurrVec slots stay in memory: ctl_glide_frames - the walk of such a glide is what this kernel's
+  // time is made of, profiles/graph_event_rows.md.)
+  [[maybe_unused]] Glide gm, gx, gy, gz, gp;
+  if constexpr (ROWS)
+  {
+    if (a.rowMask & (1u << 6)) gm.load(GS(1), ln);
+    if (a.rowMask & (1u << 4)) gx.load(GS(2), ln);
+    if (a.rowMask & (1u << 5)) gy.load(GS(3), ln);
+    if (a.rowMask & (1u << 3))
+    {
+      gz.load(GS(4), ln);
+      gp.load(GS(6), ln);
+    }
+  }
   uint32_t* GB = S + (size_t)(S_GLIDES + 0 * kGlideWords) * ln;
   Glide gb;
   gb.load(GB, ln);
@@ -641,11 +719,11 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
         switch (rc.typeTimeFlags & 0xFF)
         {
           case REC_SET_BEND: bend = rc.v1; break;
-          case REC_SET_MOD: SW(S_MOD) = f2u(rc.v1); break;
-          case REC_SET_X: SW(S_X) = f2u(rc.v1); break;
-          case REC_SET_Y: SW(S_Y) = f2u(rc.v1); break;
+          case REC_SET_MOD: if constexpr (ROWS) mod = rc.v1; else SW(S_MOD) = f2u(rc.v1); break;
+          case REC_SET_X: if constexpr (ROWS) cx = rc.v1; else SW(S_X) = f2u(rc.v1); break;
+          case REC_SET_Y: if constexpr (ROWS) cy = rc.v1; else SW(S_Y) = f2u(rc.v1); break;
           case REC_SET_Z: cz = rc.v1; break;
-          case REC_SET_CHANNEL_PRESSURE: SW(S_CHANPRESS) = f2u(rc.v1); break;
+          case REC_SET_CHANNEL_PRESSURE: if constexpr (ROWS) chanPress = rc.v1; else SW(S_CHANPRESS) = f2u(rc.v1); break;
           case REC_NOTE_ON: case REC_NOTE_RETRIG: finalVelocity = rc.v2; noteHere = true; break;
           case REC_NOTE_OFF: finalVelocity = 0.f; noteHere = true; break;
           default: break;
@@ -769,10 +847,65 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
         __builtin_nontemporal_store(vG, oG);
       }
     }
+    uint32_t rowFlags = 0u;
+    if constexpr (ROWS)
+    {
+      // ---- the rows that are one glide each: mod, x, y; z adds the smoothed channel pressure (:437-445, MIDI protocol) ----
+      uint32_t* const hw = a.held + (t * (size_t)nHeld) * ln + lane;
+      auto heldValue = [&](const Glide& gl, bool& held) {
+        const int m = gl.mode();
+        held = (m == 1) || (m == 0 && gl.isUniform());
+        return (m == 1) ? gl.target : gl.uniformValue;
+      };
+      auto glideRow = [&](Glide& gl, int glideIdx, int row, float value) {
+        uint32_t* const gs = GS(glideIdx);
+        if (on) gl.beginVector(gs, ln, value, a.s.glideVectors, a.s.glideDy);
+        bool held;
+        const float hv = heldValue(gl, held);
+        if (on && !held)
+        {
+          ctl_glide_frames(gl, gs, ln, a.rowC[row - 3] + (t * 16) * ln + lane);
+          rowFlags |= CF_ROW(row);
+        }
+        hw[(size_t)ctl_row_rank(a.rowMask, row) * ln] = f2u((on && held) ? hv : 0.f);
+        if (on) gl.endVector();
+      };
+      if (a.rowMask & (1u << 6)) glideRow(gm, 1, 6, mod);
+      if (a.rowMask & (1u << 4)) glideRow(gx, 2, 4, cx);
+      if (a.rowMask & (1u << 5)) glideRow(gy, 3, 5, cy);
+      if (a.rowMask & (1u << 3))
+      {
+        if (on)
+        {
+          gz.beginVector(GS(4), ln, cz, a.s.glideVectors, a.s.glideDy);
+          gp.beginVector(GS(6), ln, chanPress, a.s.ctlGlideVectors, a.s.ctlGlideDy);  // SmoothedController::process, :268-280
+        }
+        bool heldZ, heldP;
+        const float hz = heldValue(gz, heldZ), hp = heldValue(gp, heldP);
+        const bool held = heldZ && heldP;
+        float zv = 0.f;
+        if (on && !held)
+        {
+          ctl_z_frames(gz, gp, GS(4), GS(6), ln, a.rowC[0] + (t * 16) * ln + lane);
+          rowFlags |= CF_ROW(3);
+        }
+        else if (on)
+        {
+          zv = hz;
+          zv = zv + hp;
+        }
+        hw[(size_t)ctl_row_rank(a.rowMask, 3) * ln] = f2u(zv);
+        if (on)
+        {
+          gz.endVector();
+          gp.endVector();
+        }
+      }
+    }
     rec[0] = f2u(P);
     rec[ln] = f2u(gate);
     rec[2 * ln] = f2u(driftValue);
-    rec[3 * ln] = (on ? CF_ON : 0u) | ((walk || glideOnly) ? CF_ROWS : 0u) | (walk ? CF_GATE_ROW : 0u);
+    rec[3 * ln] = (on ? CF_ON : 0u) | ((walk || glideOnly) ? CF_ROWS : 0u) | (walk ? CF_GATE_ROW : 0u) | rowFlags;
     if (on) gb.endVector();
     if (vend != cursor)
     {
@@ -793,8 +926,25 @@ __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a)
   SW(S_PG_CURR) = f2u(pg.curr); SW(S_PG_STEP) = f2u(pg.step); SW(S_PG_TARGET) = f2u(pg.target); SW(S_PG_REMAINING) = (uint32_t)pg.remaining;
   SW(S_PG_PER_GLIDE) = (uint32_t)pg.perGlide; SW(S_PG_DY) = f2u(pg.dyPerSample);
   SW(S_DRIFT_SEED) = driftSeed; SW(S_DRIFT_COUNTER) = (uint32_t)driftCounter; SW(S_DRIFT_VALUE) = f2u(driftValue); SW(S_DRIFT_NEXT) = (uint32_t)driftNext;
+  if constexpr (ROWS)
+  {
+    SW(S_MOD) = f2u(mod); SW(S_X) = f2u(cx); SW(S_Y) = f2u(cy); SW(S_CHANPRESS) = f2u(chanPress);
+    if (a.rowMask & (1u << 6)) gm.store(GS(1), ln);
+    if (a.rowMask & (1u << 4)) gx.store(GS(2), ln);
+    if (a.rowMask & (1u << 5)) gy.store(GS(3), ln);
+    if (a.rowMask & (1u << 3))
+    {
+      gz.store(GS(4), ln);
+      gp.store(GS(6), ln);
+    }
+  }
+#undef GS
 #undef SW
 }
+// (two kernels rather than one template: the instance with the controller rows is bounded to two wavefronts per SIMD - left to itself
+// it takes every register there is for the unrolled glide loops and runs one -, the pitch/gate instance keeps the attributes it had)
+__global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a) { e2s_ctl_body<false>(a); }
+__global__ __launch_bounds__(256, 2) void e2s_ctl_rows_kernel(const E2SCtlArgs a) { e2s_ctl_body<true>(a); }
 
 // ---- smoothed controller signals: one lane per (watched controller slot, instrument); CtlRec and the C_* state words are in
 // mlev_format.hpp -------------------------------------------------------------------------------------------------------------
@@ -920,8 +1070,12 @@ struct mlgpu_events
   DeviceBuffer<uint32_t> d_ctlRecs;
   DeviceBuffer<float> d_rowP;
   DeviceBuffer<float> d_rowG;
+  // ... and for the controller rows z, x, y, mod of ctlRowMask (bits 3..6): the plane of held values [T][rows][lanes], a side signal each
+  DeviceBuffer<uint32_t> d_held;
+  DeviceBuffer<float> d_rowC[4];
+  uint32_t ctlRowMask{0};
   size_t ctlRecVectors{0};
-  bool ctlRecReserved{false};  // mlgpu_events_reserve_for_graph was called: process calls never allocate, longer blocks are refused
+  bool ctlRecReserved{false};  // mlgpu_events_reserve_for_graph[_rows] was called: process calls never allocate, longer blocks and rows outside the mask are refused
 };
 
 void mlgpu_graph_forget_events(mlgpu_events* ev);  // graph.hip
@@ -955,6 +1109,7 @@ E2SSettings deviceSettings(const mlgpu_events* ev)
   memcpy(&s.ctlGlideVectors, &c[0], 4);
   s.ctlGlideDy = c[1];
   s.mpe = ev->router.mpe() ? 1 : 0;
+  s.polyphony = ev->router.polyphony();
   return s;
 }
 
@@ -1214,6 +1369,9 @@ extern "C"
     }
     dev.ctl = nullptr;
     dev.rowP = dev.rowG = nullptr;
+    dev.held = nullptr;
+    for (const float4*& r : dev.rowC) r = nullptr;
+    dev.ctlRowMask = 0;
     dev.state = ev->d_state.get();
     dev.recs = sg.d_recs.get();
     dev.recRange = ev->d_recRange.get();
@@ -1271,49 +1429,66 @@ extern "C"
   }
 
   // control records [T][kCtlRecWords][lanes] + the two side signals [64 T][lanes] of e2s_ctl_kernel for blocks of up to nVectors
-  static int reserveCtlRecs(mlgpu_events* ev, size_t nVectors)
+  // ... and, for each of the rows z, x, y, mod in rowMask (bits 3..6), a held word [T][lanes] and a side signal [64 T][lanes]
+  static int reserveCtlRecs(mlgpu_events* ev, size_t nVectors, uint32_t rowMask)
   {
     mlgpu_engine* e = ev->e;
     const size_t lanes = ev->router.lanes();
+    rowMask &= kCtlRowsMask;
     if (hipSetDevice(e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     hipStreamSynchronize(e->stream());
     // recorded graph launches have these pointers baked in: the old buffers are retired, the new ones serve from now on
     e->retire(std::move(ev->d_ctlRecs));
     e->retire(std::move(ev->d_rowP));
     e->retire(std::move(ev->d_rowG));
+    e->retire(std::move(ev->d_held));
+    for (DeviceBuffer<float>& b : ev->d_rowC) e->retire(std::move(b));
     ev->ctlRecVectors = 0;
-    if (allocate(ev->d_ctlRecs, kCtlRecWords * nVectors * lanes) != hipSuccess || allocate(ev->d_rowP, 64 * nVectors * lanes) != hipSuccess ||
-        allocate(ev->d_rowG, 64 * nVectors * lanes) != hipSuccess)
+    ev->ctlRowMask = 0;
+    bool ok = allocate(ev->d_ctlRecs, kCtlRecWords * nVectors * lanes) == hipSuccess && allocate(ev->d_rowP, 64 * nVectors * lanes) == hipSuccess &&
+              allocate(ev->d_rowG, 64 * nVectors * lanes) == hipSuccess;
+    if (ok && rowMask) ok = allocate(ev->d_held, (size_t)ctl_row_count(rowMask) * nVectors * lanes) == hipSuccess;
+    for (int r = 3; ok && r <= 6; ++r)
+      if ((rowMask >> r) & 1u) ok = allocate(ev->d_rowC[r - 3], 64 * nVectors * lanes) == hipSuccess;
+    if (!ok)
     {
       ev->d_ctlRecs.reset();
       ev->d_rowP.reset();
       ev->d_rowG.reset();
+      ev->d_held.reset();
+      for (DeviceBuffer<float>& b : ev->d_rowC) b.reset();
       return efail(ev, MLGPU_ERR_OOM, "events as graph source nodes: control records and side signals");
     }
     ev->ctlRecVectors = nVectors;
+    ev->ctlRowMask = rowMask;
     return MLGPU_OK;
   }
-  int mlgpu_events_reserve_for_graph(mlgpu_events* ev, size_t maxVectors)
+  int mlgpu_events_reserve_for_graph_rows(mlgpu_events* ev, size_t maxVectors, unsigned rowMask)
   {
     if (!ev || maxVectors == 0) return MLGPU_ERR_INVALID;
+    if (rowMask & ~0x7Fu) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events_reserve_for_graph_rows: rows 0 (pitch) to 6 (mod) can be source nodes of a graph");
     if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_reserve_for_graph allocates: not while recording a sequence");
     if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
-    if (maxVectors != ev->ctlRecVectors)
+    if (maxVectors != ev->ctlRecVectors || (rowMask & kCtlRowsMask) != ev->ctlRowMask)
     {
-      const int st = reserveCtlRecs(ev, maxVectors);
+      const int st = reserveCtlRecs(ev, maxVectors, rowMask);
       if (st != MLGPU_OK) return st;
     }
     ev->ctlRecReserved = true;
     return MLGPU_OK;
   }
-  size_t mlgpu_events_graph_reserve_bytes(mlgpu_events* ev, size_t maxVectors)
+  int mlgpu_events_reserve_for_graph(mlgpu_events* ev, size_t maxVectors) { return mlgpu_events_reserve_for_graph_rows(ev, maxVectors, 3u); }
+  size_t mlgpu_events_graph_reserve_bytes_rows(mlgpu_events* ev, size_t maxVectors, unsigned rowMask)
   {
-    if (!ev) return 0;
-    return (sizeof(uint32_t) * kCtlRecWords + 2 * sizeof(float) * 64) * maxVectors * ev->router.lanes();
+    if (!ev || (rowMask & ~0x7Fu)) return 0;
+    const size_t perRow = sizeof(uint32_t) + sizeof(float) * 64;  // a held word and 64 frames of side signal
+    return (sizeof(uint32_t) * kCtlRecWords + 2 * sizeof(float) * 64 + perRow * (size_t)ctl_row_count(rowMask)) * maxVectors * ev->router.lanes();
   }
+  size_t mlgpu_events_graph_reserve_bytes(mlgpu_events* ev, size_t maxVectors) { return mlgpu_events_graph_reserve_bytes_rows(ev, maxVectors, 3u); }
 
   // for graph.hip: a graph whose event rows are bound to this object (mlgpu_graph_bind_events)
-  int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, EventsDev* dev, void** staging)
+  // rowMask: the graph's event rows (bit r = row r; only z, x, y, mod - bits 3..6 - need memory and work of their own here)
+  int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, unsigned rowMask, EventsDev* dev, void** staging)
   {
     if (!ev || !dev || !staging) return MLGPU_ERR_INVALID;
     if (nVectors == 0) return MLGPU_OK;
@@ -1325,11 +1500,19 @@ extern "C"
     // the control records and the two side signals of e2s_ctl_kernel: sized by mlgpu_events_reserve_for_graph at setup. An object that
     // was never reserved grows them here on the first / a longer block (a setup-time convenience: it waits for the stream and allocates);
     // once a host has reserved, a longer block is refused before the router consumes its events and nothing is ever allocated here.
-    if (nVectors > ev->ctlRecVectors)
+    // The same goes for the rows: a graph with a controller row outside the reserved mask is refused here, an unreserved object grows.
+    const uint32_t ctlRows = rowMask & kCtlRowsMask, missing = ctlRows & ~ev->ctlRowMask;
+    if (nVectors > ev->ctlRecVectors || missing)
     {
-      if (ev->ctlRecReserved)
+      if (ev->ctlRecReserved && nVectors > ev->ctlRecVectors)
         return efail(ev, MLGPU_ERR_RANGE, "graph_process_events: more DSPVectors than mlgpu_events_reserve_for_graph reserved the control records for");
-      const int rst = reserveCtlRecs(ev, nVectors);
+      if (ev->ctlRecReserved)
+      {
+        static const char* const names[] = {"3 (z)", "4 (x)", "5 (y)", "6 (mod)"};
+        return efail(ev, MLGPU_ERR_INVALID, std::string("graph_process_events: the graph reads event row ") + names[__builtin_ctz(missing) - 3] +
+                                                ", which is outside the row mask of mlgpu_events_reserve_for_graph_rows");
+      }
+      const int rst = reserveCtlRecs(ev, std::max(nVectors, ev->ctlRecVectors), ctlRows | ev->ctlRowMask);
       if (rst != MLGPU_OK) return rst;
     }
     mlgpu_events::Staging* sg = nullptr;
@@ -1340,7 +1523,15 @@ extern "C"
     a.ctl = ev->d_ctlRecs.get();
     a.rowP = (float4*)ev->d_rowP.get();
     a.rowG = (float4*)ev->d_rowG.get();
-    hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
+    if (ctlRows)  // the instance that also runs the controller glides the graph reads
+    {
+      a.held = ev->d_held.get();
+      for (int r = 0; r < 4; ++r) a.rowC[r] = (float4*)ev->d_rowC[r].get();
+      a.rowMask = ctlRows;
+      hipLaunchKernelGGL(e2s_ctl_rows_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
+    }
+    else
+      hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
     {
@@ -1350,6 +1541,12 @@ extern "C"
     dev->ctl = ev->d_ctlRecs.get();
     dev->rowP = (const float4*)ev->d_rowP.get();
     dev->rowG = (const float4*)ev->d_rowG.get();
+    if (ctlRows)
+    {
+      dev->held = ev->d_held.get();
+      for (int r = 0; r < 4; ++r) dev->rowC[r] = (const float4*)ev->d_rowC[r].get();
+      dev->ctlRowMask = ctlRows;
+    }
     return MLGPU_OK;
   }
   // The router's work of the coming launch, now: the host reads mlgpu_events_sounding_voices and makes its voice list before the

@@ -442,17 +442,22 @@ extern "C"
     if (id >= 0) g->desc.nControls++;
     return id;
   }
-  // a row of an EventsToSignals object computed inside this graph's kernel instead of read from memory (0: pitch, 1: gate)
+  // a row of an EventsToSignals object computed inside this graph's kernel instead of read from memory (mlgpu_event_row: 0 pitch .. 6 mod)
   int mlgpu_graph_add_event_row(mlgpu_graph* g, int row, const char* name)
   {
     if (!g) return -MLGPU_ERR_INVALID;
-    if (row != 0 && row != 1) return -gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_add_event_row: rows 0 (pitch) and 1 (gate) can be source nodes");
+    if (row < MLGPU_EVENT_ROW_PITCH || row > MLGPU_EVENT_ROW_MOD)
+      return -gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_add_event_row: rows 0 (pitch), 1 (gate), 2 (vox), 3 (z), 4 (x), 5 (y) and 6 (mod) can be source nodes");
     for (const Node& m : g->desc.nodes)
       if (m.type == NODE_EVENT_ROW && m.slot == row) return -gfail(g, MLGPU_ERR_INVALID, "graph_add_event_row: this row is a node already");
     Node n(NODE_EVENT_ROW, 0, name);
     n.slot = row;
     const int id = addNode(g, std::move(n));
-    if (id >= 0) g->desc.hasEventRows = true;
+    if (id >= 0)
+    {
+      g->desc.hasEventRows = true;
+      g->desc.eventRowMask |= 1u << row;
+    }
     return id;
   }
   // (file scope, see below) every graph currently bound to an events object, so that destroying the object can unbind them
@@ -1418,9 +1423,9 @@ extern "C"
     if (!g->desc.hasEventRows) return MLGPU_OK;
     if (!g->events) return gfail(g, MLGPU_ERR_INVALID, "graph_process: the graph has event rows but no events object (graph_bind_events)");
     if (g->eventOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with event rows is run with mlgpu_graph_process_events");
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, &a.events, staging);
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, g->desc.eventRowMask, &a.events, staging);
     g->eventOffset = -1;
-    return est == MLGPU_OK ? est : gfail(g, est, "graph_process: the events object refused the block (see its last error)");
+    return est == MLGPU_OK ? est : gfail(g, est, "graph_process: the events object refused the block: " + g->e->lastError);
   }
 
   int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
@@ -1541,7 +1546,7 @@ extern "C"
     const auto who = [who0] { return std::string(who0); };
     *staging = nullptr;
     if (eventOffset < 0) return MLGPU_OK;
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, &a.events, staging);
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, &a.events, staging);
     return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
   }
   // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)

@@ -184,7 +184,10 @@ std::string nodeExpr(const GraphDesc& g, const GraphPlan& p, size_t i, int l, co
   {
     case NODE_INPUT: s << "xin" << n.slot << L << "[k]"; break;
     case NODE_CONTROL: s << "ctl" << n.slot << L << "[t * a.V]"; break;
-    case NODE_EVENT_ROW: s << (n.slot == 0 ? "evP" : "evG") << L << "[k]"; break;
+    case NODE_EVENT_ROW:  // pitch and gate are CtlVoice's, the rows from vox on CtlRows'
+      if (n.slot < 2) s << (n.slot == 0 ? "evP" : "evG") << L << "[k]";
+      else s << "evR" << n.slot << L << "[k]";
+      break;
     case NODE_PARAM: s << "a.params[(size_t)" << n.slot << " * a.V + v" << L << "]"; break;
     case NODE_CONST:
       if (g.liveConsts) s << "a.consts[" << n.slot << "]";  // wave-uniform: a scalar load, kept in an SGPR
@@ -307,7 +310,11 @@ struct GraphEmitter
     PF = g.nInputs > 0;
     oscTrips = p.oscTrips;
     ringTrips = p.rings == RingLayout::SECTORS && p.totalRings;  // ring layout 4: trips of two quads, every ring's loads in the trip's prologue
+    evVoice = (g.eventRowMask & 3u) != 0;
+    evRows = g.eventRowMask & 0x7Cu;
   }
+  bool evVoice{false};   // the graph reads pitch or gate: mlev::CtlVoice
+  unsigned evRows{0};    // its rows among vox, z, x, y, mod (bit r = row r): mlev::CtlRows<evRows>, emitted only where there is one
   static std::string sfx(int l) { return "_" + std::to_string(l); }
   static std::string name(int j, const std::string& ph, int l) { return "n" + std::to_string(j) + ph + sfx(l); }
   // a group sum of 16 voices (one instrument's voices): four quads of the wavefront's 64 voices are parked in LDS and every lane
@@ -520,8 +527,12 @@ struct GraphEmitter
     // spare lanes sit in the last voice's wavefront and take every branch it takes (fetch, moving, rows are the same per-voice values), so
     // a word's loads and stores are issued by the same instructions for all of them; and within a launch no word is loaded after it was
     // stored except by a LATER instruction that wants the stored value (slot 63 and the first quad's slots at the next begin_vector).
-    if (g.hasEventRows)
+    // (CtlVoice where the graph reads pitch or gate; the rows vox, z, x, y, mod are mlev::CtlRows', which only reads - by the same voice)
+    if (evVoice)
       for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
+    if (evRows)
+      for (int l = 0; l < VL; ++l)
+        s << "  mlev::CtlRows<" << evRows << "u> er" << sfx(l) << ";\n  er" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
     // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
     // whole HBM round trip per quad, and with four wavefronts per SIMD there are long stretches with only one or two of them able to
     // issue (one wavefront alone issues at 40 % of the SIMD's rate). The very last quad of a launch loads itself again.
@@ -545,8 +556,10 @@ struct GraphEmitter
     s << "  for (size_t t = 0; t < a.T; ++t)\n  {\n";
     // (Rounds 3-4 walked the event records inside this kernel - 134 spilled registers, 0.35 scalar / branch instructions per vector
     // one; round 5: the record walk is e2s_ctl_kernel's, this kernel expands its control records - mldsp_events.hpp.)
-    if (g.hasEventRows)
+    if (evVoice)
       for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".begin_vector(t);\n";
+    if (evRows)
+      for (int l = 0; l < VL; ++l) s << "    er" << sfx(l) << ".begin_vector(t);\n";
     for (size_t i = 0; i < g.nodes.size(); ++i)
     {
       const Node& n = g.nodes[i];
@@ -631,9 +644,16 @@ struct GraphEmitter
       }
     for (size_t o = 0; o < g.outputs.size(); ++o)
       for (int l = 0; l < VL; ++l) s << "      f32x4 y" << o << sfx(l) << ";\n";
-    if (g.hasEventRows)
+    if (evVoice)
       for (int l = 0; l < VL; ++l)
         s << "      mlev::CtlVoice::f32x4e evP" << sfx(l) << ", evG" << sfx(l) << ";\n      ev" << sfx(l) << ".quad(t, q, evP" << sfx(l) << ", evG" << sfx(l) << ");\n";
+    if (evRows)
+      for (int l = 0; l < VL; ++l)
+      {
+        s << "      er" << sfx(l) << ".quad(t, q);\n";
+        for (int r = 2; r <= 6; ++r)
+          if ((evRows >> r) & 1u) s << "      const f32x4 evR" << r << sfx(l) << " = er" << sfx(l) << ".row<" << r << ">(t, q);\n";
+      }
     // A kept DSPVector's slot n is read and rewritten at sample n only: the quad's four slots are fetched together - and TWO QUADS
     // AHEAD (round 5; they were written 14 quads ago). Fetched at the top of the quad that uses them, every quad of a feedback graph
     // stood still for a memory round trip, behind the stores of the quad before (memory operations of a wavefront complete in issue
@@ -848,10 +868,10 @@ struct GraphEmitter
     for (size_t i = 0; i < g.nodes.size(); ++i)
       if (g.nodes[i].type == NODE_PROC && (g.nodes[i].region < 0 || g.nodes[i].role != ROLE_NONE))
         for (int l = 0; l < VL; ++l) s << "    p" << i << sfx(l) << ".end_vector();\n";
-    if (g.hasEventRows)
+    if (evVoice)
       for (int l = 0; l < VL; ++l) s << "    ev" << sfx(l) << ".end_vector();\n";
     s << "  }\n";
-    if (g.hasEventRows)
+    if (evVoice)
       for (int l = 0; l < VL; ++l) s << "  ev" << sfx(l) << ".store();\n";
     for (size_t i = 0; i < g.nodes.size(); ++i)
       if (g.nodes[i].type == NODE_PROC)

@@ -39,7 +39,7 @@ enum NodeType
   NODE_VOP = 6,      // index-dependent vector generator (columnIndex, rangeOpen, ...)
   NODE_ROUTE = 7,    // multiplex / demultiplex (MLDSPRouting.h); in[0] is the selector
   NODE_FEEDBACK = 8,  // value of another node one DSPVector ago (64 state words per voice)
-  NODE_EVENT_ROW = 9  // a row of the bound EventsToSignals object, computed in this kernel (slot: 0 pitch, 1 gate)
+  NODE_EVENT_ROW = 9  // a row of the bound EventsToSignals object, computed in this kernel (slot: the row - 0 pitch, 1 gate, 2 vox, 3 z, 4 x, 5 y, 6 mod)
 };
 
 // how often a node's value changes: per voice (params, consts and ops on them), per DSPVector (controls and
@@ -98,6 +98,7 @@ struct GraphDesc
   int nInputs{0}, nParams{0}, nControls{0}, nConsts{0}, NC{0}, NS{0};
   bool hasImpulse{false};
   bool hasEventRows{false};
+  unsigned eventRowMask{0};      // bit r: row r is a NODE_EVENT_ROW node (0 pitch, 1 gate, 2 vox, 3 z, 4 x, 5 y, 6 mod)
   bool strictSvf{false};         // the engine's mode when the graph was made (mlgpu_engine_set_strict_svf)
   bool liveConsts{false};        // const nodes read d_consts instead of being literals of the generated code
   int delayLayout{0};            // as mlgpu_graph_set_delay_layout took it (3: the best of 2 / 4 / 1 for the graph)

@@ -2,7 +2,8 @@
 // (events.hip: all 8 rows into HBM) and the run-time fused graph kernels (graph.hip: pitch and gate as source nodes of a voice
 // graph, never written to memory): the kernels' arguments (the record format and the state layout are mlev_format.hpp), LinearGlide
 // with its 64 slots, note_frame - one frame of a vector that holds note records - and CtlVoice: the control records of
-// e2s_ctl_kernel expanded to the pitch and gate rows inside a voice kernel, one quad of frames at a time.
+// e2s_ctl_kernel expanded to the pitch and gate rows inside a voice kernel, one quad of frames at a time - and CtlRows, which reads
+// the rows vox, z, x, y and mod that the control kernel makes for a graph that has them as source nodes.
 #pragma once
 #include "mlgpu_device_args.hpp"
 #include "mldsp_math.hpp"
@@ -378,6 +379,12 @@ enum : int
 constexpr uint32_t CF_ON = 1u;    // the voice's instrument is awake: processVector is not a no-op (:383-386)
 constexpr uint32_t CF_ROWS = 2u;  // the pitch before drift of this vector is in the side signal, frame by frame
 constexpr uint32_t CF_GATE_ROW = 4u;  // ... and so is the gate (a vector with a note event)
+// controller row r (3 z, 4 x, 5 y, 6 mod) of this vector is in its side signal, frame by frame: its glide moves inside the vector
+constexpr uint32_t CF_ROW(int r) { return 8u << (r - 3); }
+constexpr uint32_t kCtlRowsMask = 0x78u;  // the rows of a graph that are glides of e2s_ctl_kernel: bits 3..6
+// row r's place among the rows of `mask` in the plane of held values (EventsDev::held)
+constexpr int ctl_row_rank(uint32_t mask, int r) { return __builtin_popcount(mask & kCtlRowsMask & ((1u << r) - 1u)); }
+constexpr int ctl_row_count(uint32_t mask) { return __builtin_popcount(mask & kCtlRowsMask); }
 
 // Memory of this object is addressed the CDNA way: a 128-bit buffer descriptor in scalar registers (built from kernel arguments
 // only, so provably wave-uniform), ONE 32-bit per-lane byte offset in a vector register, and a scalar offset per access
@@ -539,6 +546,89 @@ struct CtlVoice
   MLD void end_vector()
   {
     if (on) gd.endVector();
+  }
+};
+
+// The rows vox, z, x, y and mod (2..6) of one voice as source nodes of a graph kernel; MASK has bit r for each row r the graph reads.
+// Unlike the drift glide these glides belong to e2s_ctl_kernel: it runs them for every lane in every call, so this object only READS -
+// per vector one held value per row (EventsDev::held) and the vector's flags, and for a row whose glide moves inside the vector
+// (CF_ROW(r): the ~15 vectors after a controller event) the 64 frames of its side signal. Nothing is stored, nothing is carried over
+// from launch to launch: a voice that was off a voice list has the bits of one that never was. vox is a constant of the voice (:302).
+// Memory is addressed as CtlVoice does: a buffer descriptor per plane and the lane's 32-bit byte offset; the side signals, read by
+// the flagged lanes only, through a pointer made inside the rare branch.
+template <uint32_t MASK>
+struct CtlRows
+{
+  typedef float f32x4e __attribute__((ext_vector_type(4)));
+  static constexpr int N = ctl_row_count(MASK);
+  static constexpr int NA = N ? N : 1;
+  EventsDev d;  // (uniform)
+  size_t T;
+  uint32_t rowBytes, laneBytes;
+  float vox;
+  float hv[NA], nx[NA];    // the held values of this vector / of the next one (fetched during this vector's last quad)
+  uint32_t flags, nflags;  // C_FLAGS of the two
+  bool any[NA];            // wave-uniform: some lane has the row flagged in this vector
+
+  MLD void fetch(size_t t)
+  {
+    if constexpr (N > 0)
+    {
+      const BufRsrc rec = lane_buffer(d.ctl + (t * (size_t)kCtlRecWords + (size_t)C_FLAGS) * d.lanes, rowBytes);
+      nflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, 0, 0);
+      const BufRsrc plane = lane_buffer(d.held + t * (size_t)N * d.lanes, (size_t)N * rowBytes);
+#pragma unroll
+      for (int k = 0; k < N; ++k) nx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
+    }
+  }
+  MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
+  {
+    d = a;
+    T = nVectors;
+    rowBytes = (uint32_t)d.lanes * 4u;
+    laneBytes = (uint32_t)voice * 4u;
+    vox = (float)((uint32_t)voice % (uint32_t)d.s.polyphony);
+    flags = nflags = 0u;
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+    {
+      hv[k] = nx[k] = 0.f;
+      any[k] = false;
+    }
+    fetch(0);
+  }
+  MLD void begin_vector(size_t t)
+  {
+    (void)t;
+    if constexpr (N > 0)
+    {
+      flags = nflags;
+#pragma unroll
+      for (int k = 0; k < N; ++k) hv[k] = nx[k];
+#pragma unroll
+      for (int r = 3; r <= 6; ++r)
+        if ((MASK >> r) & 1u) any[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((flags & CF_ROW(r)) != 0) != 0;
+    }
+  }
+  MLD void quad(size_t t, int q)
+  {
+    if (q == 15 && t + 1 < T) fetch(t + 1);
+  }
+  template <int R>
+  MLD f32x4e row(size_t t, int q) const
+  {
+    static_assert(R >= 2 && R <= 6 && ((MASK >> R) & 1u), "a row of this graph");
+    if constexpr (R == 2) return f32x4e{vox, vox, vox, vox};
+    else
+    {
+      constexpr int k = ctl_row_rank(MASK, R);
+      f32x4e v = {hv[k], hv[k], hv[k], hv[k]};
+      if (any[k])
+      {
+        if (flags & CF_ROW(R)) v = __builtin_nontemporal_load((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2)));
+      }
+      return v;
+    }
   }
 };
 

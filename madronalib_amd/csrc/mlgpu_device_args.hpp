@@ -76,6 +76,7 @@ struct E2SSettings
   int32_t driftGlideVectors;  float driftGlideDy;  // sr * 8 s (:103)
   int32_t ctlGlideVectors;  float ctlGlideDy;      // SmoothedController: int(sr * 0.02 s) samples (:274-275) — truncated first
   int32_t mpe;                         // protocol
+  int32_t polyphony;                   // voices per instrument: the vox row is (float)(voice % polyphony) under the MIDI protocol (:302)
 };
 
 // the EventsToSignals object whose pitch / gate rows are source nodes of a graph (mlgpu_graph_bind_events); state == nullptr: none
@@ -91,6 +92,12 @@ struct EventsDev
   const uint32_t* ctl;
   const float4* rowP;
   const float4* rowG;
+  // the controller rows z, x, y, mod (rows 3..6) of a graph that has them as source nodes (mlev::CtlRows): ctlRowMask has bit r for
+  // row r of this launch, `held` is the plane [T][rows of the mask, ascending][lanes] of one value per vector, rowC[r - 3] row r's side
+  // signal (QUAD layout, as rowP), written for the vectors whose C_FLAGS has CF_ROW(r) only. Null / 0 without such rows.
+  const uint32_t* held;
+  const float4* rowC[4];
+  uint32_t ctlRowMask;
 };
 
 // a fused graph kernel: up to MLGPU_GRAPH_MAX_INPUTS (32) streamed inputs, MLGPU_GRAPH_MAX_OUTPUTS (8) outputs, per-voice constants [P][V]

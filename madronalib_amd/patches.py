@@ -67,6 +67,23 @@ def synth16(pitch_input=False, full=False, event_rows=False):
     return d, ["out"]
 
 
+def synth16_mod_z(event_rows=True):
+    """synth16(pitch_input=True) with a voice that also follows the mod wheel and aftertouch: the filter input is scaled by
+    (1 + mod), z is added to the amp envelope. event_rows: gate, pitch, z and mod are rows of a bound Events object computed in the
+    voice kernel (EventRow 1, 0, 3, 6); else four streamed inputs of those names."""
+    from .constants import EventRow
+    d, outs = synth16(pitch_input=True, event_rows=event_rows)
+    src = (lambda n, k: dict(name=n, type="event_row", kind=k)) if event_rows else (lambda n, k: dict(name=n, type="input"))
+    i = next(j for j, n in enumerate(d) if n["name"] == "lp")
+    d[i:i + 1] = [src("mod", EventRow.MOD), dict(name="modGain", type="op", kind=Op.ADD, inputs=["hi", "mod"]),
+                  dict(name="preMod", type="op", kind=Op.MULTIPLY, inputs=["pre", "modGain"]),
+                  dict(name="lp", type="proc", kind=Proc.LOPASS, inputs=["preMod"])]
+    i = next(j for j, n in enumerate(d) if n["name"] == "vca")
+    d[i:i + 1] = [src("z", EventRow.Z), dict(name="envZ", type="op", kind=Op.ADD, inputs=["env", "z"]),
+                  dict(name="vca", type="op", kind=Op.MULTIPLY, inputs=["dc", "envZ"])]
+    return d, outs
+
+
 # ---- the reference's feedback composites written out as graphs (what the C++ shim's classes emit) ------------------
 
 def allpass(prefix, x, delay_kind, max_delay, delay=None):
