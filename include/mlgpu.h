@@ -1098,9 +1098,9 @@ typedef struct mlgpu_event /* ml::Event, MLEvent.h:31-53 */
 typedef struct mlgpu_events mlgpu_events;
 int mlgpu_events_create(mlgpu_engine* e, size_t n_instruments, int polyphony /* setPolyphony, 1..16 */, mlgpu_events** out);
 int mlgpu_events_destroy(mlgpu_events* ev);
-int mlgpu_events_clear(mlgpu_events* ev);                                   /* clear(), :330-340 */
+int mlgpu_events_clear(mlgpu_events* ev);                                   /* clear(), :330-340: voices and keys reset; an instrument that has seen an event stays awake */
 int mlgpu_events_set_sample_rate(mlgpu_events* ev, double sr);
-int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe);                   /* setProtocol("MIDI" / "MPE"); clears */
+int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe);                   /* setProtocol("MIDI" / "MPE"); clears; re-makes a reserve_for_graph for the new lanes (EVENT ROWS UNDER THE MPE PROTOCOL) */
 int mlgpu_events_set_unison(mlgpu_events* ev, int on);
 int mlgpu_events_set_mod_cc(mlgpu_events* ev, int cc);
 int mlgpu_events_set_pitch_bend_semitones(mlgpu_events* ev, float f);
@@ -1240,6 +1240,36 @@ int mlgpu_events_reserve_for_graph_rows(mlgpu_events* ev, size_t max_vectors, un
 size_t mlgpu_events_graph_reserve_bytes_rows(mlgpu_events* ev, size_t max_vectors, unsigned row_mask);
 int mlgpu_graph_process_events(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
                                const float* const* d_controls, float* const* d_outputs, int out_layout);
+
+/* EVENT ROWS UNDER THE MPE PROTOCOL. mlgpu_graph_enable_mpe_events(g, 1) is a build call (before compile). Without it nothing changes:
+ * every kernel's text, and every refusal that names the MIDI protocol. With it the PLAIN kernel of a graph with event rows is generated
+ * in a form for either protocol, mlgpu_graph_bind_events accepts an object in either, and mlgpu_graph_process_events serves the
+ * protocol the object has AT THE CALL - the protocol is data of the launch, a host switches it with mlgpu_events_set_protocol at run
+ * time. Under MIDI the switched kernel gives the bits of the kernel without the switch.
+ *   Lanes. Under MPE an instrument is G = nextpow2(polyphony + 1) lanes of the object: lane 0 its main voice (voices[0] of the
+ *   reference, MIDI channel 1), lanes 1..polyphony its playing voices, the rest padding. Graph voice v is lane (v / polyphony) * G + 1 +
+ *   v % polyphony; instruments x polyphony still equals the graph's voices, and vox is still v % polyphony. Device memory of the two-launch
+ *   form goes by LANE: mlgpu_events_graph_reserve_bytes[_rows] is the per-lane figure above x instruments x G under MPE.
+ *   What is added to what (source/app/MLEventsToSignals.cpp:417-458). A playing voice's bend is scaled by the MPE bend range, the main
+ *   voice's by the MIDI one; z does not add the smoothed channel pressure; and the main voice's pitch row - its bend glide and its own
+ *   drift glide - and its z, x, y and mod rows are added, sample by sample, to those rows of every playing voice of its instrument that
+ *   is awake. Gate and vox get nothing added. The control kernel makes the main voice's rows (it owns that voice's drift glide), the
+ *   voice kernel reads them with the voice's own and adds; nothing more is stored. Every voice and sample has the bits of
+ *   mlgpu_events_process on an MPE object in the same state, and either call hands over to the other in any vector.
+ *   Statuses. After a reserve, process calls under MPE never allocate and answer MLGPU_ERR_RANGE / MLGPU_ERR_INVALID exactly as under
+ *   MIDI, before the router consumes anything; mlgpu_events_route_ahead stays legal for the plain call. The listed forms are not served:
+ *   mlgpu_graph_process_events_listed[_groups] on an MPE object answers MLGPU_ERR_UNSUPPORTED naming MIDI, and
+ *   mlgpu_events_sounding_voices stays refused under MPE. A graph built WITHOUT the switch keeps MLGPU_ERR_UNSUPPORTED at bind and at
+ *   every process call on an MPE object.
+ *   mlgpu_events_set_protocol and reserves. The call clears, as ever. It now also makes the buffers of
+ *   mlgpu_events_reserve_for_graph[_rows] again for the new protocol's lane count - same DSPVectors, same row mask, the old buffers
+ *   retired through the engine - so a reserve made at setup survives every later switch (the call waits for the stream and allocates:
+ *   it is a setup-rate call, not one for the audio thread). MLGPU_ERR_OOM: the old protocol stays in force.
+ *   With the switch, event rows also no longer ask a graph with a mixed-down output (mlgpu_graph_set_output_mixdown) for whole
+ *   wavefronts: the last wavefront's spare lanes run the last voice - its lane and its main lane - again.
+ *   Cost for a MIDI-only host: the switched voice kernel is 6 - 7 % slower under MIDI than the unswitched one, about 3 % of the instrument
+ *   bank's block (profiles/graph_events_mpe.md) - a host that never switches to MPE leaves the switch off. */
+int mlgpu_graph_enable_mpe_events(mlgpu_graph* g, int on);
 
 /* VOICE LISTS FOR GRAPHS WITH EVENT ROWS: the instrument bank runs, in one fused launch, only the voices that sound.
  *

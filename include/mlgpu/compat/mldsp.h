@@ -3156,8 +3156,10 @@ struct VoiceProgramOptions
   bool autotune{false};
   bool liveConstants{false};  // constants are read from a device table: VoiceProgram::update() can change them (mlgpu_graph_set_live_constants)
   // SynthProgram: if processVoice reads no voice row but pitch and gate, the voice kernel computes those two rows itself from the
-  // events' records (mlgpu_graph_add_event_row) instead of reading them from memory - a quarter faster end to end. MIDI protocol
-  // only (mlgpu_events_set_protocol(..., 1) makes process() fail), hence opt-in.
+  // events' records (mlgpu_graph_add_event_row) instead of reading them from memory - a quarter faster end to end. SynthProgram
+  // builds such a graph with mlgpu_graph_enable_mpe_events, so the kernel serves whichever protocol the events object has at the call:
+  // kProtocol (EventsToSignals::setProtocol) stays a run-time parameter and process() goes on after a switch to MPE. Opt-in because
+  // the form for either protocol costs a MIDI-only host a little (profiles/graph_events_mpe.md).
   bool eventRowsInKernel{false};
   // Context signals (AudioContext::getInputController / getBeatPhase) have one row per this many adjacent voices: the
   // instrument's polyphony. 0: ctx->getInputPolyphony() if that was set, else one row for the whole bank.
@@ -3324,6 +3326,8 @@ class VoiceProgram
       ctx_->inputs[(int)c] = DSPVector(Sig(cap.ret(mlgpu_graph_add_input(g, ("in" + std::to_string(c)).c_str())), 0.f));
     // the 8 rows of this lane's voice (EventsToSignals) are further streamed inputs, after the audio inputs; the first pass
     // finds out whether the code reads them at all
+    // (event rows in the kernel: in the form for either protocol, so that EventsToSignals::setProtocol keeps working at run time)
+    if (!firstPass && eventRowsInKernel()) cap.ret(-mlgpu_graph_enable_mpe_events(g, 1));
     for (int r = 0; r < kNumVoiceOutputRows; ++r)
     {
       rowNode[r] = -1;

@@ -1234,7 +1234,7 @@ class Graph(_Handle):
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
                  live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False,
-                 voice_list_events=False):
+                 voice_list_events=False, mpe_events=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1259,6 +1259,8 @@ class Graph(_Handle):
             self.enable_voice_list_groups()
         if voice_list_events:   # ... and a graph with event rows has a listed form: process_events_listed / process_events_listed_groups
             self.enable_voice_list_events()
+        if mpe_events:   # the plain kernel's event rows in the form for either protocol: bind_events / process_events take an MPE object
+            self.enable_mpe_events()
         if description is not None:
             for n in description:
                 self.add(**n)
@@ -1370,6 +1372,11 @@ class Graph(_Handle):
         pc = (ctypes.c_void_p * max(1, len(d_controls)))(*[raw(b) for b in d_controls])
         pp = None if d_peak is None else ctypes.c_void_p(raw(d_peak))
         self._check(self.L.mlgpu_graph_process_listed_groups(self.h, int(n_vectors), pi, int(in_layout), pc, po, int(out_layout), pp))
+
+    def enable_mpe_events(self, on=True):
+        """Before compile: the plain kernel of a graph with event rows is generated for either protocol of the bound Events object
+        (mlgpu_graph_enable_mpe_events) - process_events serves the protocol the object has at the call. The listed forms stay MIDI only."""
+        self._check(self.L.mlgpu_graph_enable_mpe_events(self.h, 1 if on else 0))
 
     def enable_voice_list_events(self, on=True):
         """Before compile: voice lists, also for a graph with event rows - its listed kernel expands the control records of the gathered

@@ -583,8 +583,10 @@ struct E2SCtlArgs
   uint32_t* held;  // [T][rows of rowMask, ascending][lanes]
   float4* rowC[4]; // z, x, y, mod: QUAD, written for CF_ROW(r) vectors only
   uint32_t rowMask;
-  size_t lanes, T;
-  uint32_t flags;
+  int32_t group;     // the MPE instances: lane = instrument * group + (voice slot - slotBase), as E2SArgs has them. (The two sit where the
+  size_t lanes, T;   // struct had padding: every other member, and the hidden kernel arguments behind the struct, stay where the MIDI
+  uint32_t flags;    // instances' code reads them - tools/asm_compare.py.)
+  int32_t slotBase;
   E2SSettings s;
 };
 
@@ -632,12 +634,79 @@ __device__ __noinline__ void ctl_z_frames(const Glide& gz, const Glide& gp, uint
   }
 }
 
+// ... and of z under the MPE protocol: its own glide alone. The channel-pressure glide takes its steps all the same, as e2s_kernel's does
+// (its state words are what the other call expects), but is not added (:437-445).
+__device__ __noinline__ void ctl_z_frames_mpe(const Glide& gz, const Glide& gp, uint32_t* gsz, uint32_t* gsp, size_t ln, float4* out)
+{
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  f32x4* o = (f32x4*)out;
+#pragma unroll 1
+  for (int q = 0; q < 16; ++q, o += ln)
+  {
+    float cz4[4] = {0.f, 0.f, 0.f, 0.f}, cp4[4] = {0.f, 0.f, 0.f, 0.f};
+    gz.preload(gsz, ln, q, cz4);
+    gp.preload(gsp, ln, q, cp4);
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      v[k] = gz.nextWith(gsz, ln, q * 4 + k, cz4[k]);
+      (void)gp.nextWith(gsp, ln, q * 4 + k, cp4[k]);
+    }
+    __builtin_nontemporal_store(v, o);
+  }
+}
+
+// The MPE main voice's pitch row of a vector with no note event and a held bend: the pitch glide's 64 steps and the drift glide's, the
+// drift term added last (:247). The drift glide moves in nearly every vector and every wavefront holds main voices, so its mCurrVec
+// slots are fetched 16 at a time: four round trips per vector where a load per frame behind the frame before's store was 64 (the
+// control kernel's whole time, profiles/graph_events_mpe.md). In line: out of line the pitch glide's words went through scratch, a
+// memory round trip per frame again.
+__device__ __forceinline__ void ctl_main_pitch_frames(PitchGlide& pg, float pitch, float bendTerm, const Glide& gd, uint32_t* gs, size_t ln, float amount, float4* out)
+{
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  f32x4* o = (f32x4*)out;
+  constexpr int kChunk = 16;  // (32 at a time measured no faster: 2788 against 2661 us for the kernel)
+  const bool reads = gd.readsCurrVec();
+#pragma unroll 1
+  for (int h = 0; h < 64; h += kChunk)
+  {
+    float cur[kChunk];
+#pragma unroll
+    for (int i = 0; i < kChunk; ++i) cur[i] = 0.f;
+    if (reads)
+    {
+#pragma unroll
+      for (int i = 0; i < kChunk; ++i) cur[i] = u2f(gs[(size_t)(5 + h + i) * ln]);
+    }
+#pragma unroll
+    for (int q = 0; q < kChunk / 4; ++q, o += ln)
+    {
+      f32x4 v;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+      {
+        const float p = pg.next(pitch) + bendTerm;
+        v[k] = p + (gd.nextWith(gs, ln, h + q * 4 + k, cur[q * 4 + k]) * amount) * 0.02f;
+      }
+      __builtin_nontemporal_store(v, o);
+    }
+  }
+}
+
 // ROWS: the graph reads some of the rows z, x, y, mod (a.rowMask). Their glides - 1 mod, 2 x, 3 y, 4 z with 6, the smoothed channel
 // pressure - are run here as e2s_kernel's glideRow runs them, once per vector and lane: a glide that is held gives ONE word (the plane
 // a.held), one that moves inside the vector its 64 frames in the row's side signal and CF_ROW(r) in the vector's flags. A row outside
 // a.rowMask keeps its glide where it is (mlgpu_events_set_wanted_rows' rule). The instance without ROWS is the kernel of a graph
 // that reads pitch and gate only: none of this is in its code.
-template <bool ROWS>
+// MPE: the instances for an events object under the MPE protocol (a graph built with mlgpu_graph_enable_mpe_events). A lane is slot
+// lane % group + slotBase of its instrument: the padding lanes past the polyphony leave at once, the bend scale goes by slot (:417-423),
+// z does not add the channel pressure. A slot-0 lane is the MAIN voice: no voice kernel expands its record, so this kernel owns its drift
+// glide (glide 5) too - walked as e2s_kernel's general loop walks it - and its pitch is the complete row, (pitch glide + bend term) +
+// drift * amount * 0.02 in the reference's order (:244, :247): one value in C_PITCH while pitch glide, bend and drift glide are all held,
+// else 64 frames in rowP under CF_ROWS. The voice kernel adds it to the instrument's playing voices (mlev::CtlVoiceMpe). The MIDI
+// instances hold none of this.
+template <bool ROWS, bool MPE = false>
 __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
 {
   apply_fp_mode(a.flags);
@@ -646,6 +715,13 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
   if (blk < nbFull) blk = (blk & 7) * (nbFull >> 3) + (blk >> 3);
   const size_t lane = blk * 256 + threadIdx.x;
   if (lane >= a.lanes) return;
+  [[maybe_unused]] bool isMain = false;
+  if constexpr (MPE)
+  {
+    const int slot = (int)(lane % (size_t)a.group) + a.slotBase;
+    if (slot > a.s.polyphony) return;  // padding
+    isMain = slot == 0;
+  }
   uint32_t* S = a.state + lane;
   const size_t ln = a.lanes;
 #define SW(i) S[(size_t)(i) * ln]
@@ -687,13 +763,20 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
   uint32_t* GB = S + (size_t)(S_GLIDES + 0 * kGlideWords) * ln;
   Glide gb;
   gb.load(GB, ln);
+  [[maybe_unused]] uint32_t* const GD = S + (size_t)(S_GLIDES + 5 * kGlideWords) * ln;  // MPE: the main voice's drift glide
+  [[maybe_unused]] Glide gd;
+  if constexpr (MPE)
+  {
+    if (isMain) gd.load(GD, ln);
+  }
 
   const uint2 recRange = a.recRange[lane];  // this lane's records of this launch: [x, y)
   uint32_t cursor = recRange.x;
   const uint32_t recEnd = recRange.y;
   // the vector of this lane's next record, in a register: a lane with a record later in the launch does not ask memory every vector
   uint32_t nextVec = cursor < recEnd ? a.recs[cursor].vec : 0xFFFFFFFFu;
-  const float pitchBendScale = a.s.pitchBendRange;  // MIDI protocol, :417-423
+  float pitchBendScale = a.s.pitchBendRange;  // MIDI protocol, :417-423
+  if constexpr (MPE) pitchBendScale = (a.s.mpe && !isMain) ? a.s.mpePitchBendRange : a.s.pitchBendRange;
   uint32_t* rec = a.ctl + lane;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   for (size_t t = 0; t < a.T; ++t, rec += (size_t)kCtlRecWords * ln)
@@ -731,13 +814,32 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
       }
       if (finalVelocity == 0.f) cz = 0.f;  // :238-241
       gb.beginVector(GB, ln, bend, a.s.glideVectors, a.s.glideDy);
+      if constexpr (MPE)
+      {
+        if (isMain) gd.beginVector(GD, ln, driftValue, a.s.driftGlideVectors, a.s.driftGlideDy);
+      }
     }
     const int bm = gb.mode();
     const bool heldB = (bm == 1) || (bm == 0 && gb.isUniform());
     const bool pgBusy = on && (pitch != pg.target || pg.remaining >= 0);
     const bool walk = on && (noteHere || !heldB);
-    const bool glideOnly = on && !walk && pgBusy;  // a portamento in progress, nothing else: the pitch glide's 64 steps, the gate held
+    // (MPE, the main voice: its drift glide is part of its pitch row - while it moves, a vector with nothing else going on is 64 frames too)
+    [[maybe_unused]] bool driftMoves = false;
+    if constexpr (MPE)
+    {
+      const int dm = gd.mode();
+      driftMoves = on && isMain && !((dm == 1) || (dm == 0 && gd.isUniform()));
+    }
+    const bool glideOnly = on && !walk && (pgBusy || driftMoves);  // a portamento in progress, nothing else: the pitch glide's 64 steps, the gate held
     const float hvB = (bm == 1) ? gb.target : gb.uniformValue;
+    // the main voice's drift term of frame n, added last (:247); gd.next is the record-walking path's form of a glide's sample
+    [[maybe_unused]] auto withDrift = [&](float v, int n) {
+      if constexpr (MPE)
+      {
+        if (isMain) v = v + (gd.next(GD, ln, n) * a.s.driftAmount) * 0.02f;
+      }
+      return v;
+    };
     float P = 0.f, gate = 0.f;
     if (!walk)
     {
@@ -746,13 +848,21 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
         gate = velocity;
         age += (uint32_t)MLGPU_FLOATS_PER_DSPVECTOR * ageStep;
         const float bendTerm = (hvB * pitchBendScale) * (1.f / 12);  // :244
-        if (!glideOnly) P = pg.curr + bendTerm;  // the same for all 64 frames
+        if (!glideOnly)
+        {
+          P = pg.curr + bendTerm;  // the same for all 64 frames
+          if constexpr (MPE)
+          {
+            if (isMain) P = P + (((gd.mode() == 1) ? gd.target : gd.uniformValue) * a.s.driftAmount) * 0.02f;  // the drift glide is held
+          }
+        }
         else
         {
           f32x4* oP = (f32x4*)a.rowP + (t * 16) * ln + lane;
           // in the middle of a glide - 64 or more steps to go, the target unchanged - every frame of the vector is nextSample's last
           // branch (:571-576): mCurr += mStep. 64 dependent adds instead of 64 trips through the state machine.
-          if (pitch == pg.target && pg.remaining >= MLGPU_FLOATS_PER_DSPVECTOR && pg.remaining < pg.perGlide)
+          if (MPE && isMain) ctl_main_pitch_frames(pg, pitch, bendTerm, gd, GD, ln, a.s.driftAmount, a.rowP + (t * 16) * ln + lane);
+          else if (pitch == pg.target && pg.remaining >= MLGPU_FLOATS_PER_DSPVECTOR && pg.remaining < pg.perGlide)
           {
 #pragma unroll 4
             for (int q = 0; q < 16; ++q, oP += ln)
@@ -831,6 +941,7 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
             vGate = velocity;
             vPitch = pg.next(pitch) + bendTerm;
             age += ageStep;
+            if constexpr (MPE) vPitch = withDrift(vPitch, n);
           }
           else
           {
@@ -838,6 +949,7 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
                        vTime);
             const float bendSig = gb.next(GB, ln, n);
             vPitch = vPitch + (bendSig * pitchBendScale) * (1.f / 12);  // :244
+            if constexpr (MPE) vPitch = withDrift(vPitch, n);
             if (heldB) quietUntil = plan(n + 1);
           }
           vP = f32x4{k == 0 ? vPitch : vP[0], k == 1 ? vPitch : vP[1], k == 2 ? vPitch : vP[2], k == 3 ? vPitch : vP[3]};
@@ -886,13 +998,14 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
         float zv = 0.f;
         if (on && !held)
         {
-          ctl_z_frames(gz, gp, GS(4), GS(6), ln, a.rowC[0] + (t * 16) * ln + lane);
+          if (MPE && a.s.mpe) ctl_z_frames_mpe(gz, gp, GS(4), GS(6), ln, a.rowC[0] + (t * 16) * ln + lane);
+          else ctl_z_frames(gz, gp, GS(4), GS(6), ln, a.rowC[0] + (t * 16) * ln + lane);
           rowFlags |= CF_ROW(3);
         }
         else if (on)
         {
           zv = hz;
-          zv = zv + hp;
+          if (!(MPE && a.s.mpe)) zv = zv + hp;
         }
         hw[(size_t)ctl_row_rank(a.rowMask, 3) * ln] = f2u(zv);
         if (on)
@@ -907,6 +1020,10 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
     rec[2 * ln] = f2u(driftValue);
     rec[3 * ln] = (on ? CF_ON : 0u) | ((walk || glideOnly) ? CF_ROWS : 0u) | (walk ? CF_GATE_ROW : 0u) | rowFlags;
     if (on) gb.endVector();
+    if constexpr (MPE)
+    {
+      if (on && isMain) gd.endVector();
+    }
     if (vend != cursor)
     {
       cursor = vend;
@@ -920,6 +1037,10 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
     if (recRange.x != recRange.y) a.recRange[Lend] = make_uint2(0u, 0u);  // consumed
   }
   gb.store(S + (size_t)(S_GLIDES + 0 * kGlideWords) * ln, ln);
+  if constexpr (MPE)
+  {
+    if (isMain) gd.store(S + (size_t)(S_GLIDES + 5 * kGlideWords) * ln, ln);
+  }
   SW(S_AWAKE) = awake ? 1u : 0u;
   SW(S_VELOCITY) = f2u(velocity); SW(S_PITCH) = f2u(pitch); SW(S_BEND) = f2u(bend); SW(S_Z) = f2u(cz);
   SW(S_AGE) = age; SW(S_AGE_STEP) = ageStep; SW(S_INHIBIT_GLIDE) = inhibit ? 1u : 0u; SW(S_RECALC) = needsRecalc ? 1u : 0u;
@@ -945,6 +1066,9 @@ __device__ __forceinline__ void e2s_ctl_body(const E2SCtlArgs& a)
 // it takes every register there is for the unrolled glide loops and runs one -, the pitch/gate instance keeps the attributes it had)
 __global__ __launch_bounds__(256) void e2s_ctl_kernel(const E2SCtlArgs a) { e2s_ctl_body<false>(a); }
 __global__ __launch_bounds__(256, 2) void e2s_ctl_rows_kernel(const E2SCtlArgs a) { e2s_ctl_body<true>(a); }
+// ... and the two for an object under the MPE protocol (launched over all its lanes: main voices, playing voices, padding)
+__global__ __launch_bounds__(256) void e2s_ctl_mpe_kernel(const E2SCtlArgs a) { e2s_ctl_body<false, true>(a); }
+__global__ __launch_bounds__(256, 2) void e2s_ctl_rows_mpe_kernel(const E2SCtlArgs a) { e2s_ctl_body<true, true>(a); }
 
 // ---- smoothed controller signals: one lane per (watched controller slot, instrument); CtlRec and the C_* state words are in
 // mlev_format.hpp -------------------------------------------------------------------------------------------------------------
@@ -1172,6 +1296,13 @@ extern "C"
     // bank and a cleared one differ only there. This implementation resets the device state completely.
     std::vector<uint32_t> st;
     ev->router.initialVoiceState(st);
+    // ... except that an instrument that has seen an event stays awake, as the reference's object does (awake_ is set by the first
+    // event and never cleared, :374): the router sends a lane's awake record once, so S_AWAKE must survive here - cleared with the
+    // rest, an instrument that had played stayed silent for good after mlgpu_events_clear / mlgpu_events_set_protocol.
+    const size_t lanes = ev->router.lanes(), group = (size_t)ev->router.group();
+    for (size_t i = 0; i < ev->router.instruments(); ++i)
+      if (ev->router.awakeSent(i))
+        for (size_t l = 0; l < group; ++l) st[(size_t)S_AWAKE * lanes + i * group + l] = 1u;
     if (hipSetDevice(ev->e->device) != hipSuccess) return efail(ev, MLGPU_ERR_HIP, "hipSetDevice");
     return mlgpu_upload(ev->e, ev->d_state.get(), st.data(), st.size() * sizeof(uint32_t));
   }
@@ -1217,10 +1348,32 @@ extern "C"
     ev->sr = sr;
     return markRecalc(ev);
   }
-  int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe)  // setProtocol clears (:92-96)
+  static int reserveCtlRecs(mlgpu_events* ev, size_t nVectors, uint32_t rowMask);
+  // setProtocol clears (:92-96). The buffers of events-as-graph-source-nodes are sized by the protocol's lanes: what
+  // mlgpu_events_reserve_for_graph[_rows] reserved (or an unreserved object grew) is made again for the new lane count, same vectors and
+  // rows, the old buffers retired through the engine - so a reserve survives the call. MLGPU_ERR_OOM: the old protocol stays in force
+  // (with buffers of its own size made again; only if even that fails is the object left without, and unreserved).
+  int mlgpu_events_set_protocol(mlgpu_events* ev, int mpe)
   {
     if (!ev) return MLGPU_ERR_INVALID;
-    ev->router.setProtocol(mpe != 0);
+    const bool was = ev->router.mpe(), now = mpe != 0;
+    if (ev->ctlRecVectors && was != now)
+    {
+      if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_set_protocol re-makes the buffers of events_reserve_for_graph: not while recording a sequence");
+      const size_t vectors = ev->ctlRecVectors;
+      const uint32_t rows = ev->ctlRowMask;
+      ev->router.setProtocol(now);
+      const int st = reserveCtlRecs(ev, vectors, rows);
+      if (st != MLGPU_OK)
+      {
+        ev->router.setProtocol(was);
+        if (reserveCtlRecs(ev, vectors, rows) != MLGPU_OK) ev->ctlRecReserved = false;
+        mlgpu_events_clear(ev);  // (the router's setProtocol dropped its key states: the device state goes with them)
+        return efail(ev, st, "events_set_protocol: control records and side signals for the new protocol's lanes; the old protocol stays in force");
+      }
+    }
+    else
+      ev->router.setProtocol(now);
     return mlgpu_events_clear(ev);
   }
   int mlgpu_events_set_unison(mlgpu_events* ev, int on) { return ev ? (ev->router.setUnison(on != 0), MLGPU_OK) : MLGPU_ERR_INVALID; }
@@ -1376,6 +1529,8 @@ extern "C"
     dev.recs = sg.d_recs.get();
     dev.recRange = ev->d_recRange.get();
     dev.lanes = router.lanes();
+    dev.group = router.group();
+    dev.slotBase = router.slotBase();
     return MLGPU_OK;
   }
   static int launched(mlgpu_events* ev, mlgpu_events::Staging& sg)
@@ -1468,7 +1623,6 @@ extern "C"
     if (!ev || maxVectors == 0) return MLGPU_ERR_INVALID;
     if (rowMask & ~0x7Fu) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events_reserve_for_graph_rows: rows 0 (pitch) to 6 (mod) can be source nodes of a graph");
     if (ev->e->recording) return efail(ev, MLGPU_ERR_INVALID, "events_reserve_for_graph allocates: not while recording a sequence");
-    if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
     if (maxVectors != ev->ctlRecVectors || (rowMask & kCtlRowsMask) != ev->ctlRowMask)
     {
       const int st = reserveCtlRecs(ev, maxVectors, rowMask);
@@ -1488,12 +1642,14 @@ extern "C"
 
   // for graph.hip: a graph whose event rows are bound to this object (mlgpu_graph_bind_events)
   // rowMask: the graph's event rows (bit r = row r; only z, x, y, mod - bits 3..6 - need memory and work of their own here)
-  int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, unsigned rowMask, EventsDev* dev, void** staging)
+  // mpeForm: the graph's kernel is the MPE-capable form (mlgpu_graph_enable_mpe_events); every other kernel takes a voice for a lane
+  int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, unsigned rowMask, int mpeForm, EventsDev* dev, void** staging)
   {
     if (!ev || !dev || !staging) return MLGPU_ERR_INVALID;
     if (nVectors == 0) return MLGPU_OK;
     if (const int st = checkBeforeRouting(ev, nVectors)) return st;
-    if (ev->router.mpe()) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
+    const bool mpe = ev->router.mpe();
+    if (mpe && !mpeForm) return efail(ev, MLGPU_ERR_UNSUPPORTED, "events as graph source nodes: MIDI protocol only (one lane per voice)");
     if (ev->router.aheadPending() && !ev->router.aheadIs(nVectors, startOffset)) return efail(ev, MLGPU_ERR_INVALID, kAheadPending);
     mlgpu_engine* e = ev->e;
     const size_t lanes = ev->router.lanes();
@@ -1523,13 +1679,18 @@ extern "C"
     a.ctl = ev->d_ctlRecs.get();
     a.rowP = (float4*)ev->d_rowP.get();
     a.rowG = (float4*)ev->d_rowG.get();
+    a.group = dev->group;
+    a.slotBase = dev->slotBase;
     if (ctlRows)  // the instance that also runs the controller glides the graph reads
     {
       a.held = ev->d_held.get();
       for (int r = 0; r < 4; ++r) a.rowC[r] = (float4*)ev->d_rowC[r].get();
       a.rowMask = ctlRows;
-      hipLaunchKernelGGL(e2s_ctl_rows_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
+      if (mpe) hipLaunchKernelGGL(e2s_ctl_rows_mpe_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
+      else hipLaunchKernelGGL(e2s_ctl_rows_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     }
+    else if (mpe)
+      hipLaunchKernelGGL(e2s_ctl_mpe_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     else
       hipLaunchKernelGGL(e2s_ctl_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream(), a);
     const hipError_t err = hipGetLastError();

@@ -59,6 +59,7 @@ class EventRouter
   int group() const { return group_; }
   int slotBase() const { return slotBase_; }
   bool mpe() const { return mpe_; }
+  bool awakeSent(size_t instrument) const { return inst[instrument].awakeSent; }  // its awake records have gone out: they go out once
   size_t lanes() const { return inst.size() * (size_t)group_; }
   size_t maxLanes() const { return laneRecs.size(); }  // lanes() of the wider protocol (MPE)
 

@@ -467,7 +467,7 @@ extern "C"
     if (g->job) return MLGPU_ERR_BUSY;
     if (!g->desc.hasEventRows) return gfail(g, MLGPU_ERR_INVALID, "graph_bind_events: the graph has no event rows (graph_add_event_row)");
     if (mlgpu_events_engine(ev) != g->e) return gfail(g, MLGPU_ERR_INVALID, "graph_bind_events: the events object belongs to another engine");
-    if (!mlgpu_events_is_midi(ev)) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_bind_events: MIDI protocol only (one lane per voice)");
+    if (!g->desc.mpeEvents && !mlgpu_events_is_midi(ev)) return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_bind_events: MIDI protocol only (one lane per voice)");
     if (mlgpu_events_num_voices(ev) != g->desc.V) return gfail(g, MLGPU_ERR_INVALID, "graph_bind_events: instruments x polyphony must equal the graph's voices");
     {
       std::lock_guard<std::mutex> lock(g_boundMutex);  // (mlgpu_graph_forget_events reads and clears g->events under the same lock)
@@ -1215,6 +1215,15 @@ extern "C"
     if (on) g->desc.voiceLists = true;
     return MLGPU_OK;
   }
+  // The plain kernel of a graph with event rows in its MPE-capable form (mlev::CtlVoiceMpe / CtlRowsMpe): the graph binds to an events
+  // object in either protocol and mlgpu_graph_process_events serves the protocol the object has at the call. The listed forms keep
+  // their text and their refusal under MPE.
+  int mlgpu_graph_enable_mpe_events(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_mpe_events: before mlgpu_graph_compile")) return st;
+    g->desc.mpeEvents = on != 0;
+    return MLGPU_OK;
+  }
   // ... and the listed form goes by the host's lane plan: the graph's group-summed outputs get one row per listed instrument
   // (mlgpu_graph_process_listed_groups). on = 1 turns voice lists on too; mlgpu_graph_enable_voice_lists(g, 0) turns both off.
   int mlgpu_graph_enable_voice_list_groups(mlgpu_graph* g, int on)
@@ -1423,7 +1432,7 @@ extern "C"
     if (!g->desc.hasEventRows) return MLGPU_OK;
     if (!g->events) return gfail(g, MLGPU_ERR_INVALID, "graph_process: the graph has event rows but no events object (graph_bind_events)");
     if (g->eventOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with event rows is run with mlgpu_graph_process_events");
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, g->desc.eventRowMask, &a.events, staging);
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, g->desc.eventRowMask, g->desc.mpeEvents ? 1 : 0, &a.events, staging);
     g->eventOffset = -1;
     return est == MLGPU_OK ? est : gfail(g, est, "graph_process: the events object refused the block: " + g->e->lastError);
   }
@@ -1546,7 +1555,7 @@ extern "C"
     const auto who = [who0] { return std::string(who0); };
     *staging = nullptr;
     if (eventOffset < 0) return MLGPU_OK;
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, &a.events, staging);
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, 0, &a.events, staging);
     return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
   }
   // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)

@@ -312,7 +312,9 @@ struct GraphEmitter
     ringTrips = p.rings == RingLayout::SECTORS && p.totalRings;  // ring layout 4: trips of two quads, every ring's loads in the trip's prologue
     evVoice = (g.eventRowMask & 3u) != 0;
     evRows = g.eventRowMask & 0x7Cu;
+    evMpe = g.mpeEvents && !listed && !planned;
   }
+  bool evMpe{false};     // ... in the forms for either protocol (mlgpu_graph_enable_mpe_events: the plain kernel only)
   bool evVoice{false};   // the graph reads pitch or gate: mlev::CtlVoice
   unsigned evRows{0};    // its rows among vox, z, x, y, mod (bit r = row r): mlev::CtlRows<evRows>, emitted only where there is one
   static std::string sfx(int l) { return "_" + std::to_string(l); }
@@ -529,10 +531,10 @@ struct GraphEmitter
     // stored except by a LATER instruction that wants the stored value (slot 63 and the first quad's slots at the next begin_vector).
     // (CtlVoice where the graph reads pitch or gate; the rows vox, z, x, y, mod are mlev::CtlRows', which only reads - by the same voice)
     if (evVoice)
-      for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
+      for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice" << (evMpe ? "Mpe" : "") << " ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
     if (evRows)
       for (int l = 0; l < VL; ++l)
-        s << "  mlev::CtlRows<" << evRows << "u> er" << sfx(l) << ";\n  er" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
+        s << "  mlev::CtlRows" << (evMpe ? "Mpe" : "") << "<" << evRows << "u> er" << sfx(l) << ";\n  er" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
     // Streamed inputs one quad (or one trip) ahead: a wavefront that loads a quad and waits for it right away stands still for a
     // whole HBM round trip per quad, and with four wavefronts per SIMD there are long stretches with only one or two of them able to
     // issue (one wavefront alone issues at 40 % of the SIMD's rate). The very last quad of a launch loads itself again.
@@ -646,7 +648,7 @@ struct GraphEmitter
       for (int l = 0; l < VL; ++l) s << "      f32x4 y" << o << sfx(l) << ";\n";
     if (evVoice)
       for (int l = 0; l < VL; ++l)
-        s << "      mlev::CtlVoice::f32x4e evP" << sfx(l) << ", evG" << sfx(l) << ";\n      ev" << sfx(l) << ".quad(t, q, evP" << sfx(l) << ", evG" << sfx(l) << ");\n";
+        s << "      mlev::CtlVoice" << (evMpe ? "Mpe" : "") << "::f32x4e evP" << sfx(l) << ", evG" << sfx(l) << ";\n      ev" << sfx(l) << ".quad(t, q, evP" << sfx(l) << ", evG" << sfx(l) << ");\n";
     if (evRows)
       for (int l = 0; l < VL; ++l)
       {
@@ -934,7 +936,8 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   // a bank whose last wavefront is not full: its spare lanes run the last voice again (GraphEmitter) - not where voices are
   // summed in groups inside the kernel or read event records, which go by lane
   // (mlgpu_graph_enable_voice_list_events: the event rows go by voice - CtlVoice below - and a spare lane's are the last voice's)
-  bool groupedOrEvents = g.hasEventRows && !g.voiceListEvents;
+  // (mlgpu_graph_enable_mpe_events: CtlVoiceMpe goes by voice as well - the voice's lane and its main lane are made of the voice index)
+  bool groupedOrEvents = g.hasEventRows && !g.voiceListEvents && !g.mpeEvents;
   for (size_t o = 0; o < g.outputs.size(); ++o) groupedOrEvents = groupedOrEvents || g.outputGroup[o] != 0;
   const bool partialOk = g.V % 64 == 0 || !groupedOrEvents;
   if (p.rings == RingLayout::TRANSPOSED && p.totalRings && !partialOk)

@@ -106,6 +106,7 @@ struct GraphDesc
   bool autotune{false};
   bool voiceLists{false};        // a compile makes the listed form of the kernel too (mlgpu_graph_enable_voice_lists)
   bool voiceListGroups{false};   // ... and that form goes by the host's lane plan, its group-summed outputs one row per listed instrument (mlgpu_graph_enable_voice_list_groups)
+  bool mpeEvents{false};         // the plain kernel's event rows in the MPE-capable form: mlev::CtlVoiceMpe / CtlRowsMpe (mlgpu_graph_enable_mpe_events)
   bool voiceListEvents{false};   // ... and a graph with event rows has it too: CtlVoice of the gathered voice (mlgpu_graph_enable_voice_list_events)
 };
 

@@ -3,7 +3,8 @@
 // graph, never written to memory): the kernels' arguments (the record format and the state layout are mlev_format.hpp), LinearGlide
 // with its 64 slots, note_frame - one frame of a vector that holds note records - and CtlVoice: the control records of
 // e2s_ctl_kernel expanded to the pitch and gate rows inside a voice kernel, one quad of frames at a time - and CtlRows, which reads
-// the rows vox, z, x, y and mod that the control kernel makes for a graph that has them as source nodes.
+// the rows vox, z, x, y and mod that the control kernel makes for a graph that has them as source nodes. CtlVoiceMpe and CtlRowsMpe are
+// the two for an events object in either protocol (mlgpu_graph_enable_mpe_events): a voice's lane and its instrument's main lane.
 #pragma once
 #include "mlgpu_device_args.hpp"
 #include "mldsp_math.hpp"
@@ -626,6 +627,300 @@ struct CtlRows
       if (any[k])
       {
         if (flags & CF_ROW(R)) v = __builtin_nontemporal_load((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2)));
+      }
+      return v;
+    }
+  }
+};
+
+// ---- the same two objects for an events object in either protocol (mlgpu_graph_enable_mpe_events) --------------------------------
+// The protocol is data (E2SSettings::mpe, group, slotBase: a host switches it at run time), so a voice is no longer a lane:
+//   lane of graph voice v = (v / polyphony) * group + (1 + v % polyphony) - slotBase,   its instrument's first lane = (v / polyphony) * group
+// which is v itself under MIDI (group = polyphony, slotBase = 1) and skips the main voice's lane and the padding under MPE (group =
+// nextpow2(polyphony + 1), slotBase = 0). Records, side signals, the held plane and the drift glide's words go by lane; vox stays
+// v % polyphony. Under MPE (:447-458, e2s_kernel's withMain) the main voice's pitch, z, x, y and mod are added to every playing voice
+// that is on: the main lane's record of a vector (e2s_ctl_mpe_kernel: its COMPLETE pitch row, drift term included, in C_PITCH or, where
+// it moves, in rowP), its flags and its held words are fetched with the voice's own; its frames are read only where the main lane is
+// flagged (asked wave-uniformly: several instruments share a wavefront, one may straddle two). All voices of an instrument read the
+// same addresses: one fetch from cache. Nothing new is stored. Every `mpe` branch is on a scalar of EventsDev; under MIDI the
+// operations on a voice's values are CtlVoice's and CtlRows' own.
+struct CtlVoiceMpe
+{
+  typedef float f32x4e __attribute__((ext_vector_type(4)));
+  EventsDev d;    // (uniform)
+  size_t T;
+  BufRsrc glide;  // the drift glide's words [kGlideWords][lanes]
+  uint32_t rowBytes;   // 4 * lanes: one word of every lane
+  uint32_t laneBytes;  // 4 * the voice's lane
+  uint32_t mainBytes;  // 4 * its instrument's main lane (MPE)
+  Glide gd;
+  float P, gate;
+  bool on, rows, gateRow, moving, fetch, ramp;
+  bool anyRows, anyRamp, anyOff, anyFetch;  // wave-uniform
+  float nd[4];
+  float mP, nmP;       // the main voice's held pitch of this vector / of the next one
+  uint32_t nmF;        // ... and the next one's flags
+  bool mRows, anyMainRows;  // the main voice's pitch of this vector is in rowP; (wave-uniform) ... for some lane
+
+  MLD uint32_t glideWord(int w) const { return __builtin_amdgcn_raw_buffer_load_b32(glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
+  MLD void setGlideWord(int w, uint32_t x) const { __builtin_amdgcn_raw_buffer_store_b32(x, glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
+  MLD void fetchRecord(size_t t)  // into nd[]: C_PITCH, C_GATE, C_DRIFT_IN, C_FLAGS; MPE: the main lane's C_PITCH and C_FLAGS
+  {
+    const BufRsrc rec = lane_buffer(d.ctl + t * (size_t)kCtlRecWords * d.lanes, (size_t)kCtlRecWords * rowBytes);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) nd[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
+    if (d.s.mpe)
+    {
+      nmP = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_PITCH * rowBytes), 0));
+      nmF = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_FLAGS * rowBytes), 0);
+    }
+  }
+  MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
+  {
+    d = a;
+    T = nVectors;
+    rowBytes = (uint32_t)d.lanes * 4u;
+    const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;  // (the one division of a launch)
+    const uint32_t main = inst * (uint32_t)d.group;
+    mainBytes = main * 4u;
+    laneBytes = (main + 1u + ((uint32_t)voice - inst * (uint32_t)d.s.polyphony) - (uint32_t)d.slotBase) * 4u;
+    mP = nmP = 0.f;
+    nmF = 0u;
+    mRows = anyMainRows = false;
+    glide = lane_buffer(d.state + (size_t)(S_GLIDES + 5 * kGlideWords) * d.lanes, (size_t)kGlideWords * rowBytes);  // glide 5: drift
+    gd.target = u2f(glideWord(0));
+    gd.step = u2f(glideWord(1));
+    gd.remaining = (int32_t)glideWord(2);
+    gd.modeFlags = glideWord(3) ? 4 : 0;
+    gd.uniformValue = u2f(glideWord(4));
+    gd.startValue = 0.f;
+    fetchRecord(0);
+  }
+  MLD void store() const
+  {
+    setGlideWord(0, f2u(gd.target));
+    setGlideWord(1, f2u(gd.step));
+    setGlideWord(2, (uint32_t)gd.remaining);
+    setGlideWord(3, gd.isUniform() ? 1u : 0u);
+    setGlideWord(4, f2u(gd.uniformValue));
+  }
+
+  MLD void begin_vector(size_t t)
+  {
+    (void)t;
+    const uint32_t f = f2u(nd[C_FLAGS]);
+    const float din = nd[C_DRIFT_IN];
+    on = (f & CF_ON) != 0;
+    rows = (f & CF_ROWS) != 0;
+    gateRow = (f & CF_GATE_ROW) != 0;
+    P = on ? nd[C_PITCH] : 0.f;
+    gate = on ? nd[C_GATE] : 0.f;
+    if (d.s.mpe)
+    {
+      mP = nmP;  // (0 while the main voice is not on: e2s_ctl_mpe_kernel writes it so)
+      mRows = (nmF & CF_ROWS) != 0;
+      anyMainRows = __builtin_amdgcn_ballot_w64(mRows) != 0;
+    }
+    float slot63 = 0.f;
+    const bool starts = on && ((din != gd.target) || gd.remaining == d.s.driftGlideVectors) && !gd.isUniform();
+    if (__builtin_amdgcn_ballot_w64(starts) != 0)
+    {
+      if (starts) slot63 = u2f(glideWord(5 + 63));
+    }
+    if (on) gd.beginVectorKnown(din, d.s.driftGlideVectors, d.s.driftGlideDy, slot63);
+    const int m = gd.mode();
+    moving = on && m >= 2;
+    ramp = on && m == 2;
+    fetch = on && gd.readsCurrVec();
+    const float hv = (m == 1) ? gd.target : gd.uniformValue;
+    anyRows = __builtin_amdgcn_ballot_w64(rows) != 0;
+    anyRamp = __builtin_amdgcn_ballot_w64(ramp) != 0;
+    anyOff = __builtin_amdgcn_ballot_w64(!on) != 0;
+    anyFetch = __builtin_amdgcn_ballot_w64(fetch) != 0;
+    nd[0] = nd[1] = nd[2] = nd[3] = hv;
+    if (anyFetch)
+    {
+      if (fetch)
+      {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) nd[k] = u2f(glideWord(5 + k));
+      }
+    }
+  }
+
+  MLD void quad(size_t t, int q, f32x4e& oPitch, f32x4e& oGate)
+  {
+    const float prev[4] = {nd[0], nd[1], nd[2], nd[3]};
+    if (q < 15)
+    {
+      if (anyFetch)
+      {
+        if (fetch)
+        {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) nd[k] = u2f(glideWord(5 + 4 * q + 4 + k));
+        }
+      }
+    }
+    else if (t + 1 < T)
+      fetchRecord(t + 1);
+    f32x4e Pq = {P, P, P, P};
+    oGate = f32x4e{gate, gate, gate, gate};
+    if (anyRows)
+    {
+      if (rows)
+      {
+        const size_t at = (t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2);
+        Pq = __builtin_nontemporal_load((const f32x4e*)d.rowP + at);
+        if (gateRow) oGate = __builtin_nontemporal_load((const f32x4e*)d.rowG + at);
+      }
+    }
+    float c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = prev[k] + gd.step;  // a continuing glide: mCurrVec[n] += step (LinearGlide, MLDSPGens.h:497-505)
+    if (anyRamp)  // a glide's first vector ramps from its start value (:481-495)
+    {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+      {
+        const float r = gd.startValue + ((float)(4 * q + k + 1) * 0.015625f) * gd.step;
+        c[k] = ramp ? r : c[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+      const float driftSig = moving ? c[k] : prev[k];
+      oPitch[k] = Pq[k] + (driftSig * d.s.driftAmount) * 0.02f;  // kDriftScale, :247
+    }
+    if (d.s.mpe)  // the main voice's pitch row, added to every playing voice that is on (:447-458)
+    {
+      f32x4e M = {mP, mP, mP, mP};
+      if (anyMainRows)
+      {
+        if (mRows) M = *((const f32x4e*)d.rowP + ((t * 16 + (size_t)q) * d.lanes + (size_t)(mainBytes >> 2)));
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) oPitch[k] = on ? oPitch[k] + M[k] : oPitch[k];
+    }
+    if (anyOff)  // voices of instruments that have not seen an event yet: processVector is a no-op, the rows are zero (:383-386)
+    {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) oPitch[k] = on ? oPitch[k] : 0.f;
+    }
+    if (moving)
+    {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) setGlideWord(5 + 4 * q + k, f2u(c[k]));
+    }
+  }
+
+  MLD void end_vector()
+  {
+    if (on) gd.endVector();
+  }
+};
+
+template <uint32_t MASK>
+struct CtlRowsMpe
+{
+  typedef float f32x4e __attribute__((ext_vector_type(4)));
+  static constexpr int N = ctl_row_count(MASK);
+  static constexpr int NA = N ? N : 1;
+  EventsDev d;  // (uniform)
+  size_t T;
+  uint32_t rowBytes, laneBytes, mainBytes;
+  float vox;
+  float hv[NA], nx[NA];      // the held values of this vector / of the next one (fetched during this vector's last quad)
+  float mhv[NA], mnx[NA];    // ... and the main voice's (MPE)
+  uint32_t flags, nflags;    // C_FLAGS of the two
+  uint32_t mflags, nmflags;  // ... and the main voice's
+  bool any[NA], anyM[NA];    // wave-uniform: some lane has the row / the main voice's row flagged in this vector
+
+  MLD void fetch(size_t t)
+  {
+    if constexpr (N > 0)
+    {
+      const BufRsrc rec = lane_buffer(d.ctl + (t * (size_t)kCtlRecWords + (size_t)C_FLAGS) * d.lanes, rowBytes);
+      nflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, 0, 0);
+      const BufRsrc plane = lane_buffer(d.held + t * (size_t)N * d.lanes, (size_t)N * rowBytes);
+#pragma unroll
+      for (int k = 0; k < N; ++k) nx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
+      if (d.s.mpe)
+      {
+        nmflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, 0, 0);
+#pragma unroll
+        for (int k = 0; k < N; ++k) mnx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)mainBytes, (int)((uint32_t)k * rowBytes), 0));
+      }
+    }
+  }
+  MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
+  {
+    d = a;
+    T = nVectors;
+    rowBytes = (uint32_t)d.lanes * 4u;
+    const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;
+    const uint32_t slot0 = (uint32_t)voice - inst * (uint32_t)d.s.polyphony;
+    const uint32_t main = inst * (uint32_t)d.group;
+    mainBytes = main * 4u;
+    laneBytes = (main + 1u + slot0 - (uint32_t)d.slotBase) * 4u;
+    vox = (float)slot0;
+    flags = nflags = mflags = nmflags = 0u;
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+    {
+      hv[k] = nx[k] = mhv[k] = mnx[k] = 0.f;
+      any[k] = anyM[k] = false;
+    }
+    fetch(0);
+  }
+  MLD void begin_vector(size_t t)
+  {
+    (void)t;
+    if constexpr (N > 0)
+    {
+      flags = nflags;
+#pragma unroll
+      for (int k = 0; k < N; ++k) hv[k] = nx[k];
+#pragma unroll
+      for (int r = 3; r <= 6; ++r)
+        if ((MASK >> r) & 1u) any[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((flags & CF_ROW(r)) != 0) != 0;
+      if (d.s.mpe)
+      {
+        mflags = nmflags;
+#pragma unroll
+        for (int k = 0; k < N; ++k) mhv[k] = mnx[k];
+#pragma unroll
+        for (int r = 3; r <= 6; ++r)
+          if ((MASK >> r) & 1u) anyM[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((mflags & CF_ROW(r)) != 0) != 0;
+      }
+    }
+  }
+  MLD void quad(size_t t, int q)
+  {
+    if (q == 15 && t + 1 < T) fetch(t + 1);
+  }
+  template <int R>
+  MLD f32x4e row(size_t t, int q) const
+  {
+    static_assert(R >= 2 && R <= 6 && ((MASK >> R) & 1u), "a row of this graph");
+    if constexpr (R == 2) return f32x4e{vox, vox, vox, vox};
+    else
+    {
+      constexpr int k = ctl_row_rank(MASK, R);
+      f32x4e v = {hv[k], hv[k], hv[k], hv[k]};
+      if (any[k])
+      {
+        if (flags & CF_ROW(R)) v = __builtin_nontemporal_load((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2)));
+      }
+      if (d.s.mpe)  // the main voice's row, added where the voice is on (:447-458)
+      {
+        f32x4e m = {mhv[k], mhv[k], mhv[k], mhv[k]};
+        if (anyM[k])
+        {
+          if (mflags & CF_ROW(R)) m = *((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(mainBytes >> 2)));
+        }
+        if (flags & CF_ON) v = v + m;
       }
       return v;
     }

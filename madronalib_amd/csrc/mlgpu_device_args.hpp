@@ -98,6 +98,10 @@ struct EventsDev
   const uint32_t* held;
   const float4* rowC[4];
   uint32_t ctlRowMask;
+  // the protocol's lane layout (EventRouter::setProtocol): lane = instrument * group + (slot - slotBase), slot 0 the MPE main voice,
+  // slots 1..polyphony the playing voices. MIDI: group = polyphony, slotBase = 1 (lane == voice); MPE: group = nextpow2(polyphony + 1),
+  // slotBase = 0; s.mpe says which. Read by the MPE-capable forms only (mlev::CtlVoiceMpe, mlev::CtlRowsMpe).
+  int32_t group, slotBase;
 };
 
 // a fused graph kernel: up to MLGPU_GRAPH_MAX_INPUTS (32) streamed inputs, MLGPU_GRAPH_MAX_OUTPUTS (8) outputs, per-voice constants [P][V]

@@ -392,7 +392,7 @@ void mlgpu_build_impulse_table(float* out17);
 // the pitch and gate rows itself (mlgpu_graph_bind_events)
 struct mlgpu_events;
 extern "C" int mlgpu_events_abandoned_by_graph(mlgpu_events* ev, void* staging);
-extern "C" int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, unsigned rowMask, EventsDev* dev, void** staging);
+extern "C" int mlgpu_events_prepare_for_graph(mlgpu_events* ev, size_t nVectors, int startOffset, unsigned rowMask, int mpeForm, EventsDev* dev, void** staging);
 extern "C" int mlgpu_events_launched_by_graph(mlgpu_events* ev, void* staging);
 extern "C" int mlgpu_events_is_midi(mlgpu_events* ev);
 extern "C" mlgpu_engine* mlgpu_events_engine(mlgpu_events* ev);
