@@ -1257,9 +1257,10 @@ int mlgpu_graph_process_events(mlgpu_graph* g, size_t n_vectors, int start_offse
  *   voice kernel reads them with the voice's own and adds; nothing more is stored. Every voice and sample has the bits of
  *   mlgpu_events_process on an MPE object in the same state, and either call hands over to the other in any vector.
  *   Statuses. After a reserve, process calls under MPE never allocate and answer MLGPU_ERR_RANGE / MLGPU_ERR_INVALID exactly as under
- *   MIDI, before the router consumes anything; mlgpu_events_route_ahead stays legal for the plain call. The listed forms are not served:
- *   mlgpu_graph_process_events_listed[_groups] on an MPE object answers MLGPU_ERR_UNSUPPORTED naming MIDI, and
- *   mlgpu_events_sounding_voices stays refused under MPE. A graph built WITHOUT the switch keeps MLGPU_ERR_UNSUPPORTED at bind and at
+ *   MIDI, before the router consumes anything; mlgpu_events_route_ahead stays legal for the plain call. The listed forms are not served
+ *   by THIS switch: mlgpu_graph_process_events_listed[_groups] on an MPE object answers MLGPU_ERR_UNSUPPORTED naming MIDI, and
+ *   mlgpu_events_sounding_voices stays refused under MPE - mlgpu_graph_enable_voice_list_mpe_events and
+ *   mlgpu_events_sounding_graph_voices (below) serve them. A graph built WITHOUT the switch keeps MLGPU_ERR_UNSUPPORTED at bind and at
  *   every process call on an MPE object.
  *   mlgpu_events_set_protocol and reserves. The call clears, as ever. It now also makes the buffers of
  *   mlgpu_events_reserve_for_graph[_rows] again for the new protocol's lane count - same DSPVectors, same row mask, the old buffers
@@ -1336,8 +1337,62 @@ int mlgpu_graph_process_events_listed_groups(mlgpu_graph* g, size_t n_vectors, i
 int mlgpu_events_route_ahead(mlgpu_events* ev, size_t n_vectors, int start_offset);
 int mlgpu_events_sounding_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n);
 
+/* VOICE LISTS FOR GRAPHS WITH EVENT ROWS UNDER THE MPE PROTOCOL: an MPE instrument bank runs only the voices that sound.
+ *
+ * mlgpu_graph_enable_voice_list_mpe_events(g, 1) is a build call (after compile: MLGPU_ERR_INVALID naming "before mlgpu_graph_compile").
+ * on = 1 ALSO turns on mlgpu_graph_enable_voice_list_events (and through it mlgpu_graph_enable_voice_lists) and
+ * mlgpu_graph_enable_mpe_events; mlgpu_graph_enable_voice_lists(g, 0), mlgpu_graph_enable_voice_list_events(g, 0) and
+ * mlgpu_graph_enable_mpe_events(g, 0) turn it off with the rest. Without it nothing changes: every kernel's text, every status and
+ * every message (the MIDI-only refusal of the listed events calls goes on to name this switch). With it the graph's listed kernel -
+ * the plain list form, or the lane plan's with mlgpu_graph_enable_voice_list_groups as well - is generated around mlev::CtlVoiceMpe /
+ * CtlRowsMpe loaded with the gathered voice, which make the voice's lane and its instrument's main lane of the voice index (Lanes,
+ * above), and mlgpu_graph_process_events_listed / _listed_groups serve the protocol the bound object has AT THE CALL. Apart from the
+ * structs' names the switched listed source is the unswitched one. The checks of the reserve's length, the row mask and a routed-ahead
+ * launch stand; every status still comes before the router consumes anything; mlgpu_events_route_ahead is legal in either protocol.
+ *
+ * Bits. For a listed voice under MPE every row has the bits of mlgpu_events_process on an MPE object in the same state, with the
+ * qualification the MIDI listed form has:
+ *   gate and vox: always exact.
+ *   z, x, y, mod: the voice's own glide plus the main voice's. Both belong to the control kernel, which runs for every lane in every
+ *   call: exact from a relisted voice's first listed vector on.
+ *   pitch: the voice's bend and pitch glides and the WHOLE main-voice pitch row - the main voice's own drift glide included - are the
+ *   control kernel's and exact. The playing voice's own drift LinearGlide (glide 5, addressed by lane) is the voice kernel's: exact when
+ *   the drift amount is 0, or when the voice has been listed in every launch since the object was cleared; neither read nor written for
+ *   an unlisted voice.
+ *   Unlisted voices' graph state, coefficients, params, feedback and ring words are neither read nor written. An empty list launches no
+ *   voice kernel; the host half and the control kernel still run for every lane. Any split of n_vectors into launches gives the bits
+ *   of one launch. After listed blocks a block may be processed by mlgpu_graph_process_events or mlgpu_events_process; with drift 0 the
+ *   bits are those of never having used lists. Under MIDI the switched listed kernels give the bits of the listed kernels built with
+ *   mlgpu_graph_enable_voice_list_events alone: the protocol is data of the launch.
+ *   A listed wavefront holds voices of arbitrary instruments in arbitrary order: the main lane's frames are read wherever some lane's
+ *   main voice is flagged, by that lane, at its own main lane's address. With a mixed-down output the last wavefront's spare lanes run
+ *   the list's last voice - its lane and its main lane - again.
+ *
+ * mlgpu_events_sounding_graph_voices(ev, h_voices, capacity, &n): the set of mlgpu_events_sounding_voices in EITHER protocol, as graph
+ * voice indices instrument * polyphony + voice, ascending. The held velocities go by voice index in both protocols; a lane with records
+ * is mapped back (instrument = lane / G, slot = lane % G + slot base; slots 1..polyphony are voices, the main voice's lane and the
+ * padding lanes add nothing). The same validity window (after a route, until the next), the same MLGPU_ERR_RANGE rule (*n set, nothing
+ * written), no device access, no allocation. Under MIDI it returns exactly what mlgpu_events_sounding_voices returns, which is
+ * untouched, its refusal under MPE included. Step 3 of the intended block above becomes this call.
+ *   The guarantee: every voice whose GATE row is non-zero anywhere in the routed launch is in the set; the gate row gets nothing added
+ *   from the main voice. A channel-1 event (the main voice's bend, pressure, x, y, mod) is a record of the main lane only and adds no
+ *   voice: it changes rows of the instrument's voices that are on - those that are held are in the set already, those in a release tail
+ *   are the host's tails (step 4). The first event of an instrument wakes it: its awake records list all its voices once.
+ *
+ * Cost (profiles/graph_voice_list_events_mpe.md, with the compiler's figures per form). Under MPE a listed voice also reads its main
+ * voice's record, flags, held words and - where flagged - frames, and the kernel keeps them in registers: no form has scratch, with or
+ * without the switch (a listed kernel with event rows takes a wavefront bound only where it costs none), and the switch costs 15 to 36
+ * VGPRs. The instrument bank's voice at 262 144 voices, VGPRs without -> with the switch: pitch and gate only 129 -> 144 in the list
+ * form (three wavefronts per SIMD either way) and 157 -> 173 in the lane plan's (three -> two); with mod and z 145 -> 176 and
+ * 168 -> 204 (three -> two in both). So the switch costs a MIDI host a wavefront per SIMD in three of the four kernels: a host that
+ * never lists under MPE leaves it off. Measured, 16 384 x 16 voices: the list does not shorten an MPE bank's block - the control
+ * kernel, which runs for every lane, is two thirds of it, and the listed voice kernel is bound by one voice's latency (1.24 ms for 5 %
+ * of the voices against 1.26 ms for all of them); what the list frees is the chip's other SIMDs and the rows of all voices. */
+int mlgpu_graph_enable_voice_list_mpe_events(mlgpu_graph* g, int on);
+int mlgpu_events_sounding_graph_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n);
+
 /* ------------------------------------------------------------------------- */
-/* published signals                                                         */
+/* published signals                                                        */
 /*
  * SignalProcessor::PublishedSignal (source/app/MLSignalProcessor.h:26-105, MLSignalProcessor.cpp:9-38): a decimated,
  * frame-major copy of `channels` signals of a few voices for code outside the DSP calculation (displays). write() is

@@ -691,6 +691,16 @@ class Events(_Handle):
         self.engine._check(self.L.mlgpu_events_sounding_voices(self.h, _np_ptr(self._sounding), self._sounding.size, ctypes.byref(n)))
         return self._sounding[:n.value].copy()
 
+    def sounding_graph_voices(self):
+        """sounding_voices() in either protocol, as graph voice indices instrument * polyphony + voice (ascending, uint32): under MPE the
+        lanes with records are mapped back to voices, the main voice's lane and the padding add nothing
+        (mlgpu_events_sounding_graph_voices). Under MIDI exactly sounding_voices(). No device access."""
+        if getattr(self, "_sounding", None) is None:
+            self._sounding = np.zeros(self.V, np.uint32)
+        n = ctypes.c_size_t()
+        self.engine._check(self.L.mlgpu_events_sounding_graph_voices(self.h, _np_ptr(self._sounding), self._sounding.size, ctypes.byref(n)))
+        return self._sounding[:n.value].copy()
+
     def reserve_for_graph(self, max_vectors, rows=None):
         """Setup-time reserve of the control records and side signals a graph bound to this object needs for blocks of up to max_vectors
         DSPVectors (mlgpu_events_reserve_for_graph): from then on Graph.process_events never allocates and refuses longer blocks.
@@ -1234,7 +1244,7 @@ class Graph(_Handle):
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
                  live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False,
-                 voice_list_events=False, mpe_events=False):
+                 voice_list_events=False, mpe_events=False, voice_list_mpe_events=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1261,6 +1271,8 @@ class Graph(_Handle):
             self.enable_voice_list_events()
         if mpe_events:   # the plain kernel's event rows in the form for either protocol: bind_events / process_events take an MPE object
             self.enable_mpe_events()
+        if voice_list_mpe_events:   # ... and the listed forms too (turns voice_list_events and mpe_events on): process_events_listed[_groups] take an MPE object
+            self.enable_voice_list_mpe_events()
         if description is not None:
             for n in description:
                 self.add(**n)
@@ -1375,8 +1387,16 @@ class Graph(_Handle):
 
     def enable_mpe_events(self, on=True):
         """Before compile: the plain kernel of a graph with event rows is generated for either protocol of the bound Events object
-        (mlgpu_graph_enable_mpe_events) - process_events serves the protocol the object has at the call. The listed forms stay MIDI only."""
+        (mlgpu_graph_enable_mpe_events) - process_events serves the protocol the object has at the call. The listed forms stay MIDI only
+        unless enable_voice_list_mpe_events is on as well; enable_mpe_events(False) turns that off too."""
         self._check(self.L.mlgpu_graph_enable_mpe_events(self.h, 1 if on else 0))
+
+    def enable_voice_list_mpe_events(self, on=True):
+        """Before compile: the listed kernel of a graph with event rows - the plain list form, or the lane plan's - is generated for either
+        protocol of the bound Events object (mlgpu_graph_enable_voice_list_mpe_events): process_events_listed[_groups] serve the protocol
+        the object has at the call, Events.sounding_graph_voices() makes the list. on=True also turns on enable_voice_list_events (and
+        voice lists) and enable_mpe_events; enable_voice_lists(False) and enable_mpe_events(False) turn it off with the rest."""
+        self._check(self.L.mlgpu_graph_enable_voice_list_mpe_events(self.h, 1 if on else 0))
 
     def enable_voice_list_events(self, on=True):
         """Before compile: voice lists, also for a graph with event rows - its listed kernel expands the control records of the gathered

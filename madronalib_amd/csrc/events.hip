@@ -1734,6 +1734,16 @@ extern "C"
       return efail(ev, MLGPU_ERR_RANGE, "events_sounding_voices: " + std::to_string(*n) + " voices sound, the caller's memory holds " + std::to_string(capacity));
     return MLGPU_OK;
   }
+  // ... in either protocol, as graph voice indices instrument * polyphony + voice (EventRouter::soundingGraphVoices): what a host of
+  // mlgpu_graph_enable_voice_list_mpe_events makes its list of. Under MIDI the set above.
+  int mlgpu_events_sounding_graph_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n)
+  {
+    if (!ev || !n || (capacity && !h_voices)) return MLGPU_ERR_INVALID;
+    *n = 0;
+    if (!ev->router.soundingGraphVoices(h_voices, capacity, n))
+      return efail(ev, MLGPU_ERR_RANGE, "events_sounding_graph_voices: " + std::to_string(*n) + " voices sound, the caller's memory holds " + std::to_string(capacity));
+    return MLGPU_OK;
+  }
   // the graph's voice kernel could not be launched after prepare_for_graph had succeeded (e2s_ctl_kernel has consumed the lanes' record
   // ranges by then, or will: abandonRanges puts back whatever it has not, stream-ordered, and submits the staging set's turn)
   int mlgpu_events_abandoned_by_graph(mlgpu_events* ev, void* staging)

@@ -335,6 +335,27 @@ bool EventRouter::soundingVoices(uint32_t* voices, size_t capacity, size_t* n) c
   return true;
 }
 
+bool EventRouter::soundingGraphVoices(uint32_t* voices, size_t capacity, size_t* n) const
+{
+  *n = 0;
+  sounding = held;  // (same size: no allocation; held goes by voice index in both protocols - setHeld)
+  for (uint32_t l : dirtyLanes)
+  {
+    const size_t instrument = (size_t)l / (size_t)group_;
+    const int slot = (int)((size_t)l % (size_t)group_) + slotBase_;  // voices[] index: 0 the MPE main voice, above polyphony the padding
+    if (slot < 1 || slot > polyphony_ || instrument >= inst.size()) continue;
+    const size_t v = instrument * (size_t)polyphony_ + (size_t)(slot - 1);
+    sounding[v >> 6] |= (uint64_t)1 << (v & 63);
+  }
+  size_t count = 0;
+  for (uint64_t w : sounding) count += (size_t)__builtin_popcountll(w);
+  *n = count;
+  if (count > capacity) return false;
+  for (size_t i = 0; i < sounding.size(); ++i)
+    for (uint64_t w = sounding[i]; w; w &= w - 1) *voices++ = (uint32_t)(i * 64 + (size_t)__builtin_ctzll(w));
+  return true;
+}
+
 bool EventRouter::route(size_t nVectors, int startOffset)
 {
   if (ahead_)  // routed already: the records stand as routeAhead left them

@@ -100,6 +100,17 @@ class EventRouter
   // the bitmap's words and the launch's lanes with records, not a walk over the voices. *n: the set's size, also when it is larger than
   // `capacity` (false then, and nothing written). MIDI protocol only (false under MPE with *n = 0).
   bool soundingVoices(uint32_t* voices, size_t capacity, size_t* n) const;
+  // The same set in either protocol, as GRAPH voice indices instrument * polyphony + voice, ascending: `held` goes by voice index in
+  // both protocols, and a lane with records is mapped back - instrument l / group, slot l % group + slotBase; a slot in 1..polyphony
+  // is voice instrument * polyphony + slot - 1, slot 0 (the MPE main voice) and the padding lanes add nothing. Under MIDI exactly
+  // soundingVoices' set. The same scratch bitmap, no allocation, the same rule for `capacity`.
+  // The guarantee: every voice whose GATE row is non-zero anywhere in the routed launch is in the set - a gate rises by a note record
+  // of the voice's own lane and stays up only while its velocity is held, and the gate row gets nothing added from the main voice.
+  // What an MPE channel-1 event (bend, pressure, controllers 74 / 73 / mod on the main voice) means for the host: it is a record of
+  // the main lane alone and adds no voice. It changes the pitch, z, x, y and mod rows of the instrument's voices that are ON: those
+  // that are held are in the set already, those in a release tail are the host's tails - the host keeps listing a released voice
+  // until its peak has died away, and while it does the voice reads the main voice's rows like any listed voice.
+  bool soundingGraphVoices(uint32_t* voices, size_t capacity, size_t* n) const;
 
   void initialVoiceState(std::vector<uint32_t>& st) const;       // [kStateWords][lanes()]: freshly constructed / reset voices
   void initialControllerState(std::vector<uint32_t>& st) const;  // [kCtlWords][ctlLanes()]: smoothers settled on the current inputs

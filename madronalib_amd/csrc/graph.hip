@@ -1203,7 +1203,7 @@ extern "C"
   {
     if (const int st = checkEditable(g, "graph_enable_voice_lists: before mlgpu_graph_compile")) return st;
     g->desc.voiceLists = on != 0;
-    if (!on) g->desc.voiceListGroups = g->desc.voiceListEvents = false;
+    if (!on) g->desc.voiceListGroups = g->desc.voiceListEvents = g->desc.voiceListMpeEvents = false;
     return MLGPU_OK;
   }
   // ... and a graph with event rows has a listed form as well (mlgpu_graph_process_events_listed[_groups]): CtlVoice of the gathered
@@ -1213,15 +1213,28 @@ extern "C"
     if (const int st = checkEditable(g, "graph_enable_voice_list_events: before mlgpu_graph_compile")) return st;
     g->desc.voiceListEvents = on != 0;
     if (on) g->desc.voiceLists = true;
+    else g->desc.voiceListMpeEvents = false;  // (the MPE-capable listed form is a listed form of the event rows)
+    return MLGPU_OK;
+  }
+  // ... in the form for either protocol (mlev::CtlVoiceMpe / CtlRowsMpe of the gathered voice): mlgpu_graph_process_events_listed[_groups]
+  // then serve the protocol the bound object has at the call. on = 1 turns on mlgpu_graph_enable_voice_list_events (and through it voice
+  // lists) and mlgpu_graph_enable_mpe_events; mlgpu_graph_enable_voice_lists(g, 0), mlgpu_graph_enable_voice_list_events(g, 0) and
+  // mlgpu_graph_enable_mpe_events(g, 0) turn it off with the rest.
+  int mlgpu_graph_enable_voice_list_mpe_events(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_voice_list_mpe_events: before mlgpu_graph_compile")) return st;
+    g->desc.voiceListMpeEvents = on != 0;
+    if (on) g->desc.voiceLists = g->desc.voiceListEvents = g->desc.mpeEvents = true;
     return MLGPU_OK;
   }
   // The plain kernel of a graph with event rows in its MPE-capable form (mlev::CtlVoiceMpe / CtlRowsMpe): the graph binds to an events
   // object in either protocol and mlgpu_graph_process_events serves the protocol the object has at the call. The listed forms keep
-  // their text and their refusal under MPE.
+  // their text and their refusal under MPE unless mlgpu_graph_enable_voice_list_mpe_events is on as well.
   int mlgpu_graph_enable_mpe_events(mlgpu_graph* g, int on)
   {
     if (const int st = checkEditable(g, "graph_enable_mpe_events: before mlgpu_graph_compile")) return st;
     g->desc.mpeEvents = on != 0;
+    if (!on) g->desc.voiceListMpeEvents = false;
     return MLGPU_OK;
   }
   // ... and the listed form goes by the host's lane plan: the graph's group-summed outputs get one row per listed instrument
@@ -1535,7 +1548,9 @@ extern "C"
     if (eventOffset < 0)
       return g->desc.hasEventRows ? gfail(g, MLGPU_ERR_INVALID, who() + ": a graph with event rows is run with mlgpu_graph_process_events_listed[_groups]") : MLGPU_OK;
     if (!g->events) return gfail(g, MLGPU_ERR_INVALID, who() + ": the graph has event rows but no events object (graph_bind_events)");
-    if (!mlgpu_events_is_midi(g->events)) return gfail(g, MLGPU_ERR_UNSUPPORTED, who() + ": events as graph source nodes: MIDI protocol only (one lane per voice)");
+    if (!g->desc.voiceListMpeEvents && !mlgpu_events_is_midi(g->events))
+      return gfail(g, MLGPU_ERR_UNSUPPORTED, who() + ": events as graph source nodes: MIDI protocol only (one lane per voice) - mlgpu_graph_enable_voice_list_mpe_events(g, 1) "
+                                                     "before compile makes the listed form for either protocol");
     return MLGPU_OK;
   }
   // The first checks of the two events calls: the switch, the graph's event rows, the offset
@@ -1555,7 +1570,7 @@ extern "C"
     const auto who = [who0] { return std::string(who0); };
     *staging = nullptr;
     if (eventOffset < 0) return MLGPU_OK;
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, 0, &a.events, staging);
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, g->desc.voiceListMpeEvents ? 1 : 0, &a.events, staging);
     return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
   }
   // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)

@@ -312,9 +312,11 @@ struct GraphEmitter
     ringTrips = p.rings == RingLayout::SECTORS && p.totalRings;  // ring layout 4: trips of two quads, every ring's loads in the trip's prologue
     evVoice = (g.eventRowMask & 3u) != 0;
     evRows = g.eventRowMask & 0x7Cu;
-    evMpe = g.mpeEvents && !listed && !planned;
+    evMpe = g.mpeEvents && ((!listed && !planned) || g.voiceListMpeEvents);
   }
-  bool evMpe{false};     // ... in the forms for either protocol (mlgpu_graph_enable_mpe_events: the plain kernel only)
+  // ... in the forms for either protocol (mlgpu_graph_enable_mpe_events: the plain kernel; mlgpu_graph_enable_voice_list_mpe_events: the
+  // listed and the planned form too - CtlVoiceMpe / CtlRowsMpe make the voice's lane and its main lane of the gathered voice index)
+  bool evMpe{false};
   bool evVoice{false};   // the graph reads pitch or gate: mlev::CtlVoice
   unsigned evRows{0};    // its rows among vox, z, x, y, mod (bit r = row r): mlev::CtlRows<evRows>, emitted only where there is one
   static std::string sfx(int l) { return "_" + std::to_string(l); }
@@ -530,6 +532,12 @@ struct GraphEmitter
     // a word's loads and stores are issued by the same instructions for all of them; and within a launch no word is loaded after it was
     // stored except by a LATER instruction that wants the stored value (slot 63 and the first quad's slots at the next begin_vector).
     // (CtlVoice where the graph reads pitch or gate; the rows vox, z, x, y, mod are mlev::CtlRows', which only reads - by the same voice)
+    // The listed forms for either protocol (mlgpu_graph_enable_voice_list_mpe_events): all of the above holds for CtlVoiceMpe - its stores
+    // are CtlVoice's, by the voice's lane, a function of v alone - and what it adds is read-only: the main lane's record, held words and
+    // frames, by an address made of v. Nothing in the two structs looks at a neighbouring lane or assumes a wavefront of one instrument's
+    // voices: the ballots ask "some lane of the wavefront" and each lane then goes by its own flag, so a wavefront of voices of arbitrary
+    // instruments in arbitrary order reads each flagged main lane's frames where they are. A spare lane reads the last voice's lane and
+    // main lane again.
     if (evVoice)
       for (int l = 0; l < VL; ++l) s << "  mlev::CtlVoice" << (evMpe ? "Mpe" : "") << " ev" << sfx(l) << ";\n  ev" << sfx(l) << ".load(a.events, v" << sfx(l) << ", a.T);\n";
     if (evRows)

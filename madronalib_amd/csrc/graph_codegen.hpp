@@ -108,6 +108,7 @@ struct GraphDesc
   bool voiceListGroups{false};   // ... and that form goes by the host's lane plan, its group-summed outputs one row per listed instrument (mlgpu_graph_enable_voice_list_groups)
   bool mpeEvents{false};         // the plain kernel's event rows in the MPE-capable form: mlev::CtlVoiceMpe / CtlRowsMpe (mlgpu_graph_enable_mpe_events)
   bool voiceListEvents{false};   // ... and a graph with event rows has it too: CtlVoice of the gathered voice (mlgpu_graph_enable_voice_list_events)
+  bool voiceListMpeEvents{false};  // ... in the form for either protocol: CtlVoiceMpe / CtlRowsMpe of the gathered voice (mlgpu_graph_enable_voice_list_mpe_events; implies the two above)
 };
 
 // Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them by planGraph)
