@@ -964,7 +964,8 @@ int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h
  * mlgpu_graph_compile / mlgpu_graph_emit refuse (MLGPU_ERR_UNSUPPORTED, the message names the reason, nothing is built) a graph with
  * voice lists enabled that the listed form does not serve:
  *   delay ring layouts 1, 2 and 4 - also where layout 3 resolves to one of them: their LDS windows and 64-byte pieces are made by a
- *   wavefront's neighbouring voices of one 256-voice block (layout 0, the rows, is served: mlgpu_graph_set_delay_layout(g, 0));
+ *   wavefront's neighbouring voices of one 256-voice block (layout 0, the rows, is served: mlgpu_graph_set_delay_layout(g, 0); with
+ *   mlgpu_graph_enable_voice_list_rings layouts 1 and 4 are served too: VOICE LISTS FOR GRAPHS WITH SECTOR DELAY RINGS);
  *   an output group sum (mlgpu_graph_set_output_group_sum) without mlgpu_graph_enable_voice_list_groups (below), with it a mixdown of
  *   all voices in either form and outputs summed by groups of different sizes or none at all; the shard form of a mixdown (mlgpu_graph_set_output_mixdown(.., 2));
  *   event rows (mlgpu_graph_add_event_row) without mlgpu_graph_enable_voice_list_events (VOICE LISTS FOR GRAPHS WITH EVENT ROWS); a MLGPU_REGION_DOWNSAMPLE_2X region (it pairs DSPVectors
@@ -1033,6 +1034,37 @@ size_t mlgpu_graph_listed_group_count(mlgpu_graph* g);
 int mlgpu_graph_listed_groups(mlgpu_graph* g, uint32_t* h_groups, size_t capacity);
 int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t n_vectors, const float* const* d_inputs, int in_layout,
                                       const float* const* d_controls, float* const* d_outputs, int out_layout, uint32_t* d_peak);
+/* VOICE LISTS FOR GRAPHS WITH SECTOR DELAY RINGS: the listed form of a graph whose delay rings are kept in ring layout 1 or 4 - the
+ * plucked-string and reverb banks, whose per-voice delay times make the rows (layout 0) pull a cache line for 4 bytes. Both layouts
+ * keep the ring of a 256-voice block as [sample / 8][voice][8]: a voice owns its 32-byte sectors, the kernels address that memory by
+ * the voice and their LDS windows by the lane, and nothing in them looks at a neighbouring lane - so a wavefront of gathered voices
+ * runs them as it stands. Layout 4's listed kernel runs its trips on each lane's own write clock (every lane on a sector boundary,
+ * not every lane at the same write index): voices that were off the list for different numbers of DSPVectors differ by multiples of
+ * 64. A listed voice whose write index a host set off a sector boundary sends its wavefront through memory sample by sample, with
+ * the same bits (a PitchbendableDelay's two write indices moved together; set apart they make two rings of that voice's, as ever only
+ * before the first launch after a clear).
+ *
+ * mlgpu_graph_enable_voice_list_rings(g, 1) is a build call like mlgpu_graph_enable_voice_lists, and turns that on too
+ * (mlgpu_graph_enable_voice_lists(g, 0) turns it off with the rest); it composes with mlgpu_graph_enable_voice_list_groups, _events and
+ * _mpe_events. Without the switch nothing changes: both kernels' text, and the refusal of voice lists with ring layouts 1, 2 and 4.
+ * With it mlgpu_graph_compile / mlgpu_graph_emit
+ *   serve layouts 1 and 4 next to voice lists, in the plain list form and the lane plan's;
+ *   resolve layout 3 to layout 4 where its LDS fits and no delay line sits in a rate region, else to layout 1 where its LDS fits, else
+ *   to the rows - never to layout 2. The plan is one value for both kernels: mlgpu_graph_process of such a graph uses that layout
+ *   too, and mlgpu_graph_delay_layout reports it;
+ *   refuse, naming the reason: MLGPU_ERR_UNSUPPORTED for layout 2 (its 64-byte pieces are moved by four neighbouring lanes of a block)
+ *   and for ring windows that do not fit a workgroup's LDS next to the lane plan's segment strips (the message has the sizes);
+ *   MLGPU_ERR_INVALID for a graph without a delay node (mlgpu_graph_enable_voice_lists serves it).
+ * One call is refused afterwards: mlgpu_graph_process (and _ctl, _events) of a graph with a PitchbendableDelay whose layout in effect
+ * is 4, after a listed launch and until the next mlgpu_graph_clear, and while recording a sequence (MLGPU_ERR_UNSUPPORTED). Such a node
+ * keeps ONE ring for a voice whose two write indices agree; the listed kernel decides that per voice, the plain kernel per wavefront,
+ * and a wavefront whose voices were listed for different numbers of DSPVectors would read a second ring that was never written. Run
+ * all voices through mlgpu_graph_process_listed with every voice listed. Every other graph may mix the calls: with IntegerDelay and
+ * FractionalDelay nodes the plain kernel is only slower on such a bank (sample by sample through memory), with the same bits.
+ * The process calls, d_peak and the one rule are unchanged: a listed call behaves as a graph of K voices made of the listed ones,
+ * ring words included, in every layout with the same bits; unlisted voices' rings are neither read nor written. MLGPU_UPDATE_CLEAR_RINGS
+ * clears a voice's sectors whether it is listed or not. */
+int mlgpu_graph_enable_voice_list_rings(mlgpu_graph* g, int on);
 
 /* Chains without an ahead-of-time kernel are fused with hiprtc when their bank is created
  * (default on). With jit off they run processor by processor through HBM scratch signals. */

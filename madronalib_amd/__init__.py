@@ -1244,7 +1244,7 @@ class Graph(_Handle):
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
                  live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False,
-                 voice_list_events=False, mpe_events=False, voice_list_mpe_events=False):
+                 voice_list_events=False, mpe_events=False, voice_list_mpe_events=False, voice_list_rings=False):
         self.engine = engine
         self.L = engine.L
         self.V = int(n_voices)
@@ -1267,6 +1267,8 @@ class Graph(_Handle):
             self.enable_voice_lists()
         if voice_list_groups:   # ... and the listed form goes by the lane plan: reserve_voice_list_groups / process_listed_groups
             self.enable_voice_list_groups()
+        if voice_list_rings:   # ... and a graph with delay rings has it in ring layouts 1 and 4 too (delay_windows 3 then resolves to 4, 1 or 0)
+            self.enable_voice_list_rings()
         if voice_list_events:   # ... and a graph with event rows has a listed form: process_events_listed / process_events_listed_groups
             self.enable_voice_list_events()
         if mpe_events:   # the plain kernel's event rows in the form for either protocol: bind_events / process_events take an MPE object
@@ -1359,6 +1361,12 @@ class Graph(_Handle):
         """Before compile: voice lists, with the listed kernel going by the lane plan - the group-summed outputs get one row per
         listed instrument (mlgpu_graph_enable_voice_list_groups). enable_voice_lists(False) turns both off."""
         self._check(self.L.mlgpu_graph_enable_voice_list_groups(self.h, 1 if on else 0))
+
+    def enable_voice_list_rings(self, on=True):
+        """Before compile: voice lists, with the delay rings in the sector layouts served too - delay_windows 1 and 4, and 3 ("best"),
+        which then resolves to 4, 1 or 0 and never to 2 (mlgpu_graph_enable_voice_list_rings). enable_voice_lists(False) turns it off
+        with the rest."""
+        self._check(self.L.mlgpu_graph_enable_voice_list_rings(self.h, 1 if on else 0))
 
     def reserve_voice_list_groups(self, max_listed):
         """Setup: reserve_voice_list(max_listed), and from now on set_voice_list also makes and uploads the lane plan

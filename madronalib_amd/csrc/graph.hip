@@ -75,6 +75,7 @@ struct mlgpu_graph
   DeviceBuffer<float> d_consts;  // live constants: [nConsts] floats
   DeviceBuffer<float> d_mem;
   size_t vectorCount{0};         // DSPVectors processed since the last clear (GraphArgs::t0)
+  bool listedSinceClear{false};  // a listed launch has run since the last mlgpu_graph_clear (GraphPlan::ringsByLaneOnly: the plain kernel is then refused)
   std::string lastError;         // mlgpu_graph_last_error
   mlgpu_events* events{nullptr}; // mlgpu_graph_bind_events: the object the NODE_EVENT_ROW nodes read
   // mlgpu_graph_compile_async: planning, code generation and hiprtc on a thread of the library's, off the caller's (audio) thread.
@@ -137,6 +138,8 @@ TestHooks readTestHooks()
   const char* rowAddr32 = getenv("MLGPU_GRAPH_ROW_ADDR32");
   const char* earlyReads = getenv("MLGPU_GRAPH_EARLY_READS");
   const char* oscTrip = getenv("MLGPU_GRAPH_OSC_TRIP");
+  const char* laneClock = getenv("MLGPU_GRAPH_RING_LANE_CLOCK");
+  h.ringLaneClock = !(laneClock && !strcmp(laneClock, "0"));
   if (minWaves) h.minWaves = atoi(minWaves);
   h.rowAddr64 = rowAddr32 && !strcmp(rowAddr32, "0");
   h.earlyReads = !(earlyReads && !strcmp(earlyReads, "0"));
@@ -1023,6 +1026,7 @@ extern "C"
       if (st) return st;
     }
     g->vectorCount = 0;
+    g->listedSinceClear = false;
     return MLGPU_OK;
   }
 
@@ -1203,7 +1207,17 @@ extern "C"
   {
     if (const int st = checkEditable(g, "graph_enable_voice_lists: before mlgpu_graph_compile")) return st;
     g->desc.voiceLists = on != 0;
-    if (!on) g->desc.voiceListGroups = g->desc.voiceListEvents = g->desc.voiceListMpeEvents = false;
+    if (!on) g->desc.voiceListGroups = g->desc.voiceListEvents = g->desc.voiceListMpeEvents = g->desc.voiceListRings = false;
+    return MLGPU_OK;
+  }
+  // ... and a graph with delay rings has its listed form in the sector layouts too (1 and 4: a voice owns its 32-byte sectors, memory
+  // goes by the voice and LDS by the lane; layout 3 then resolves to 4, 1 or the rows, never to 2 - planGraph). on = 1 turns voice lists
+  // on too; mlgpu_graph_enable_voice_lists(g, 0) turns it off with the rest.
+  int mlgpu_graph_enable_voice_list_rings(mlgpu_graph* g, int on)
+  {
+    if (const int st = checkEditable(g, "graph_enable_voice_list_rings: before mlgpu_graph_compile")) return st;
+    g->desc.voiceListRings = on != 0;
+    if (on) g->desc.voiceLists = true;
     return MLGPU_OK;
   }
   // ... and a graph with event rows has a listed form as well (mlgpu_graph_process_events_listed[_groups]): CtlVoice of the gathered
@@ -1475,6 +1489,17 @@ extern "C"
     if (g->job) return MLGPU_ERR_BUSY;
     if (!g->compiled) return gfail(g, MLGPU_ERR_INVALID, "graph_process: compile first");
     if (T == 0) return MLGPU_OK;
+    // A PitchbendableDelay in ring layout 4 next to voice lists (mlgpu_graph_enable_voice_list_rings): the listed kernel keeps ONE ring for
+    // a voice whose two write indices agree, whatever its wavefront does; this kernel decides per wavefront, and a wavefront whose voices
+    // were listed for different numbers of DSPVectors would send them all through two rings - the second never written (mldsp_procs.hpp,
+    // above RingCore::beginS). Wrong samples are not an answer: refused until the next clear. A recorded launch is replayed later, after
+    // who knows which listed launches: refused as well.
+    if (g->build->plan.ringsByLaneOnly && (g->listedSinceClear || g->e->recording))
+      return gfail(g, MLGPU_ERR_UNSUPPORTED,
+                   std::string("graph_process: a PitchbendableDelay in delay layout 4 next to voice lists (mlgpu_graph_enable_voice_list_rings) ") +
+                       (g->listedSinceClear ? "after a listed launch" : "while recording a sequence") +
+                       ": the listed kernel keeps one ring per voice where this kernel decides per wavefront, and the listed voices' write indices now differ - run "
+                       "all voices through mlgpu_graph_process_listed (every voice listed), or mlgpu_graph_clear first");
     GraphArgs a;
     if (const int st = signalArgs(g, a, "graph_process", T, d_inputs, inLayout, d_controls, d_outputs, outLayout)) return st;
     if (const int st = outputViews(g, a, T, d_outputs, outLayout, g->desc.V, 0,
@@ -1617,6 +1642,7 @@ extern "C"
           return gfail(g, MLGPU_ERR_HIP, w() + ": clearing a mixed-down output");
       return MLGPU_OK;
     }
+    g->listedSinceClear = true;
     if (const int st = listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream()))) return st;
     return mixdownStages(g, T, d_outputs, K, who);
   }
@@ -1678,6 +1704,7 @@ extern "C"
     void* eventStaging = nullptr;
     if (const int st = listedEventsPrepare(g, who, T, eventOffset, a, &eventStaging)) return st;
     if (K == 0) return listedEventsLaunched(g, who, eventStaging, hipSuccess);  // (the events object advanced; no voice kernel)
+    g->listedSinceClear = true;
     return listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream()));
   }
   int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,

@@ -356,7 +356,11 @@ struct GraphEmitter
   }
   void header()
   {
-    const std::string ringWindows = p.rings == RingLayout::ROWS ? std::string() : "#define MLGPU_RING_WINDOWS " + std::to_string((int)p.rings) + "\n";
+    // (the listed kernel of ring layout 4 - mlgpu_graph_enable_voice_list_rings - runs its trips on each LANE's write clock: voices that
+    // were off the list for different numbers of DSPVectors have write indices that differ by multiples of 64; RingCore::beginS)
+    // (... and decides per LANE what a wavefront of the plain kernel decides once for voices that never change: MLGPU_RING_BY_LANE)
+    const std::string ringWindows = p.rings == RingLayout::ROWS ? std::string() : "#define MLGPU_RING_WINDOWS " + std::to_string((int)p.rings) + "\n" +
+                                    ((listed && p.ringByLane) ? "#define MLGPU_RING_BY_LANE 1\n" : "") + ((listed && p.ringLaneClock) ? "#define MLGPU_RING_LANE_CLOCK 1\n" : "");
     s << "// generated by libmlgpu graph.hip (" << VL << " voice" << (VL > 1 ? "s" : "") << " per lane" << (planned ? ", the voices of a list by its lane plan" : listed ? ", the voices of a list" : "") << ")\n" << ringWindows
       << (g.strictSvf ? "#define MLGPU_SVF_STRICT 1\n" : "") << "#include \"mldsp_kernels.hpp\"\n#include \"mldsp_ops.hpp\"\n"
       << (g.hasEventRows ? "#include \"mldsp_events.hpp\"\n" : "") << "using namespace mldev;\n";
@@ -368,6 +372,8 @@ struct GraphEmitter
         s << "};\n";
       }
     // windowed rings: the latency of a sector refill is hidden by other waves only, so keep at least two per SIMD
+    // (the listed forms with rings - mlgpu_graph_enable_voice_list_rings - take the same bounds: they count wavefronts per SIMD and registers
+    // per lane, and a lane of a listed launch holds one voice's windows like any other)
     const std::string bound = (p.rings == RingLayout::TRANSPOSED && p.totalRings == 1) ? ", 4" : ringTrips ? ", 1" : windowed ? ", 2"
                               : form.minWaves ? ", " + std::to_string(form.minWaves) : std::string();
     s << "extern \"C\" __global__ __launch_bounds__(256" << bound << ") void " << (listed ? "mlgpu_graph_listed_kernel" : "mlgpu_graph_kernel") << "(const GraphArgs a)\n{\n  apply_fp_mode(a.flags);\n";
@@ -405,6 +411,10 @@ struct GraphEmitter
       // outputs and peaks), .z the row of its instrument, .w rank | length << 8 in its segment. A lane at or past the plan's end and a
       // pad leave here - after the impulse table's barrier, the only one of the kernel, and before every wave-uniform ballot below,
       // which so counts the wavefront's voices alone. A pad loads, runs and stores nothing.
+      // (Rings in layouts 1 and 4 - mlgpu_graph_enable_voice_list_rings: the return stays safe. Neither layout has a barrier - layout 1's
+      // write window is the lane's own LDS column, layout 4's held sectors and history rows are the lane's own columns of its wavefront's
+      // strip - and their ballots ask "some lane of those still here": RingCore's trip code then goes by the lane's own w, sectors and
+      // column. A lane that left holds no sector and owes no flush.)
       s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n  if (vr_0 >= a.listed) return;\n  const uint4 plan = ((const uint4*)a.lanePlan)[vr_0];\n"
            "  if (plan.x == 0xFFFFFFFFu) return;  // a pad\n  const size_t v_0 = plan.x, pl_0 = plan.y;\n"
            "  const unsigned rank_0 = plan.w & 0xFFu, length_0 = plan.w >> 8;\n  __builtin_assume(length_0 != 0u);\n  uint32_t pk_0 = 0u;\n";
@@ -415,6 +425,16 @@ struct GraphEmitter
     {
       // the lane's place in the list (vr), the place whose voice it runs and whose rows it stores to (pl), the voice (v): everything
       // below that is made of v - tables, ring rows, input rows, control columns - is the gathered voice's
+      // Rings in layouts 1 and 4 (mlgpu_graph_enable_voice_list_rings): ring MEMORY is addressed by v (procSetup: the voice's 32-byte
+      // sectors of its 256-voice block), the LDS windows by threadIdx.x - the split a gathered voice needs. The early return of the lanes
+      // past the list stands: after the impulse table's barrier these layouts have none (layout 2's wave barriers are not served), and
+      // every ballot of RingCore asks the lanes that are still here.
+      // The spare lanes of a mixed-down output's last wavefront run the list's last voice again in lockstep with its real lane: the same
+      // state, inputs and delay times, so the same w, the same sectors and the same floats at every instruction. Layout 1: each keeps
+      // the write window in its own LDS column and both flush the same sector with the same eight floats, by one store instruction -
+      // whichever lane's write lands last, the sector holds those floats, and a later refill by either reads them. Layout 4: both store
+      // and load the same positions by the same instructions, held sectors and history rows in columns of their own. Loads and stores
+      // of a wavefront complete in issue order, so no lane ever reads a sector between two different values of it: there are none.
       s << "  const size_t vr_0 = blk * 256 + threadIdx.x;\n";
       if (partialWaves) s << "  if ((vr_0 & ~(size_t)63) >= a.listed) return;\n  const size_t pl_0 = vr_0 < a.listed ? vr_0 : a.listed - 1;\n";
       else s << "  if (vr_0 >= a.listed) return;\n  const size_t pl_0 = vr_0;\n";
@@ -635,6 +655,8 @@ struct GraphEmitter
       }
       s << "    }\n";
     }
+    // ring layout 4: every ring's loads of the trip together, before any arithmetic. The listed forms too: each lane predicts its OWN
+    // read position from its own w and delay time and loads its own voice's sectors (tripBegin), the ballots only ask whether some lane needs to
     if (ringTrips)
       for (size_t i = 0; i < g.nodes.size(); ++i)
         if (g.nodes[i].type == NODE_PROC && g.nodes[i].region < 0 && mlgpu_proc_rings(g.nodes[i].kind))
@@ -973,6 +995,16 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   for (const Node& n : g.nodes) ringInRegion = ringInRegion || (n.type == NODE_PROC && n.region >= 0 && mlgpu_proc_rings(n.kind) != 0);
   if (p.rings == RingLayout::SECTORS && ringInRegion)
     return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 4 (sector trips) does not serve a delay line inside a rate region (layout 1 or 3 for this graph)");
+  // mlgpu_graph_enable_voice_list_rings: the listed kernel keeps ring windows too. The lane plan's has LDS of its own beside them -
+  // the tables and the segment strips (below; its early reads are the rows' alone) - where the plain kernel has ldsOther.
+  const bool listRings = g.voiceLists && g.voiceListRings;
+  size_t planSums = 0;
+  for (size_t o = 0; o < g.outputs.size(); ++o) planSums += g.outputGroup[o] ? 1 : 0;
+  const size_t ldsPlanned = !g.voiceListGroups ? 0 : (g.hasImpulse ? 128 : 0) + planSums * sizeof(float) * (4 * (size_t)kHostSegmentStripFloats + (size_t)kHostSegmentTailFloats);
+  const size_t ldsBoth = std::max(ldsOther, ldsPlanned);
+  if (listRings && !p.totalRings)
+    return fail(MLGPU_ERR_INVALID, "graph_compile: voice lists with rings in the sector layouts (mlgpu_graph_enable_voice_list_rings): the graph has no delay node; "
+                                   "without one mlgpu_graph_enable_voice_lists serves the graph");
   if (g.delayLayout == 3)
   {
     // "the best form": one or two rings - the transposed windows (0.72-0.74 of the HBM peak on the strings bank); more - the sector
@@ -987,6 +1019,12 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
     const bool transposed = !preferSectors && partialOk && p.totalRings <= 4 && ldsLayout2 + ldsOther <= kLdsBytes;
     // more rings than any windowed form has LDS for (the reference's reverb example: 24): the default rows
     p.rings = transposed ? RingLayout::TRANSPOSED : sectorFits ? RingLayout::SECTORS : ldsLayout1 + ldsOther > kLdsBytes ? RingLayout::ROWS : RingLayout::WINDOWS;
+    // Voice lists with rings (mlgpu_graph_enable_voice_list_rings): never layout 2, whose pieces are moved by a block's neighbouring
+    // lanes. The sector trips where their LDS fits and no delay line sits in a rate region, else layout 1 where its LDS fits, else
+    // the rows - each next to the LDS of BOTH kernels, the plan is one value for the two (measured on listed launches of a string
+    // bank and of four Allpass nodes: profiles/graph_voice_list_rings.md)
+    if (listRings)
+      p.rings = (!ringInRegion && ldsLayout4 + ldsBoth <= kLdsBytes) ? RingLayout::SECTORS : ldsLayout1 + ldsBoth <= kLdsBytes ? RingLayout::WINDOWS : RingLayout::ROWS;
   }
   if (p.rings == RingLayout::TRANSPOSED && ldsLayout2 + ldsOther > kLdsBytes)
     return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: delay layout 2 needs 40 KiB of LDS per ring (" + kib(ldsLayout2) + " for " + std::to_string(p.totalRings) +
@@ -1004,7 +1042,13 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   if (g.voiceLists)
   {
     const std::string who = g.voiceListGroups ? "graph_compile: voice lists by a lane plan (mlgpu_graph_enable_voice_list_groups): " : "graph_compile: voice lists (mlgpu_graph_enable_voice_lists): ";
-    if (p.rings != RingLayout::ROWS && p.totalRings)
+    // (mlgpu_graph_enable_voice_list_rings: layouts 1 and 4 keep a voice's 32-byte sectors to the voice - memory goes by v, the LDS
+    // windows by the lane, nothing looks at a neighbour; layout 2's stage registers hold other lanes' pieces)
+    if (listRings && p.rings == RingLayout::TRANSPOSED)
+      return fail(MLGPU_ERR_UNSUPPORTED, who + "delay layout 2 (transposed windows) moves a voice's 64-byte pieces with its neighbouring lanes and has no listed form; "
+                                             "mlgpu_graph_enable_voice_list_rings serves the sector layouts 1 and 4, and layout 3, which then resolves to one of them: "
+                                             "mlgpu_graph_set_delay_layout(g, 1), (g, 4) or (g, 3)");
+    if (!listRings && p.rings != RingLayout::ROWS && p.totalRings)
       return fail(MLGPU_ERR_UNSUPPORTED, who + "delay layout " + std::to_string(apiLayout(p.rings)) + (g.delayLayout == 3 ? " (what layout 3 resolves to for this graph)" : "") +
                                              " keeps its rings in pieces made by the neighbouring voices of a 256-voice block; the rows are served: mlgpu_graph_set_delay_layout(g, 0)");
     // the lane plan (mlgpu_graph_enable_voice_list_groups): instruments of ONE size, and no mixdown - the tree of a K-voice graph goes
@@ -1036,6 +1080,11 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
   p.memVoices = p.rings != RingLayout::ROWS ? ((g.V + 255) & ~(size_t)255) : g.V;
   p.minWavesHook = hooks.minWaves;
   p.rowAddr64 = hooks.rowAddr64;
+  p.ringByLane = listRings && p.rings == RingLayout::SECTORS && p.totalRings;
+  p.ringLaneClock = p.ringByLane && hooks.ringLaneClock;
+  // ... and a PitchbendableDelay among them: a wavefront of the plain kernel that cannot run trips sends ALL its lanes through two rings,
+  // where the listed kernel kept one for a lane whose two write indices agree (mldsp_procs.hpp, above RingCore::beginS)
+  for (const Node& n : g.nodes) p.ringsByLaneOnly = p.ringsByLaneOnly || (p.ringByLane && n.type == NODE_PROC && n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY);
   // ring layout 0: rows behind 32-bit offsets where every delay node's memory stays below 4 GiB (VoiceMem::ringPtr)
   // (node by node in the generator: a ring of the bank at most 4 GiB)
   p.rowAddr32 = p.rings == RingLayout::ROWS && p.totalRings && g.V < ((size_t)1 << 22) && !p.rowAddr64;
@@ -1069,6 +1118,13 @@ int mlgraph::planGraph(const GraphDesc& g, const TestHooks& hooks, GraphPlan& p,
     for (size_t o = 0; o < g.outputs.size(); ++o) sums += g.outputGroup[o] ? 1 : 0;
     const size_t ldsTables = g.hasImpulse ? 128 : 0, ldsEarly = (size_t)p.earlySlots * 4 * 64 * sizeof(float);
     const size_t ldsSegments = sums * sizeof(float) * (4 * (size_t)kHostSegmentStripFloats + (size_t)kHostSegmentTailFloats);
+    // (mlgpu_graph_enable_voice_list_rings: and the ring windows of the layout in effect, as in the plain kernel)
+    const size_t ldsRingWindows = !(listRings && p.totalRings) ? 0 : p.rings == RingLayout::SECTORS ? ldsLayout4 : p.rings == RingLayout::WINDOWS ? ldsLayout1 : 0;
+    if (ldsRingWindows && ldsPlanned + ldsRingWindows > kLdsBytes)  // (ldsPlanned: the tables and the segment strips)
+      return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: voice lists by a lane plan (mlgpu_graph_enable_voice_list_groups) with rings in the sector layouts (mlgpu_graph_enable_voice_list_rings): " +
+                                             kib(ldsRingWindows) + " of LDS for the ring windows of delay layout " + std::to_string(apiLayout(p.rings)) + " next to " + kib(ldsSegments) +
+                                             " for the segment strips of " + std::to_string(sums) + " group-summed outputs (16 KiB + 256 B each) and " + std::to_string(ldsTables) +
+                                             " B of tables; a workgroup has 160 KiB (layout 3 or 0 for this graph)");
     if (ldsTables + ldsEarly + ldsSegments > kLdsBytes)
       return fail(MLGPU_ERR_UNSUPPORTED, "graph_compile: voice lists by a lane plan (mlgpu_graph_enable_voice_list_groups): " + kib(ldsSegments) + " of LDS for the segment strips of " +
                                              std::to_string(sums) + " group-summed outputs (16 KiB + 256 B each) next to " + kib(ldsEarly) + " of early ring reads and " +

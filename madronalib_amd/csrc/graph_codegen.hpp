@@ -109,6 +109,7 @@ struct GraphDesc
   bool mpeEvents{false};         // the plain kernel's event rows in the MPE-capable form: mlev::CtlVoiceMpe / CtlRowsMpe (mlgpu_graph_enable_mpe_events)
   bool voiceListEvents{false};   // ... and a graph with event rows has it too: CtlVoice of the gathered voice (mlgpu_graph_enable_voice_list_events)
   bool voiceListMpeEvents{false};  // ... in the form for either protocol: CtlVoiceMpe / CtlRowsMpe of the gathered voice (mlgpu_graph_enable_voice_list_mpe_events; implies the two above)
+  bool voiceListRings{false};    // ... and a graph with delay rings has it in the sector layouts 1 and 4 too, layout 3 resolving to one of them (mlgpu_graph_enable_voice_list_rings)
 };
 
 // Where the delay rings live (mlgpu_graph_set_delay_layout 0, 1, 2 and 4; its layout 3 is resolved to one of them by planGraph)
@@ -142,6 +143,7 @@ struct TestHooks
   bool rowAddr64{false};   // MLGPU_GRAPH_ROW_ADDR32=0: 64-bit state and ring row addresses
   bool earlyReads{true};   // MLGPU_GRAPH_EARLY_READS=0: the plain ring loads
   int oscTripQ{2};         // MLGPU_GRAPH_OSC_TRIP: 0: polyBLEP per sample, else 1, 2 or 4 quads per trip
+  bool ringLaneClock{true};  // MLGPU_GRAPH_RING_LANE_CLOCK=0: the listed kernel of ring layout 4 keeps the plain kernel's aligned test (equal write indices)
 };
 
 struct NodePlan
@@ -179,6 +181,9 @@ struct GraphPlan
   int oscTripQ{2};               // quads per trip of the oscillators' sparse polyBLEP (0: per sample; mldsp_procs.hpp: trip_u)
   bool oscTrips{false};          // some node is an oscillator trip
   int minWavesHook{-1};          // TestHooks::minWaves
+  bool ringByLane{false};        // voice lists with rings in layout 4: the listed kernel decides per lane what the plain one decides per wavefront (MLGPU_RING_BY_LANE)
+  bool ringsByLaneOnly{false};   // ... and the graph has a PitchbendableDelay: after a listed launch the plain kernel would read its second ring, which the listed one leaves unwritten
+  bool ringLaneClock{false};     // the listed kernel of ring layout 4 asks each lane for a sector boundary, not the wavefront for one write index (MLGPU_RING_LANE_CLOCK; TestHooks::ringLaneClock)
   KernelForm form;               // the default form (autotune may run another: mlgpu_graph::activeForm)
   std::vector<NodePlan> nodes;   // indexed like GraphDesc::nodes
 };

@@ -1280,6 +1280,18 @@ constexpr bool kRingTransposed = MLGPU_RING_WINDOWS == 2;
 // plain per-sample accesses of the same memory. Layout 1 decided per lane and sample whether to refill its register window: a
 // divergent load and a round trip on almost every sample of a wavefront whose voices have different delay times.
 constexpr bool kRingSectors = MLGPU_RING_WINDOWS == 3;
+// Layout 4 in the LISTED kernels (mlgpu_graph_enable_voice_list_rings): a wavefront is 64 gathered voices, and who they are changes
+// from launch to launch. MLGPU_RING_BY_LANE (every listed source of layout 4): what a lane does to its rings depends on that lane
+// alone - a PitchbendableDelay keeps one ring wherever the LANE's two write indices agree, whichever path its wavefront takes.
+// MLGPU_RING_LANE_CLOCK (the same sources, unless the test hook MLGPU_GRAPH_RING_LANE_CLOCK=0 keeps it out): the trips run on each
+// lane's own write clock (RingCore::beginS). The plain kernel defines neither and keeps its text.
+#ifndef MLGPU_RING_BY_LANE
+#define MLGPU_RING_BY_LANE 0
+#endif
+#ifndef MLGPU_RING_LANE_CLOCK
+#define MLGPU_RING_LANE_CLOCK 0
+#endif
+constexpr bool kRingByLane = MLGPU_RING_BY_LANE != 0, kRingLaneClock = MLGPU_RING_LANE_CLOCK != 0;
 constexpr int32_t kSectorMinDelay = 16;
 constexpr int kTChunk = 16, kTWrite = 8, kTRowPad = 64, kTRows = kTWrite + 2 * kTChunk, kTStrip = kTRows * kTRowPad;
 constexpr uint32_t kTNone = 0xFFFFFFFFu;
@@ -1711,10 +1723,39 @@ struct RingCore  // IntegerDelay's buffer, index and mask
     v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
   }
   bool sAligned, sFast;              // launch: w is the same multiple of 8 in every lane; trip: served from sH / sN
+  // The listed kernel (MLGPU_RING_LANE_CLOCK, mlgpu_graph_enable_voice_list_rings) asks less: w a multiple of 8 in every lane, not the
+  // same one - voices that were off the list for different numbers of DSPVectors differ by multiples of 64. What the trip code does
+  // with w, read use by use:
+  //   beginS          the history rows from sectors (w >> 3) - 2 and - 1 into rows (w - 16 + j) & 15: the lane's w, the lane's column
+  //   tripBegin       s0, s1 from (w - dPred): the lane's; sTag / sNTag are compared with them per lane, the ballots ask "some lane"
+  //                   and the loads inside are unconditional, each lane its own sectors into its own LDS column (held) and sN
+  //   tripStart       r0, s0, s1, the barrel's r0 & 7, the early request's next sector: all the lane's; sD0 is the lane's delay time
+  //   writeS          sX[K] and history row (w + K) & 15; the sector store at K == 7 to chunkMem(w): K is the loop's constant, the same
+  //                   in every lane - the trips need w & 7 == 0 per lane so that the lane's eight samples ARE one sector, nothing more
+  //   readS           history row (w + K - d) & 15 and, for a delay time that moved, position w + K - d in memory: the lane's
+  //   advanceS        w += 8 at K == 7, per lane
+  //   held, histRows  m.lds (the wavefront's strip) + threadIdx.x & 63: the lane's column, never w
+  //   chunkMem        m.mem is the VOICE's sector of chunk 0 (the generated kernel makes it of v), i only picks the chunk
+  // No use above compares w, a tag or a sector number between lanes, and none derives a wave-uniform value from them: the relaxed
+  // test serves every one. (Write indices always move by whole DSPVectors, so a lane on a sector boundary at the launch's start is on
+  // one at every trip's.)
+  // The ONE use where a lane's result depends on its neighbours is Proc<PITCHBENDABLE_DELAY>::load: oneRing wants sAligned of both
+  // cores - a wavefront-wide value - and f1.w == f2.w in every lane, and while it holds ring 1 is NOT WRITTEN. In the plain kernel a
+  // wavefront's voices never change, so a voice is served one way for good. In a listed kernel a voice with one-ring history can be
+  // gathered next to a voice a host set off a sector boundary (or, under the strict test, next to any voice with another write
+  // index): sent through two rings then, it would read ring 1's stale samples. So the listed kernels (kRingByLane) decide the ring per
+  // LANE on the path outside the trips too (next_i): ring 0 for both cores wherever the lane's own two indices agree, which
+  // no launch changes. The plain kernel cannot have that without changing its code; mlgpu_graph_process of such a graph is refused
+  // after a listed launch (graph.hip: ringsByLaneOnly).
   MLD void beginS(const VoiceMem& m, int ringIdx, bool histWriter)
   {
-    const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
-    sAligned = __builtin_amdgcn_ballot_w64(w != w0) == 0 && (w0 & 7u) == 0u;
+    if (kRingLaneClock)
+      sAligned = __builtin_amdgcn_ballot_w64((w & 7u) != 0u) == 0;
+    else
+    {
+      const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
+      sAligned = __builtin_amdgcn_ballot_w64(w != w0) == 0 && (w0 & 7u) == 0u;
+    }
     sTag = sNTag = kTNone;
     sFast = false;
     sD0 = 0;
@@ -2300,8 +2341,13 @@ struct Proc<MLGPU_PROC_PITCHBENDABLE_DELAY>  // :1050-1106  C{}  S{delay1: 5 wor
     }
     else
     {
+      // The listed kernels of layout 4 (kRingByLane), a wavefront outside the trips: a lane whose own two write indices agree - they
+      // advance together, so no launch changes that - lives in ring 0 alone, as in the trips (see the audit above RingCore::beginS). It
+      // writes x to ring 0 a second time, the same float to the same place, and reads its second tap there, where all its history is.
+      // (Asked here and not kept from load(): one more member of this struct changes the plain kernel's code.)
+      const int ring2 = (kRingSectors && kRingByLane && f1.ringc.w == f2.ringc.w) ? 0 : 1;
       y1 = f1.sample(mem, 0, x, K);
-      y2 = f2.sample(mem, 1, x, K);
+      y2 = f2.sample(mem, ring2, x, K);
     }
     const float fade = 2.f * ((r > 16) ? 1.0f - (float)r / 32.f : (float)r / 32.f);
     return y1 + (fade * (y2 - y1));
