@@ -97,7 +97,6 @@ struct mlgpu_graph
   };
   CompileJob* job{nullptr};
   bool aotDone{false};           // an engine-less graph whose ahead-of-time compile has been collected (mlgpu_graph_compile_poll keeps answering MLGPU_OK)
-  int eventOffset{-1};           // frame offset of the block being processed (mlgpu_graph_process_events), -1: none pending
   // Online tuning (mlgpu_graph_set_autotune): every variant (voices per lane x quads per trip) computes the same bits from
   // the same state arrays, so the first process calls simply take turns, are timed, and the fastest one stays.
   struct Variant
@@ -1452,38 +1451,52 @@ extern "C"
         return gfail(g, MLGPU_ERR_HIP, std::string(who) + ": the mixdown's later stages");
     return MLGPU_OK;
   }
-  // Event rows: the host half of the EventsToSignals block (routing the block's events into records, their upload) goes first, on
-  // the same stream; the kernel then walks the records itself. *staging: null without event rows, else what the launch is reported with.
-  static int prepareEvents(mlgpu_graph* g, size_t T, GraphArgs& a, void** staging)
+  // ---- the events of a process call, plain or listed. The call has the block's frame offset as an argument (eventOffset; < 0: it is
+  // not an events call) and goes through these three in this order; `listed` says which kernel it launches. The events object belongs
+  // to ALL voices: its host half (routing the block's events into records, their upload) and e2s_ctl_kernel run for every lane in every
+  // call, on the engine's stream - note state, the pitch and bend glides and the drift random walk advance for listed and unlisted
+  // voices alike -, the voice kernel then expands the control records of its voices only. ----
+  // The protocol form of the kernel the call launches: for an events object in either protocol, or MIDI only
+  static bool eventsEitherProtocol(const mlgpu_graph* g, bool listed) { return listed ? g->desc.voiceListMpeEvents : g->desc.mpeEvents; }
+  // What the call refuses without looking at the block
+  static int eventsReady(mlgpu_graph* g, const char* who0, int eventOffset, bool listed)
   {
-    if (!g->desc.hasEventRows) return MLGPU_OK;
-    if (!g->events) return gfail(g, MLGPU_ERR_INVALID, "graph_process: the graph has event rows but no events object (graph_bind_events)");
-    if (g->eventOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process: a graph with event rows is run with mlgpu_graph_process_events");
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, g->eventOffset, g->desc.eventRowMask, g->desc.mpeEvents ? 1 : 0, &a.events, staging);
-    g->eventOffset = -1;
-    return est == MLGPU_OK ? est : gfail(g, est, "graph_process: the events object refused the block: " + g->e->lastError);
+    const auto who = [who0] { return std::string(who0); };  // (made where a refusal needs it: the success path allocates nothing)
+    if (!g->desc.hasEventRows) return MLGPU_OK;  // (an events call of such a graph: refused by its entry point)
+    // (a call that is no events call and has no events object either: the plain call names the object, a listed call the call)
+    if (eventOffset < 0 && (listed || g->events))
+      return gfail(g, MLGPU_ERR_INVALID, who() + ": a graph with event rows is run with mlgpu_graph_process_events" + (listed ? "_listed[_groups]" : ""));
+    if (!g->events) return gfail(g, MLGPU_ERR_INVALID, who() + ": the graph has event rows but no events object (graph_bind_events)");
+    // (a plain kernel's protocol is settled when the object is bound: graph_bind_events)
+    if (listed && !eventsEitherProtocol(g, listed) && !mlgpu_events_is_midi(g->events))
+      return gfail(g, MLGPU_ERR_UNSUPPORTED, who() + ": events as graph source nodes: MIDI protocol only (one lane per voice) - mlgpu_graph_enable_voice_list_mpe_events(g, 1) "
+                                                     "before compile makes the listed form for either protocol");
+    return MLGPU_OK;
+  }
+  // ... and once nothing of the call can be refused any more: the host half and e2s_ctl_kernel. *staging: null if the call is not an
+  // events call, else what the launch is reported with.
+  static int eventsPrepare(mlgpu_graph* g, const char* who0, size_t T, int eventOffset, bool listed, GraphArgs& a, void** staging)
+  {
+    const auto who = [who0] { return std::string(who0); };
+    *staging = nullptr;
+    if (eventOffset < 0) return MLGPU_OK;
+    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, eventsEitherProtocol(g, listed) ? 1 : 0, &a.events, staging);
+    return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
+  }
+  // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)
+  static int eventsLaunched(mlgpu_graph* g, const char* who0, void* staging, hipError_t err)
+  {
+    const auto who = [who0] { return std::string(who0); };
+    if (staging && err != hipSuccess) mlgpu_events_abandoned_by_graph(g->events, staging);  // (the lanes' record ranges back to "none": no kernel will consume them)
+    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, who() + " launch: " + hipGetErrorString(err));
+    if (staging)
+      if (const int est = mlgpu_events_launched_by_graph(g->events, staging)) return gfail(g, est, who() + ": events bookkeeping after the launch");
+    return MLGPU_OK;
   }
 
-  int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
-  {
-    return mlgpu_graph_process_ctl(g, T, d_inputs, inLayout, nullptr, d_outputs, outLayout);
-  }
-  // a graph with event rows: T DSPVectors starting at frame startOffset of the bound object's event times (as mlgpu_events_process)
-  int mlgpu_graph_process_events(mlgpu_graph* g, size_t T, int startOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
-                                 float* const* d_outputs, int outLayout)
-  {
-    if (!g) return MLGPU_ERR_INVALID;
-    if (g->job) return MLGPU_ERR_BUSY;
-    if (!g->desc.hasEventRows) return gfail(g, MLGPU_ERR_INVALID, "graph_process_events: the graph has no event rows");
-    if (startOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process_events: negative frame offset");
-    g->eventOffset = startOffset;
-    const int st = mlgpu_graph_process_ctl(g, T, d_inputs, inLayout, d_controls, d_outputs, outLayout);
-    g->eventOffset = -1;
-    return st;
-  }
-
-  int mlgpu_graph_process_ctl(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls,
-                              float* const* d_outputs, int outLayout)
+  // The plain call: all voices. Its refusals are in the name of graph_process, whichever entry point it came through.
+  static int processPlain(mlgpu_graph* g, size_t T, int eventOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                          float* const* d_outputs, int outLayout)
   {
     if (!g) return MLGPU_ERR_INVALID;
     if (g->job) return MLGPU_ERR_BUSY;
@@ -1519,20 +1532,34 @@ extern "C"
     if (trial && !g->tuneEv0 && (allocate(g->tuneEv0) != hipSuccess || allocate(g->tuneEv1) != hipSuccess))
       return gfail(g, MLGPU_ERR_HIP, "graph_process: hipEventCreate");
     void* eventStaging = nullptr;
-    if (const int st = prepareEvents(g, T, a, &eventStaging)) return st;
+    if (const int st = eventsReady(g, "graph_process", eventOffset, false)) return st;
+    if (const int st = eventsPrepare(g, "graph_process", T, eventOffset, false, a, &eventStaging)) return st;
     if (trial) hipEventRecord(g->tuneEv0.get(), g->e->stream());
     const hipError_t err = mlgpu_jit_launch(fn, &a, sizeof(a), (g->desc.V + (size_t)vl - 1) / (size_t)vl, g->e->stream());
-    if (err != hipSuccess)
-    {
-      if (eventStaging) mlgpu_events_abandoned_by_graph(g->events, eventStaging);  // (the lanes' record ranges back to "none": no kernel will consume them)
-      return gfail(g, MLGPU_ERR_HIP, std::string("graph_process launch: ") + hipGetErrorString(err));
-    }
-    if (eventStaging)
-      if (const int est = mlgpu_events_launched_by_graph(g->events, eventStaging)) return gfail(g, est, "graph_process: events bookkeeping after the launch");
+    if (const int st = eventsLaunched(g, "graph_process", eventStaging, err)) return st;
     if (const int st = mixdownStages(g, T, d_outputs, g->desc.V, "graph_process")) return st;
     if (trial) tuningRecord(g, trial, T);
     g->vectorCount += T;
     return MLGPU_OK;
+  }
+  int mlgpu_graph_process_ctl(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                              float* const* d_outputs, int outLayout)
+  {
+    return processPlain(g, T, -1, d_inputs, inLayout, d_controls, d_outputs, outLayout);
+  }
+  int mlgpu_graph_process(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, float* const* d_outputs, int outLayout)
+  {
+    return processPlain(g, T, -1, d_inputs, inLayout, nullptr, d_outputs, outLayout);
+  }
+  // a graph with event rows: T DSPVectors starting at frame startOffset of the bound object's event times (as mlgpu_events_process)
+  int mlgpu_graph_process_events(mlgpu_graph* g, size_t T, int startOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
+                                 float* const* d_outputs, int outLayout)
+  {
+    if (!g) return MLGPU_ERR_INVALID;
+    if (g->job) return MLGPU_ERR_BUSY;
+    if (!g->desc.hasEventRows) return gfail(g, MLGPU_ERR_INVALID, "graph_process_events: the graph has no event rows");
+    if (startOffset < 0) return gfail(g, MLGPU_ERR_INVALID, "graph_process_events: negative frame offset");
+    return processPlain(g, T, startOffset, d_inputs, inLayout, d_controls, d_outputs, outLayout);
   }
 
   // ---- voice lists: run only the listed voices (mlgpu_voice_list keeps the list, the listed form of the generated kernel runs it);
@@ -1563,22 +1590,7 @@ extern "C"
   }
   size_t mlgpu_graph_voice_list_size(mlgpu_graph* g) { return (g && !g->job) ? g->list.size : 0; }
 
-  // The events of a listed launch. The events object belongs to ALL voices: its host half and e2s_ctl_kernel run for every lane in
-  // every call - note state, the pitch and bend glides and the drift random walk advance for listed and unlisted voices alike -, the
-  // voice kernel then expands the control records of the listed voices only. eventOffset < 0: the call is not an events call.
-  // Before anything else of the call: what it refuses without looking at the block.
-  static int listedEventsReady(mlgpu_graph* g, const char* who0, int eventOffset)
-  {
-    const auto who = [who0] { return std::string(who0); };  // (made where a refusal needs it: the success path allocates nothing)
-    if (eventOffset < 0)
-      return g->desc.hasEventRows ? gfail(g, MLGPU_ERR_INVALID, who() + ": a graph with event rows is run with mlgpu_graph_process_events_listed[_groups]") : MLGPU_OK;
-    if (!g->events) return gfail(g, MLGPU_ERR_INVALID, who() + ": the graph has event rows but no events object (graph_bind_events)");
-    if (!g->desc.voiceListMpeEvents && !mlgpu_events_is_midi(g->events))
-      return gfail(g, MLGPU_ERR_UNSUPPORTED, who() + ": events as graph source nodes: MIDI protocol only (one lane per voice) - mlgpu_graph_enable_voice_list_mpe_events(g, 1) "
-                                                     "before compile makes the listed form for either protocol");
-    return MLGPU_OK;
-  }
-  // The first checks of the two events calls: the switch, the graph's event rows, the offset
+  // The first checks of the two listed events calls: the switch, the graph's event rows, the offset
   static int listedEventsCall(mlgpu_graph* g, const char* who, int startOffset)
   {
     if (!g) return MLGPU_ERR_INVALID;
@@ -1589,25 +1601,6 @@ extern "C"
     if (startOffset < 0) return gfail(g, MLGPU_ERR_INVALID, std::string(who) + ": negative frame offset");
     return MLGPU_OK;
   }
-  // ... and once nothing of the call can be refused any more: the host half and e2s_ctl_kernel, on the engine's stream
-  static int listedEventsPrepare(mlgpu_graph* g, const char* who0, size_t T, int eventOffset, GraphArgs& a, void** staging)
-  {
-    const auto who = [who0] { return std::string(who0); };
-    *staging = nullptr;
-    if (eventOffset < 0) return MLGPU_OK;
-    const int est = mlgpu_events_prepare_for_graph(g->events, T, eventOffset, g->desc.eventRowMask, g->desc.voiceListMpeEvents ? 1 : 0, &a.events, staging);
-    return est == MLGPU_OK ? est : gfail(g, est, who() + ": the events object refused the block: " + g->e->lastError);
-  }
-  // ... and after the voice kernel's launch (or instead of it: an empty list - e2s_ctl_kernel has consumed the lanes' record ranges itself)
-  static int listedEventsLaunched(mlgpu_graph* g, const char* who0, void* staging, hipError_t err)
-  {
-    const auto who = [who0] { return std::string(who0); };
-    if (staging && err != hipSuccess) mlgpu_events_abandoned_by_graph(g->events, staging);
-    if (err != hipSuccess) return gfail(g, MLGPU_ERR_HIP, who() + " launch: " + hipGetErrorString(err));
-    if (staging)
-      if (const int est = mlgpu_events_launched_by_graph(g->events, staging)) return gfail(g, est, who() + ": events bookkeeping after the launch");
-    return MLGPU_OK;
-  }
 
   static int processListed(mlgpu_graph* g, const char* who, size_t T, int eventOffset, const float* const* d_inputs, int inLayout, const float* const* d_controls,
                            float* const* d_outputs, int outLayout, uint32_t* d_peak)
@@ -1616,7 +1609,7 @@ extern "C"
     if (const int st = listsReady(g, who)) return st;
     if (g->desc.voiceListGroups)
       return gfail(g, MLGPU_ERR_INVALID, w() + ": the graph's listed kernel goes by the lane plan (mlgpu_graph_enable_voice_list_groups): mlgpu_" + w() + "_groups runs it");
-    if (const int st = listedEventsReady(g, who, eventOffset)) return st;
+    if (const int st = eventsReady(g, who, eventOffset, true)) return st;
     if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, w() + ": misaligned peaks");
     if (T == 0) return MLGPU_OK;
     if (eventOffset >= 0 && g->e->recording) return gfail(g, MLGPU_ERR_INVALID, w() + ": events route on the host: not while recording a sequence");
@@ -1633,17 +1626,17 @@ extern "C"
       return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
     void* eventStaging = nullptr;
-    if (const int st = listedEventsPrepare(g, who, T, eventOffset, a, &eventStaging)) return st;
+    if (const int st = eventsPrepare(g, who, T, eventOffset, true, a, &eventStaging)) return st;
     if (K == 0)  // (no voice kernel to launch; the sum of no voices: +0.0)
     {
-      if (const int st = listedEventsLaunched(g, who, eventStaging, hipSuccess)) return st;
+      if (const int st = eventsLaunched(g, who, eventStaging, hipSuccess)) return st;
       for (size_t o = 0; o < g->desc.outputs.size(); ++o)
         if (g->desc.outputMix[o] && hipMemsetAsync(d_outputs[o], 0, sizeof(float) * 64 * T, g->e->stream()) != hipSuccess)
           return gfail(g, MLGPU_ERR_HIP, w() + ": clearing a mixed-down output");
       return MLGPU_OK;
     }
     g->listedSinceClear = true;
-    if (const int st = listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream()))) return st;
+    if (const int st = eventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), K, g->e->stream()))) return st;
     return mixdownStages(g, T, d_outputs, K, who);
   }
   int mlgpu_graph_process_listed(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
@@ -1687,7 +1680,7 @@ extern "C"
       return gfail(g, MLGPU_ERR_INVALID,
                    w() + ": not while recording a sequence - the launch's lane count and its rows go with the list's contents, not "
                        "only its length, so a recorded launch could not follow a later list");
-    if (const int st = listedEventsReady(g, who, eventOffset)) return st;
+    if (const int st = eventsReady(g, who, eventOffset, true)) return st;
     if (g->list.outGroup == 0) return gfail(g, MLGPU_ERR_INVALID, w() + ": call mlgpu_graph_reserve_voice_list_groups(graph, max listed voices) at setup");
     if (((uintptr_t)d_peak) & 3) return gfail(g, MLGPU_ERR_INVALID, w() + ": misaligned peaks");
     if (T == 0) return MLGPU_OK;
@@ -1702,10 +1695,10 @@ extern "C"
     if (const int st = outputViews(g, a, T, d_outputs, outLayout, K, J, "")) return st;
     if (hipSetDevice(g->e->device) != hipSuccess) return gfail(g, MLGPU_ERR_HIP, "hipSetDevice");
     void* eventStaging = nullptr;
-    if (const int st = listedEventsPrepare(g, who, T, eventOffset, a, &eventStaging)) return st;
-    if (K == 0) return listedEventsLaunched(g, who, eventStaging, hipSuccess);  // (the events object advanced; no voice kernel)
+    if (const int st = eventsPrepare(g, who, T, eventOffset, true, a, &eventStaging)) return st;
+    if (K == 0) return eventsLaunched(g, who, eventStaging, hipSuccess);  // (the events object advanced; no voice kernel)
     g->listedSinceClear = true;
-    return listedEventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream()));
+    return eventsLaunched(g, who, eventStaging, mlgpu_jit_launch(g->fnListed, &a, sizeof(a), N, g->e->stream()));
   }
   int mlgpu_graph_process_listed_groups(mlgpu_graph* g, size_t T, const float* const* d_inputs, int inLayout, const float* const* d_controls, float* const* d_outputs,
                                         int outLayout, uint32_t* d_peak)

@@ -1,10 +1,12 @@
 // mldsp_events.hpp — the device side of EventsToSignals (source/app/MLEventsToSignals.{h,cpp}) shared by the events kernel
 // (events.hip: all 8 rows into HBM) and the run-time fused graph kernels (graph.hip: pitch and gate as source nodes of a voice
 // graph, never written to memory): the kernels' arguments (the record format and the state layout are mlev_format.hpp), LinearGlide
-// with its 64 slots, note_frame - one frame of a vector that holds note records - and CtlVoice: the control records of
-// e2s_ctl_kernel expanded to the pitch and gate rows inside a voice kernel, one quad of frames at a time - and CtlRows, which reads
-// the rows vox, z, x, y and mod that the control kernel makes for a graph that has them as source nodes. CtlVoiceMpe and CtlRowsMpe are
-// the two for an events object in either protocol (mlgpu_graph_enable_mpe_events): a voice's lane and its instrument's main lane.
+// with its 64 slots, note_frame - one frame of a vector that holds note records - and the two objects of a voice kernel: CtlVoiceOf<MPE>,
+// the control records of e2s_ctl_kernel expanded to the pitch and gate rows, one quad of frames at a time, and CtlRowsOf<MASK, MPE>,
+// which reads the rows vox, z, x, y and mod that the control kernel makes for a graph that has them as source nodes. Each is one
+// definition with two instances: CtlVoice and CtlRows<MASK> (MPE = false) for an events object in the MIDI protocol, a voice's own
+// lane; CtlVoiceMpe and CtlRowsMpe<MASK> (MPE = true; mlgpu_graph_enable_mpe_events) for an events object in either protocol, a voice's
+// lane and its instrument's main lane.
 #pragma once
 #include "mlgpu_device_args.hpp"
 #include "mldsp_math.hpp"
@@ -362,13 +364,12 @@ MLD void note_rewind(const Rec* recs, uint32_t& nc, uint32_t vend, float& veloci
 //     the drift glide's input of this vector, flags. A vector in which the pitch or the gate moves inside the vector (a note event,
 //     a portamento in progress, a moving bend: a few per cent of all vectors) is flagged CF_ROWS and its 64 frames of pitch-before-
 //     drift and gate are written to two side signals, which only the flagged lanes read back.
-//   * the voice kernel (CtlVoice below) expands a record to audio rate. The one per-sample state machine left to it is the drift
+//   * the voice kernel (CtlVoiceOf below) expands a record to audio rate. The one per-sample state machine left to it is the drift
 //     LinearGlide (8 s per glide, a new target every 8-16 s: moving most of the time in most wavefronts, its mCurrVec slots
 //     read and rewritten every vector - 8 B per voice-sample, what reading the two rows used to cost): pitch[n] = P[n] +
 //     (drift[n] * driftAmount) * kDriftScale, the reference's own operation order (:244, :247).
 // Same operations on the same values as e2s_kernel (both use note_frame, note_rewind, PitchGlide and drift_step): a launch of either form
 // leaves the state words the other expects.
-// MIDI protocol only: one lane per playing voice, lane == voice index.
 enum : int
 {
   C_PITCH = 0,   // float: the pitch glide at rest + the held bend term (vPitch after :244), the same for all 64 frames
@@ -398,7 +399,22 @@ MLD BufRsrc lane_buffer(const void* uniformBase, size_t bytes)
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(uniformBase), (short)0, (int)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes), 0x00020000);
 }
 
-struct CtlVoice
+// The parameter MPE of the two objects below. false (CtlVoice, CtlRows): an events object in the MIDI protocol, one lane per playing
+// voice, lane == voice index. true (CtlVoiceMpe, CtlRowsMpe; mlgpu_graph_enable_mpe_events): an events object in either protocol.
+// The protocol is data (E2SSettings::mpe, group, slotBase: a host switches it at run time), so a voice is no longer a lane:
+//   lane of graph voice v = (v / polyphony) * group + (1 + v % polyphony) - slotBase,   its instrument's first lane = (v / polyphony) * group
+// which is v itself under MIDI (group = polyphony, slotBase = 1) and skips the main voice's lane and the padding under MPE (group =
+// nextpow2(polyphony + 1), slotBase = 0). Records, side signals, the held plane and the drift glide's words go by lane; vox stays
+// v % polyphony. Under MPE (:447-458, e2s_kernel's withMain) the main voice's pitch, z, x, y and mod are added to every playing voice
+// that is on: the main lane's record of a vector (e2s_ctl_mpe_kernel: its COMPLETE pitch row, drift term included, in C_PITCH or, where
+// it moves, in rowP), its flags and its held words are fetched with the voice's own; its frames are read only where the main lane is
+// flagged (asked wave-uniformly: several instruments share a wavefront, one may straddle two). All voices of an instrument read the
+// same addresses: one fetch from cache. Nothing new is stored. What MPE adds is compiled into the `true` instance alone
+// (`if constexpr (MPE)`) and there sits behind a scalar of EventsDev (`d.s.mpe`): the operations on a voice's own values are the same
+// in both instances and under either protocol. (The members are laid out for the register allocator as much as for the reader: a
+// generated kernel's code follows the order of the members its instance uses - profiles/event_structs_one_definition.md.)
+template <bool MPE>
+struct CtlVoiceOf
 {
   typedef float f32x4e __attribute__((ext_vector_type(4)));
   // Per lane this object keeps the lane's byte offset, the drift glide's few words, the vector's pitch and gate and ONE set of four
@@ -407,28 +423,51 @@ struct CtlVoice
   size_t T;
   BufRsrc glide;  // the drift glide's words [kGlideWords][lanes]
   uint32_t rowBytes;   // 4 * lanes: one word of every lane
-  uint32_t laneBytes;  // 4 * lane
+  uint32_t laneBytes;  // 4 * the voice's lane
+  uint32_t mainBytes;  // 4 * its instrument's main lane (this and the other words of the main voice: the MPE instance's alone)
   Glide gd;
   float P, gate;
   bool on, rows, gateRow, moving, fetch, ramp;
   bool anyRows, anyRamp, anyOff, anyFetch;  // wave-uniform
   float nd[4];
+  float mP, nmP;       // the main voice's held pitch of this vector / of the next one
+  uint32_t nmF;        // ... and the next one's flags
+  bool mRows, anyMainRows;  // the main voice's pitch of this vector is in rowP; (wave-uniform) ... for some lane
 
   MLD uint32_t glideWord(int w) const { return __builtin_amdgcn_raw_buffer_load_b32(glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
   MLD void setGlideWord(int w, uint32_t x) const { __builtin_amdgcn_raw_buffer_store_b32(x, glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
-  MLD void fetchRecord(size_t t)  // into nd[]: C_PITCH, C_GATE, C_DRIFT_IN, C_FLAGS
+  MLD void fetchRecord(size_t t)  // into nd[]: C_PITCH, C_GATE, C_DRIFT_IN, C_FLAGS; MPE: the main lane's C_PITCH and C_FLAGS
   {
     const BufRsrc rec = lane_buffer(d.ctl + t * (size_t)kCtlRecWords * d.lanes, (size_t)kCtlRecWords * rowBytes);
 #pragma unroll
     for (int k = 0; k < 4; ++k) nd[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
+    if constexpr (MPE)
+    {
+      if (d.s.mpe)
+      {
+        nmP = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_PITCH * rowBytes), 0));
+        nmF = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_FLAGS * rowBytes), 0);
+      }
+    }
   }
   MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
   {
     d = a;
     T = nVectors;
     rowBytes = (uint32_t)d.lanes * 4u;
-    laneBytes = (uint32_t)voice * 4u;
-    glide = lane_buffer(d.state + (size_t)(S_GLIDES + 5 * kGlideWords) * d.lanes, (size_t)kGlideWords * rowBytes);  // glide 5: drift
+    if constexpr (MPE)
+    {
+      const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;  // (the one division of a launch)
+      const uint32_t main = inst * (uint32_t)d.group;
+      mainBytes = main * 4u;
+      laneBytes = (main + 1u + ((uint32_t)voice - inst * (uint32_t)d.s.polyphony) - (uint32_t)d.slotBase) * 4u;
+      mP = nmP = 0.f;
+      nmF = 0u;
+      mRows = anyMainRows = false;
+    }
+    else
+      laneBytes = (uint32_t)voice * 4u;  // (no division)
+    glide =lane_buffer(d.state + (size_t)(S_GLIDES + 5 * kGlideWords) * d.lanes, (size_t)kGlideWords * rowBytes);  // glide 5: drift
     gd.target = u2f(glideWord(0));
     gd.step = u2f(glideWord(1));
     gd.remaining = (int32_t)glideWord(2);
@@ -456,6 +495,15 @@ struct CtlVoice
     gateRow = (f & CF_GATE_ROW) != 0;
     P = on ? nd[C_PITCH] : 0.f;
     gate = on ? nd[C_GATE] : 0.f;
+    if constexpr (MPE)
+    {
+      if (d.s.mpe)
+      {
+        mP = nmP;  // (0 while the main voice is not on: e2s_ctl_mpe_kernel writes it so)
+        mRows = (nmF & CF_ROWS) != 0;
+        anyMainRows = __builtin_amdgcn_ballot_w64(mRows) != 0;
+      }
+    }
     // a glide that starts from a non-uniform mCurrVec reads its slot 63 - this lane's own store of the vector before (once per
     // 8-16 s and voice: asked wave-uniformly)
     float slot63 = 0.f;
@@ -532,6 +580,19 @@ struct CtlVoice
       const float driftSig = moving ? c[k] : prev[k];
       oPitch[k] = Pq[k] + (driftSig * d.s.driftAmount) * 0.02f;  // kDriftScale, :247
     }
+    if constexpr (MPE)
+    {
+      if (d.s.mpe)  // the main voice's pitch row, added to every playing voice that is on (:447-458)
+      {
+        f32x4e M = {mP, mP, mP, mP};
+        if (anyMainRows)
+        {
+          if (mRows) M = *((const f32x4e*)d.rowP + ((t * 16 + (size_t)q) * d.lanes + (size_t)(mainBytes >> 2)));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) oPitch[k] = on ? oPitch[k] + M[k] : oPitch[k];
+      }
+    }
     if (anyOff)  // voices of instruments that have not seen an event yet: processVector is a no-op, the rows are zero (:383-386)
     {
 #pragma unroll
@@ -549,6 +610,8 @@ struct CtlVoice
     if (on) gd.endVector();
   }
 };
+typedef CtlVoiceOf<false> CtlVoice;
+typedef CtlVoiceOf<true> CtlVoiceMpe;
 
 // The rows vox, z, x, y and mod (2..6) of one voice as source nodes of a graph kernel; MASK has bit r for each row r the graph reads.
 // Unlike the drift glide these glides belong to e2s_ctl_kernel: it runs them for every lane in every call, so this object only READS -
@@ -557,29 +620,90 @@ struct CtlVoice
 // from launch to launch: a voice that was off a voice list has the bits of one that never was. vox is a constant of the voice (:302).
 // Memory is addressed as CtlVoice does: a buffer descriptor per plane and the lane's 32-bit byte offset; the side signals, read by
 // the flagged lanes only, through a pointer made inside the rare branch.
-template <uint32_t MASK>
-struct CtlRows
+//
+// The reader is written for ONE lane, L: 0 is the voice's own lane, 1 its instrument's main lane, which the MPE instance reads as well
+// and adds to the voice's rows where the voice is on. Its words are the [L] entries of the members below; the MIDI instance has L = 0
+// alone. The side signals of the voice's own lane are read once and stream past the caches (nontemporal loads); the main lane's are
+// read by every voice of its instrument and should stay in them (plain loads).
+template <uint32_t MASK, bool MPE>
+struct CtlRowsOf
 {
   typedef float f32x4e __attribute__((ext_vector_type(4)));
   static constexpr int N = ctl_row_count(MASK);
   static constexpr int NA = N ? N : 1;
+  static constexpr int LANES = MPE ? 2 : 1;
   EventsDev d;  // (uniform)
   size_t T;
-  uint32_t rowBytes, laneBytes;
+  uint32_t rowBytes, laneBytes[LANES];  // 4 * lanes: one word of every lane; 4 * the lane
   float vox;
-  float hv[NA], nx[NA];    // the held values of this vector / of the next one (fetched during this vector's last quad)
-  uint32_t flags, nflags;  // C_FLAGS of the two
-  bool any[NA];            // wave-uniform: some lane has the row flagged in this vector
+  // (in this order - the held values of all lanes, then the flags of all lanes, then `any` - the compiler allocates the registers of a
+  // kernel: another order is another kernel)
+  struct
+  {
+    float now[NA], next[NA];
+  } held[LANES];  // the held values of this vector / of the next one (fetched during this vector's last quad)
+  struct
+  {
+    uint32_t now, next;
+  } flags[LANES];       // C_FLAGS of the two
+  bool any[LANES][NA];  // wave-uniform: some lane has the row flagged in this vector
+
+  template <int L>
+  MLD void clearLane()
+  {
+    flags[L].now = flags[L].next = 0u;
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+    {
+      held[L].now[k] = held[L].next[k] = 0.f;
+      any[L][k] = false;
+    }
+  }
+  template <int L>
+  MLD void fetchLane(size_t t)
+  {
+    const BufRsrc rec = lane_buffer(d.ctl + (t * (size_t)kCtlRecWords + (size_t)C_FLAGS) * d.lanes, rowBytes);
+    flags[L].next = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes[L], 0, 0);
+    const BufRsrc plane = lane_buffer(d.held + t * (size_t)N * d.lanes, (size_t)N * rowBytes);
+#pragma unroll
+    for (int k = 0; k < N; ++k) held[L].next[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)laneBytes[L], (int)((uint32_t)k * rowBytes), 0));
+  }
+  template <int L>
+  MLD void beginLane()
+  {
+    flags[L].now = flags[L].next;
+#pragma unroll
+    for (int k = 0; k < N; ++k) held[L].now[k] = held[L].next[k];
+#pragma unroll
+    for (int r = 3; r <= 6; ++r)
+      if ((MASK >> r) & 1u) any[L][ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((flags[L].now & CF_ROW(r)) != 0) != 0;
+  }
+  template <int L, int R>
+  MLD f32x4e laneRow(size_t t, int q) const
+  {
+    constexpr int k = ctl_row_rank(MASK, R);
+    f32x4e v = {held[L].now[k], held[L].now[k], held[L].now[k], held[L].now[k]};
+    if (any[L][k])
+    {
+      if (flags[L].now & CF_ROW(R))
+      {
+        const f32x4e* const at = (const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes[L] >> 2));
+        if constexpr (L == 0) v = __builtin_nontemporal_load(at);
+        else v = *at;
+      }
+    }
+    return v;
+  }
 
   MLD void fetch(size_t t)
   {
     if constexpr (N > 0)
     {
-      const BufRsrc rec = lane_buffer(d.ctl + (t * (size_t)kCtlRecWords + (size_t)C_FLAGS) * d.lanes, rowBytes);
-      nflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, 0, 0);
-      const BufRsrc plane = lane_buffer(d.held + t * (size_t)N * d.lanes, (size_t)N * rowBytes);
-#pragma unroll
-      for (int k = 0; k < N; ++k) nx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
+      fetchLane<0>(t);
+      if constexpr (MPE)
+      {
+        if (d.s.mpe) fetchLane<1>(t);
+      }
     }
   }
   MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
@@ -587,291 +711,22 @@ struct CtlRows
     d = a;
     T = nVectors;
     rowBytes = (uint32_t)d.lanes * 4u;
-    laneBytes = (uint32_t)voice * 4u;
-    vox = (float)((uint32_t)voice % (uint32_t)d.s.polyphony);
-    flags = nflags = 0u;
-#pragma unroll
-    for (int k = 0; k < NA; ++k)
+    if constexpr (MPE)
     {
-      hv[k] = nx[k] = 0.f;
-      any[k] = false;
+      const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;
+      const uint32_t slot0 = (uint32_t)voice - inst * (uint32_t)d.s.polyphony;
+      const uint32_t main = inst * (uint32_t)d.group;
+      laneBytes[1] = main * 4u;
+      laneBytes[0] = (main + 1u + slot0 - (uint32_t)d.slotBase) * 4u;
+      vox = (float)slot0;
     }
-    fetch(0);
-  }
-  MLD void begin_vector(size_t t)
-  {
-    (void)t;
-    if constexpr (N > 0)
-    {
-      flags = nflags;
-#pragma unroll
-      for (int k = 0; k < N; ++k) hv[k] = nx[k];
-#pragma unroll
-      for (int r = 3; r <= 6; ++r)
-        if ((MASK >> r) & 1u) any[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((flags & CF_ROW(r)) != 0) != 0;
-    }
-  }
-  MLD void quad(size_t t, int q)
-  {
-    if (q == 15 && t + 1 < T) fetch(t + 1);
-  }
-  template <int R>
-  MLD f32x4e row(size_t t, int q) const
-  {
-    static_assert(R >= 2 && R <= 6 && ((MASK >> R) & 1u), "a row of this graph");
-    if constexpr (R == 2) return f32x4e{vox, vox, vox, vox};
     else
     {
-      constexpr int k = ctl_row_rank(MASK, R);
-      f32x4e v = {hv[k], hv[k], hv[k], hv[k]};
-      if (any[k])
-      {
-        if (flags & CF_ROW(R)) v = __builtin_nontemporal_load((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2)));
-      }
-      return v;
+      laneBytes[0] = (uint32_t)voice * 4u;
+      vox = (float)((uint32_t)voice % (uint32_t)d.s.polyphony);
     }
-  }
-};
-
-// ---- the same two objects for an events object in either protocol (mlgpu_graph_enable_mpe_events) --------------------------------
-// The protocol is data (E2SSettings::mpe, group, slotBase: a host switches it at run time), so a voice is no longer a lane:
-//   lane of graph voice v = (v / polyphony) * group + (1 + v % polyphony) - slotBase,   its instrument's first lane = (v / polyphony) * group
-// which is v itself under MIDI (group = polyphony, slotBase = 1) and skips the main voice's lane and the padding under MPE (group =
-// nextpow2(polyphony + 1), slotBase = 0). Records, side signals, the held plane and the drift glide's words go by lane; vox stays
-// v % polyphony. Under MPE (:447-458, e2s_kernel's withMain) the main voice's pitch, z, x, y and mod are added to every playing voice
-// that is on: the main lane's record of a vector (e2s_ctl_mpe_kernel: its COMPLETE pitch row, drift term included, in C_PITCH or, where
-// it moves, in rowP), its flags and its held words are fetched with the voice's own; its frames are read only where the main lane is
-// flagged (asked wave-uniformly: several instruments share a wavefront, one may straddle two). All voices of an instrument read the
-// same addresses: one fetch from cache. Nothing new is stored. Every `mpe` branch is on a scalar of EventsDev; under MIDI the
-// operations on a voice's values are CtlVoice's and CtlRows' own.
-struct CtlVoiceMpe
-{
-  typedef float f32x4e __attribute__((ext_vector_type(4)));
-  EventsDev d;    // (uniform)
-  size_t T;
-  BufRsrc glide;  // the drift glide's words [kGlideWords][lanes]
-  uint32_t rowBytes;   // 4 * lanes: one word of every lane
-  uint32_t laneBytes;  // 4 * the voice's lane
-  uint32_t mainBytes;  // 4 * its instrument's main lane (MPE)
-  Glide gd;
-  float P, gate;
-  bool on, rows, gateRow, moving, fetch, ramp;
-  bool anyRows, anyRamp, anyOff, anyFetch;  // wave-uniform
-  float nd[4];
-  float mP, nmP;       // the main voice's held pitch of this vector / of the next one
-  uint32_t nmF;        // ... and the next one's flags
-  bool mRows, anyMainRows;  // the main voice's pitch of this vector is in rowP; (wave-uniform) ... for some lane
-
-  MLD uint32_t glideWord(int w) const { return __builtin_amdgcn_raw_buffer_load_b32(glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
-  MLD void setGlideWord(int w, uint32_t x) const { __builtin_amdgcn_raw_buffer_store_b32(x, glide, (int)laneBytes, (int)((uint32_t)w * rowBytes), 0); }
-  MLD void fetchRecord(size_t t)  // into nd[]: C_PITCH, C_GATE, C_DRIFT_IN, C_FLAGS; MPE: the main lane's C_PITCH and C_FLAGS
-  {
-    const BufRsrc rec = lane_buffer(d.ctl + t * (size_t)kCtlRecWords * d.lanes, (size_t)kCtlRecWords * rowBytes);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) nd[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
-    if (d.s.mpe)
-    {
-      nmP = u2f(__builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_PITCH * rowBytes), 0));
-      nmF = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, (int)((uint32_t)C_FLAGS * rowBytes), 0);
-    }
-  }
-  MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
-  {
-    d = a;
-    T = nVectors;
-    rowBytes = (uint32_t)d.lanes * 4u;
-    const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;  // (the one division of a launch)
-    const uint32_t main = inst * (uint32_t)d.group;
-    mainBytes = main * 4u;
-    laneBytes = (main + 1u + ((uint32_t)voice - inst * (uint32_t)d.s.polyphony) - (uint32_t)d.slotBase) * 4u;
-    mP = nmP = 0.f;
-    nmF = 0u;
-    mRows = anyMainRows = false;
-    glide = lane_buffer(d.state + (size_t)(S_GLIDES + 5 * kGlideWords) * d.lanes, (size_t)kGlideWords * rowBytes);  // glide 5: drift
-    gd.target = u2f(glideWord(0));
-    gd.step = u2f(glideWord(1));
-    gd.remaining = (int32_t)glideWord(2);
-    gd.modeFlags = glideWord(3) ? 4 : 0;
-    gd.uniformValue = u2f(glideWord(4));
-    gd.startValue = 0.f;
-    fetchRecord(0);
-  }
-  MLD void store() const
-  {
-    setGlideWord(0, f2u(gd.target));
-    setGlideWord(1, f2u(gd.step));
-    setGlideWord(2, (uint32_t)gd.remaining);
-    setGlideWord(3, gd.isUniform() ? 1u : 0u);
-    setGlideWord(4, f2u(gd.uniformValue));
-  }
-
-  MLD void begin_vector(size_t t)
-  {
-    (void)t;
-    const uint32_t f = f2u(nd[C_FLAGS]);
-    const float din = nd[C_DRIFT_IN];
-    on = (f & CF_ON) != 0;
-    rows = (f & CF_ROWS) != 0;
-    gateRow = (f & CF_GATE_ROW) != 0;
-    P = on ? nd[C_PITCH] : 0.f;
-    gate = on ? nd[C_GATE] : 0.f;
-    if (d.s.mpe)
-    {
-      mP = nmP;  // (0 while the main voice is not on: e2s_ctl_mpe_kernel writes it so)
-      mRows = (nmF & CF_ROWS) != 0;
-      anyMainRows = __builtin_amdgcn_ballot_w64(mRows) != 0;
-    }
-    float slot63 = 0.f;
-    const bool starts = on && ((din != gd.target) || gd.remaining == d.s.driftGlideVectors) && !gd.isUniform();
-    if (__builtin_amdgcn_ballot_w64(starts) != 0)
-    {
-      if (starts) slot63 = u2f(glideWord(5 + 63));
-    }
-    if (on) gd.beginVectorKnown(din, d.s.driftGlideVectors, d.s.driftGlideDy, slot63);
-    const int m = gd.mode();
-    moving = on && m >= 2;
-    ramp = on && m == 2;
-    fetch = on && gd.readsCurrVec();
-    const float hv = (m == 1) ? gd.target : gd.uniformValue;
-    anyRows = __builtin_amdgcn_ballot_w64(rows) != 0;
-    anyRamp = __builtin_amdgcn_ballot_w64(ramp) != 0;
-    anyOff = __builtin_amdgcn_ballot_w64(!on) != 0;
-    anyFetch = __builtin_amdgcn_ballot_w64(fetch) != 0;
-    nd[0] = nd[1] = nd[2] = nd[3] = hv;
-    if (anyFetch)
-    {
-      if (fetch)
-      {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) nd[k] = u2f(glideWord(5 + k));
-      }
-    }
-  }
-
-  MLD void quad(size_t t, int q, f32x4e& oPitch, f32x4e& oGate)
-  {
-    const float prev[4] = {nd[0], nd[1], nd[2], nd[3]};
-    if (q < 15)
-    {
-      if (anyFetch)
-      {
-        if (fetch)
-        {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) nd[k] = u2f(glideWord(5 + 4 * q + 4 + k));
-        }
-      }
-    }
-    else if (t + 1 < T)
-      fetchRecord(t + 1);
-    f32x4e Pq = {P, P, P, P};
-    oGate = f32x4e{gate, gate, gate, gate};
-    if (anyRows)
-    {
-      if (rows)
-      {
-        const size_t at = (t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2);
-        Pq = __builtin_nontemporal_load((const f32x4e*)d.rowP + at);
-        if (gateRow) oGate = __builtin_nontemporal_load((const f32x4e*)d.rowG + at);
-      }
-    }
-    float c[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = prev[k] + gd.step;  // a continuing glide: mCurrVec[n] += step (LinearGlide, MLDSPGens.h:497-505)
-    if (anyRamp)  // a glide's first vector ramps from its start value (:481-495)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-      {
-        const float r = gd.startValue + ((float)(4 * q + k + 1) * 0.015625f) * gd.step;
-        c[k] = ramp ? r : c[k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-    {
-      const float driftSig = moving ? c[k] : prev[k];
-      oPitch[k] = Pq[k] + (driftSig * d.s.driftAmount) * 0.02f;  // kDriftScale, :247
-    }
-    if (d.s.mpe)  // the main voice's pitch row, added to every playing voice that is on (:447-458)
-    {
-      f32x4e M = {mP, mP, mP, mP};
-      if (anyMainRows)
-      {
-        if (mRows) M = *((const f32x4e*)d.rowP + ((t * 16 + (size_t)q) * d.lanes + (size_t)(mainBytes >> 2)));
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) oPitch[k] = on ? oPitch[k] + M[k] : oPitch[k];
-    }
-    if (anyOff)  // voices of instruments that have not seen an event yet: processVector is a no-op, the rows are zero (:383-386)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) oPitch[k] = on ? oPitch[k] : 0.f;
-    }
-    if (moving)
-    {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) setGlideWord(5 + 4 * q + k, f2u(c[k]));
-    }
-  }
-
-  MLD void end_vector()
-  {
-    if (on) gd.endVector();
-  }
-};
-
-template <uint32_t MASK>
-struct CtlRowsMpe
-{
-  typedef float f32x4e __attribute__((ext_vector_type(4)));
-  static constexpr int N = ctl_row_count(MASK);
-  static constexpr int NA = N ? N : 1;
-  EventsDev d;  // (uniform)
-  size_t T;
-  uint32_t rowBytes, laneBytes, mainBytes;
-  float vox;
-  float hv[NA], nx[NA];      // the held values of this vector / of the next one (fetched during this vector's last quad)
-  float mhv[NA], mnx[NA];    // ... and the main voice's (MPE)
-  uint32_t flags, nflags;    // C_FLAGS of the two
-  uint32_t mflags, nmflags;  // ... and the main voice's
-  bool any[NA], anyM[NA];    // wave-uniform: some lane has the row / the main voice's row flagged in this vector
-
-  MLD void fetch(size_t t)
-  {
-    if constexpr (N > 0)
-    {
-      const BufRsrc rec = lane_buffer(d.ctl + (t * (size_t)kCtlRecWords + (size_t)C_FLAGS) * d.lanes, rowBytes);
-      nflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)laneBytes, 0, 0);
-      const BufRsrc plane = lane_buffer(d.held + t * (size_t)N * d.lanes, (size_t)N * rowBytes);
-#pragma unroll
-      for (int k = 0; k < N; ++k) nx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)laneBytes, (int)((uint32_t)k * rowBytes), 0));
-      if (d.s.mpe)
-      {
-        nmflags = __builtin_amdgcn_raw_buffer_load_b32(rec, (int)mainBytes, 0, 0);
-#pragma unroll
-        for (int k = 0; k < N; ++k) mnx[k] = u2f(__builtin_amdgcn_raw_buffer_load_b32(plane, (int)mainBytes, (int)((uint32_t)k * rowBytes), 0));
-      }
-    }
-  }
-  MLD void load(const EventsDev& a, size_t voice, size_t nVectors)
-  {
-    d = a;
-    T = nVectors;
-    rowBytes = (uint32_t)d.lanes * 4u;
-    const uint32_t inst = (uint32_t)voice / (uint32_t)d.s.polyphony;
-    const uint32_t slot0 = (uint32_t)voice - inst * (uint32_t)d.s.polyphony;
-    const uint32_t main = inst * (uint32_t)d.group;
-    mainBytes = main * 4u;
-    laneBytes = (main + 1u + slot0 - (uint32_t)d.slotBase) * 4u;
-    vox = (float)slot0;
-    flags = nflags = mflags = nmflags = 0u;
-#pragma unroll
-    for (int k = 0; k < NA; ++k)
-    {
-      hv[k] = nx[k] = mhv[k] = mnx[k] = 0.f;
-      any[k] = anyM[k] = false;
-    }
+    clearLane<0>();
+    if constexpr (MPE) clearLane<1>();
     fetch(0);
   }
   MLD void begin_vector(size_t t)
@@ -879,20 +734,10 @@ struct CtlRowsMpe
     (void)t;
     if constexpr (N > 0)
     {
-      flags = nflags;
-#pragma unroll
-      for (int k = 0; k < N; ++k) hv[k] = nx[k];
-#pragma unroll
-      for (int r = 3; r <= 6; ++r)
-        if ((MASK >> r) & 1u) any[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((flags & CF_ROW(r)) != 0) != 0;
-      if (d.s.mpe)
+      beginLane<0>();
+      if constexpr (MPE)
       {
-        mflags = nmflags;
-#pragma unroll
-        for (int k = 0; k < N; ++k) mhv[k] = mnx[k];
-#pragma unroll
-        for (int r = 3; r <= 6; ++r)
-          if ((MASK >> r) & 1u) anyM[ctl_row_rank(MASK, r)] = __builtin_amdgcn_ballot_w64((mflags & CF_ROW(r)) != 0) != 0;
+        if (d.s.mpe) beginLane<1>();
       }
     }
   }
@@ -907,24 +752,22 @@ struct CtlRowsMpe
     if constexpr (R == 2) return f32x4e{vox, vox, vox, vox};
     else
     {
-      constexpr int k = ctl_row_rank(MASK, R);
-      f32x4e v = {hv[k], hv[k], hv[k], hv[k]};
-      if (any[k])
+      f32x4e v = laneRow<0, R>(t, q);
+      if constexpr (MPE)
       {
-        if (flags & CF_ROW(R)) v = __builtin_nontemporal_load((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(laneBytes >> 2)));
-      }
-      if (d.s.mpe)  // the main voice's row, added where the voice is on (:447-458)
-      {
-        f32x4e m = {mhv[k], mhv[k], mhv[k], mhv[k]};
-        if (anyM[k])
+        if (d.s.mpe)  // the main voice's row, added where the voice is on (:447-458)
         {
-          if (mflags & CF_ROW(R)) m = *((const f32x4e*)d.rowC[R - 3] + ((t * 16 + (size_t)q) * d.lanes + (size_t)(mainBytes >> 2)));
+          const f32x4e m = laneRow<1, R>(t, q);
+          if (flags[0].now & CF_ON) v = v + m;
         }
-        if (flags & CF_ON) v = v + m;
       }
       return v;
     }
   }
 };
+template <uint32_t MASK>
+using CtlRows = CtlRowsOf<MASK, false>;
+template <uint32_t MASK>
+using CtlRowsMpe = CtlRowsOf<MASK, true>;
 
 }  // namespace mlev
