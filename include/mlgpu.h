@@ -942,6 +942,65 @@ int mlgpu_bank_apply_updates(mlgpu_bank* b, const mlgpu_update* recs, size_t n);
 int mlgpu_graph_get_param(mlgpu_graph* g, int param_node, float* h_per_voice);
 int mlgpu_graph_get_coeff(mlgpu_graph* g, int proc_node, int coeff_idx, float* h_per_voice);
 
+/* ---- Voice records: listed voices' whole state to and from a device buffer ------------------------------------------------------
+ * The getters and setters above move one row of ALL voices through the host and wait for the device, and nothing reads or writes a
+ * voice's delay rings. A host that takes a voice WITH its sound somewhere else - into a rebuilt larger graph, onto another device,
+ * aside and back - moves records: mlgpu_*_export_voices gathers the listed voices' state into a DEVICE buffer of n records,
+ * mlgpu_*_import_voices scatters records into the listed voices, each by one small kernel on the engine's stream, ordered between
+ * the process calls around it. The call never waits for the device (except for its own call before last), and after a reserve never
+ * allocates.
+ *
+ * A record is W = mlgpu_*_voice_record_words() 32-bit words (0 before compile), W a multiple of 4; d_records is [n][W] words,
+ * voice-major, 16-byte aligned, record i belonging to voice h_voices[i]. Its words, in order: the voice's word of every params
+ * row, of every coefficient row, of every state row (feedback nodes' stored vectors included), a bank's input-const word, zeros up to
+ * a multiple of 4, then node by node in node order the voice's delay-ring words in ascending address order of the voice's own ring
+ * memory. A record is an exact image: write indices and every other state word go as they are, so a moved voice continues its
+ * sound bit for bit. Banks have no rings.
+ *
+ * What a record does NOT hold: the per-voice state of a bound events object (mlgpu_graph_bind_events); live constants, constant
+ * DSPVectors and impulse tables, which are the graph's, not a voice's; the graph's DSPVector count. A voice whose two
+ * PitchbendableDelay write indices a host set apart (mlgpu_graph_set_state) belongs only in a graph where the host did the same
+ * before the first launch after a clear: such a delay keeps one ring while the two indices agree and leaves the second unwritten.
+ *
+ * mlgpu_*_voice_record_signature() is a 64-bit value over the record format, mlgpu_behaviour_revision(), every node's type, kind,
+ * coefficient and state counts, ring length and ring count, the number of param rows, and the delay layout the compile resolved to.
+ * It does not cover n_voices, the device, constants or the voice-list switches: two objects with equal signatures exchange records
+ * (a graph of 80 voices and one of 600 with the same description and layout; banks of the same chain). import takes the signature
+ * the records were exported under and refuses another (MLGPU_ERR_UNSUPPORTED); records are not converted between delay layouts.
+ *
+ * export takes any voices in any order, repeats allowed; import wants distinct voices in any order. In delay layout 2 with
+ * n_voices % 64 != 0 an import of the last voice writes the ring memory of the last wavefront's spare lanes too, which run that
+ * voice again (as MLGPU_UPDATE_CLEAR_RINGS does). h_voices is HOST memory and is the caller's again when the call returns.
+ *
+ * Everything is validated before anything is enqueued; a refused call changes no word. MLGPU_ERR_INVALID: an object that is not
+ * compiled, a null pointer (or a record buffer that is not 16-byte aligned), a voice twice in an import, a call while recording a
+ * sequence (it reads host memory; between the launches of a recorded sequence it works). MLGPU_ERR_RANGE: a voice >= n_voices, n
+ * above the reserve. MLGPU_ERR_BUSY: a compile job owns the graph. MLGPU_ERR_UNSUPPORTED, with the reason in the error text: another
+ * signature; a graph with a DOWNSAMPLE_2X region (its pairing of DSPVectors is per graph, not per voice: voice lists' reason too); an
+ * IMPORT into a graph that keeps a PitchbendableDelay in delay layout 4 without mlgpu_graph_enable_voice_list_rings - its plain
+ * kernel decides "one ring" per wavefront from a write index it takes to be the wavefront's, and one imported voice on another clock
+ * would send its 63 neighbours through a second ring nobody wrote (export from such a graph is fine). With
+ * mlgpu_graph_enable_voice_list_rings the listed kernels decide per lane: import is allowed and counts as a listed launch -
+ * mlgpu_graph_process is refused until the next mlgpu_graph_clear, run all voices through mlgpu_graph_process_listed. n == 0: MLGPU_OK.
+ *
+ * An imported voice keeps its write index. In delay layouts 2 and 4 the plain kernel runs its windows / trips on a write index
+ * that is the same in every lane of a wavefront; a wavefront whose lanes differ falls back to per-sample accesses - the same
+ * samples, more slowly (profiles/voice_records.md) - until the next mlgpu_graph_clear. In layout 0 the imported voice's ring words
+ * lie in other rows than its neighbours': more memory sectors per access, nothing else.
+ *
+ * mlgpu_*_reserve_voice_records(max_voices) is setup (it allocates and waits): from then on export and import never allocate and
+ * refuse n > max_voices. Without a reserve the staging buffers grow inside the call: a setup convenience that allocates and may wait. */
+size_t mlgpu_graph_voice_record_words(mlgpu_graph* g);
+uint64_t mlgpu_graph_voice_record_signature(mlgpu_graph* g);
+int mlgpu_graph_reserve_voice_records(mlgpu_graph* g, size_t max_voices);
+int mlgpu_graph_export_voices(mlgpu_graph* g, const uint32_t* h_voices, size_t n, uint32_t* d_records);
+int mlgpu_graph_import_voices(mlgpu_graph* g, uint64_t signature, const uint32_t* h_voices, size_t n, const uint32_t* d_records);
+size_t mlgpu_bank_voice_record_words(mlgpu_bank* b);
+uint64_t mlgpu_bank_voice_record_signature(mlgpu_bank* b);
+int mlgpu_bank_reserve_voice_records(mlgpu_bank* b, size_t max_voices);
+int mlgpu_bank_export_voices(mlgpu_bank* b, const uint32_t* h_voices, size_t n, uint32_t* d_records);
+int mlgpu_bank_import_voices(mlgpu_bank* b, uint64_t signature, const uint32_t* h_voices, size_t n, const uint32_t* d_records);
+
 /* VOICE LISTS FOR GRAPHS: run only the listed voices of a graph, with the bank's rule and call discipline (VOICE LISTS above). With the
  * list L[0 .. K) - voice indices, strictly ascending, all below n_voices - a listed process call behaves exactly as a graph of K voices
  * with the same description, made of voices L[0] ... L[K-1] in that order.

@@ -931,9 +931,51 @@ def _update_array(records):
     return (Update * max(1, len(records)))(*records), len(records)
 
 
-class Bank(_Handle):
+class _VoiceRecords:
+    """Voice records of a Graph or a Bank (mlgpu_*_export_voices / _import_voices): listed voices' whole state - params, coefficients,
+    state, a bank's input const, a graph's delay rings - to and from a device buffer of [n][voice_record_words] uint32 words, by one
+    small kernel on the engine's stream; no wait for the device. Objects with equal voice_record_signature exchange records."""
+
+    def _vr(self, name):
+        return getattr(self.L, "mlgpu_%s_%s" % (self._records_owner, name))
+
+    def _vr_check(self, st):
+        (self._check if hasattr(self, "_check") else self.engine._check)(st)
+
+    @property
+    def voice_record_words(self):
+        """W, the 32-bit words of one record (a multiple of 4; 0 before compile)."""
+        return int(self._vr("voice_record_words")(self.h))
+
+    @property
+    def voice_record_signature(self):
+        return int(self._vr("voice_record_signature")(self.h))
+
+    def reserve_voice_records(self, max_voices):
+        """Setup: from now on export_voices / import_voices never allocate, and refuse (Status.ERR_RANGE) more voices in one call."""
+        self._vr_check(self._vr("reserve_voice_records")(self.h, int(max_voices)))
+
+    def export_voices(self, voices, d_records=None):
+        """The listed voices' records into d_records (a DeviceBuffer or a raw pointer; made here if None), record i of voices[i]:
+        any voices in any order. Returns the device buffer."""
+        v = np.ascontiguousarray(voices, np.uint32).reshape(-1)
+        if d_records is None:
+            d_records = self.engine.alloc(max(16, 4 * v.size * self.voice_record_words))
+        p = ctypes.c_void_p(d_records.ptr if hasattr(d_records, "ptr") else int(d_records))
+        self._vr_check(self._vr("export_voices")(self.h, _np_ptr(v) if v.size else None, v.size, p))
+        return d_records
+
+    def import_voices(self, signature, voices, d_records):
+        """Record i of d_records into voice voices[i] (distinct voices, any order); `signature` is the exporting object's."""
+        v = np.ascontiguousarray(voices, np.uint32).reshape(-1)
+        p = ctypes.c_void_p(d_records.ptr if hasattr(d_records, "ptr") else int(d_records))
+        self._vr_check(self._vr("import_voices")(self.h, int(signature), _np_ptr(v) if v.size else None, v.size, p))
+
+
+class Bank(_Handle, _VoiceRecords):
     """Runtime-sized Bank<T,ROWS> (reference MLDSPFunctional.h:321-360): V voices of one chain."""
     _destroy = "mlgpu_bank_destroy"
+    _records_owner = "bank"
 
     def __init__(self, engine, procs, n_voices):
         self.engine = engine
@@ -1233,7 +1275,7 @@ class OfflineEngine:
             raise MlgpuError(st, "offline graph (no engine): status %d" % st)
 
 
-class Graph(_Handle):
+class Graph(_Handle, _VoiceRecords):
     """A run-time defined per-voice DAG of processors and ops, fused into one kernel (mlgpu_graph).
 
     Nodes are named (after the reference's proc convention, source/procs/MLProcMultiply.cpp:12-18) and
@@ -1241,6 +1283,7 @@ class Graph(_Handle):
       {"name", "type": "input"|"param"|"const"|"proc"|"op", "kind": Proc.X / Op.X, "inputs": [names], "value"}
     """
     _destroy = "mlgpu_graph_destroy"
+    _records_owner = "graph"
 
     def __init__(self, engine, n_voices, description=None, outputs=None, voices_per_lane=0, delay_windows=False, autotune=False,
                  live_constants=False, output_groups=None, input_groups=None, compile_now=True, voice_lists=False, voice_list_groups=False,

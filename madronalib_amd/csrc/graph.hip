@@ -112,6 +112,7 @@ struct mlgpu_graph
   OwnedEvent tuneEv0, tuneEv1;
   int inLayoutOverride[MLGPU_GRAPH_MAX_INPUTS];  // -1: none
   mlgpu_updater updates;         // mlgpu_graph_apply_updates: the planner, the tables' description, the staging sets
+  mlgpu_recorder records;        // mlgpu_graph_export_voices / _import_voices: the record layout, the staging sets
   mlgpu_graph()
   {
     for (int& x : inLayoutOverride) x = -1;
@@ -1186,6 +1187,87 @@ extern "C"
   // Not in mlgpu.h: the tests' view of the staging sets (their four buffer addresses, the capacity in records), to see that
   // apply_updates after a reserve leaves them alone
   size_t mlgpu_graph_update_staging(mlgpu_graph* g, const void** four) { return (g && !g->job && four) ? mlgpu_updater_staging(g->updates, four) : 0; }
+
+  // ---- voice records: listed voices' whole state to and from a device buffer (voice_records.hpp plans, voice_records.hip moves) ----
+  // The compiled graph's record layout and signature, from the tables' description the updates keep
+  static int recordsReady(mlgpu_graph* g, const char* who)
+  {
+    if (const int st = updatesReady(g, who)) return st;
+    mlgpu_recorder& r = g->records;
+    if (!r.described)
+    {
+      std::vector<mlrec::NodeSig> sigs(g->desc.nodes.size());
+      for (size_t i = 0; i < sigs.size(); ++i)
+      {
+        const Node& n = g->desc.nodes[i];
+        sigs[i].type = n.type;
+        sigs[i].kind = n.kind;
+        sigs[i].ringLen = (uint32_t)n.ringLen;
+        sigs[i].rings = n.type == NODE_PROC ? (uint32_t)mlgpu_proc_rings(n.kind) : 0u;
+      }
+      r.plan.describe(g->updates.desc, sigs, apiLayout(g->build->plan.rings), mlgpu_behaviour_revision());
+      r.described = true;
+    }
+    if (!r.plan.described()) return gfail(g, MLGPU_ERR_UNSUPPORTED, std::string(who) + ": " + r.plan.error());
+    return MLGPU_OK;
+  }
+  // The refusals of a move that are the graph's own, before anything is enqueued
+  static int recordsMovable(mlgpu_graph* g, const char* who, bool import)
+  {
+    for (const Region& R : g->desc.regions)
+      if (R.kind == MLGPU_REGION_DOWNSAMPLE_2X)
+        return gfail(g, MLGPU_ERR_UNSUPPORTED, std::string(who) + ": a graph with a DOWNSAMPLE_2X region pairs its DSPVectors by a count that is the graph's, not a voice's: a voice's record would not say which half of a pair it stands at");
+    if (import && g->build->plan.rings == RingLayout::SECTORS && !g->build->plan.ringsByLaneOnly)
+      for (const Node& n : g->desc.nodes)
+        if (n.type == NODE_PROC && n.kind == MLGPU_PROC_PITCHBENDABLE_DELAY)
+          return gfail(g, MLGPU_ERR_UNSUPPORTED,
+                       std::string(who) + ": a PitchbendableDelay in delay layout 4 keeps one ring per WAVEFRONT while its voices' write indices agree, and an imported voice brings its own: "
+                                          "its neighbours would read a second ring nobody wrote. Compile the graph with mlgpu_graph_enable_voice_list_rings (the listed kernels decide per lane), "
+                                          "or use another delay layout");
+    return MLGPU_OK;
+  }
+  size_t mlgpu_graph_voice_record_words(mlgpu_graph* g)
+  {
+    if (!g || g->job || !g->compiled) return 0;
+    return recordsReady(g, "graph_voice_record_words") ? 0 : g->records.plan.words();
+  }
+  uint64_t mlgpu_graph_voice_record_signature(mlgpu_graph* g)
+  {
+    if (!g || g->job || !g->compiled) return 0;
+    return recordsReady(g, "graph_voice_record_signature") ? 0 : g->records.plan.signature();
+  }
+  int mlgpu_graph_reserve_voice_records(mlgpu_graph* g, size_t maxVoices)
+  {
+    if (const int st = recordsReady(g, "graph_reserve_voice_records")) return st;
+    std::string err;
+    const int st = mlgpu_recorder_reserve(g->e, g->records, maxVoices, err);
+    return st == MLGPU_OK ? st : gfail(g, st, "graph_" + err);
+  }
+  static int moveVoices(mlgpu_graph* g, const char* who, const uint32_t* h_voices, size_t n, uint32_t* d_records, bool import)
+  {
+    uint32_t* const tables[mlupd::kTables] = {(uint32_t*)g->d_params.get(), (uint32_t*)g->d_coeffs.get(), g->d_state.get(), nullptr};
+    std::string err;
+    const int st = mlgpu_recorder_move(g->e, g->records, tables, (uint32_t*)g->d_mem.get(), g->build->plan.memVoices * g->build->plan.memFloatsPerVoice, h_voices, n, d_records, import, err);
+    return st == MLGPU_OK ? st : gfail(g, st, "graph_" + err);
+  }
+  int mlgpu_graph_export_voices(mlgpu_graph* g, const uint32_t* h_voices, size_t n, uint32_t* d_records)
+  {
+    if (const int st = recordsReady(g, "graph_export_voices")) return st;
+    if (const int st = recordsMovable(g, "graph_export_voices", false)) return st;
+    return moveVoices(g, "graph_export_voices", h_voices, n, d_records, false);
+  }
+  int mlgpu_graph_import_voices(mlgpu_graph* g, uint64_t signature, const uint32_t* h_voices, size_t n, const uint32_t* d_records)
+  {
+    if (const int st = recordsReady(g, "graph_import_voices")) return st;
+    if (signature != g->records.plan.signature())
+      return gfail(g, MLGPU_ERR_UNSUPPORTED, "graph_import_voices: the records' signature differs from this graph's (another description, ring layout, record format or behaviour revision): such objects do not exchange records");
+    if (const int st = recordsMovable(g, "graph_import_voices", true)) return st;
+    const int st = moveVoices(g, "graph_import_voices", h_voices, n, (uint32_t*)d_records, true);
+    // the imported voices' write indices differ from their neighbours' now, as after a listed launch (processPlain)
+    if (st == MLGPU_OK && n && g->build->plan.ringsByLaneOnly) g->listedSinceClear = true;
+    return st;
+  }
+  size_t mlgpu_graph_voice_record_staging(mlgpu_graph* g, const void** four) { return (g && !g->job && four) ? mlgpu_recorder_staging(g->records, four) : 0; }  // (not in mlgpu.h: the tests' view, as mlgpu_graph_update_staging)
 
   int mlgpu_graph_set_delay_layout(mlgpu_graph* g, int windowed)
   {

@@ -16,6 +16,7 @@
 #include "mlgpu_device_args.hpp"
 #include "param_updates.hpp"
 #include "staging_turns.hpp"
+#include "voice_records.hpp"
 
 // Owning device memory, pinned host memory and HIP events: every handle frees what it holds by deleting its members
 struct DeviceFree
@@ -351,6 +352,28 @@ size_t mlgpu_updater_device_records(mlgpu_updater& u, const mlgpu_update* recs, 
 int mlgpu_updater_apply(mlgpu_engine* e, mlgpu_updater& u, uint32_t* const* tables, uint32_t* ringMem, size_t ringMemWords, const mlgpu_update* recs, size_t n,
                         std::string& err);
 size_t mlgpu_updater_staging(const mlgpu_updater& u, const void** four);  // (test hook: buffer addresses and capacity)
+
+// voice_records.hip — voice records (mlgpu_graph_export_voices / _import_voices and the bank's): what a graph or a bank keeps for
+// them. `plan` holds the record layout, made by the owner from its updater's table description (once); the two staging sets carry a
+// call's segments and entries and take turns.
+struct mlgpu_recorder
+{
+  mlrec::RecordPlan plan;
+  bool described{false};  // (tried: plan.described() says whether the object has a layout)
+  struct Set
+  {
+    PinnedBuffer<uint32_t> h_words;
+    DeviceBuffer<uint32_t> d_words;
+    size_t capacity{0};
+  };
+  StagingTurns<Set> stage;
+  size_t reserved{0};  // reserve_voice_records: voices per call (0: no reserve, the buffers grow inside the call)
+};
+int mlgpu_recorder_reserve(mlgpu_engine* e, mlgpu_recorder& r, size_t maxVoices, std::string& err);
+// tables / ringMem as mlgpu_updater_apply takes them; d_records[n][plan.words()]; import: records -> the object, else the object -> records
+int mlgpu_recorder_move(mlgpu_engine* e, mlgpu_recorder& r, uint32_t* const* tables, uint32_t* ringMem, size_t ringMemWords, const uint32_t* h_voices, size_t n,
+                        uint32_t* d_records, bool import, std::string& err);
+size_t mlgpu_recorder_staging(const mlgpu_recorder& r, const void** four);  // (test hook: buffer addresses and capacity in words)
 
 // capi.hip — the voice list of a bank or a graph (mlgpu_bank_set_voice_list, mlgpu_graph_set_voice_list). The list in force lives in ONE
 // device buffer, written by copies on the engine's stream: a listed launch - a recorded one too, which has the address - reads
