@@ -1415,10 +1415,12 @@ int mlgpu_graph_enable_mpe_events(mlgpu_graph* g, int on);
  *   1. mlgpu_events_add_events                       the block's events
  *   2. mlgpu_events_route_ahead(ev, T, off)
  *   3. mlgpu_events_sounding_voices
- *   4. the host unions them with its tails: voices listed earlier whose d_peak has not died away yet (profiles/voice_list.md)
+ *   4. mlgpu_tails_next_list(t, the sounding voices, ...)   their union with the tails: voices listed earlier whose d_peak has not
+ *                                                    died away yet (VOICE TAILS, below)
  *   5. mlgpu_graph_set_voice_list
- *   6. mlgpu_graph_process_events_listed[_groups](g, T, off, ...)
- *   7. mlgpu_events_clear_events at the block's end
+ *   6. mlgpu_graph_process_events_listed[_groups](g, T, off, ..., d_peak)
+ *   7. mlgpu_tails_note(t, T, d_peak)
+ *   8. mlgpu_events_clear_events at the block's end
  * A note-on that lands on a voice the host did not list is not an error: the events object has it, the voice is silent until listed. */
 int mlgpu_graph_enable_voice_list_events(mlgpu_graph* g, int on);
 int mlgpu_graph_process_events_listed(mlgpu_graph* g, size_t n_vectors, int start_offset, const float* const* d_inputs, int in_layout,
@@ -1481,6 +1483,72 @@ int mlgpu_events_sounding_voices(mlgpu_events* ev, uint32_t* h_voices, size_t ca
  * of the voices against 1.26 ms for all of them); what the list frees is the chip's other SIMDs and the rows of all voices. */
 int mlgpu_graph_enable_voice_list_mpe_events(mlgpu_graph* g, int on);
 int mlgpu_events_sounding_graph_voices(mlgpu_events* ev, uint32_t* h_voices, size_t capacity, size_t* n);
+
+/* VOICE TAILS: the engine tells which listed voices have died away, and the host never waits for it.
+ *
+ * A voice that is no longer held still sounds - a release, a string, a reverb - and has to stay listed until it has died away. What
+ * says so is d_peak, which every listed process call writes - bank or graph, plain list or lane plan, MIDI or MPE -, and d_peak is
+ * device memory. An mlgpu_tails object looks at the peaks of every listed launch ON THE DEVICE, brings one bit per list position to
+ * the host behind an event that is only ever queried, and makes the next list under the one rule below, which never drops a voice
+ * early however late the device is. It belongs to neither a bank nor a graph: it needs the list, which it made itself, and a device
+ * pointer to K peak words by list position. The block (step 4 and 7 of the intended block above; a bank's is the same without events):
+ *   mlgpu_tails_next_list(t, S, n_S, L, capacity, &K)     S: what the host wants listed regardless - the router's sounding set
+ *   mlgpu_graph_set_voice_list(g, L, K)                   (mlgpu_events_sounding_graph_voices) plus anything of its own
+ *   mlgpu_graph_process_events_listed(..., d_peak)
+ *   mlgpu_tails_note(t, n_vectors, d_peak)
+ *
+ * THE RULE. The lists made by mlgpu_tails_next_list are numbered L_1, L_2, ...; S_j is the must-set L_j was made from.
+ *   Loud or quiet. In a noted launch, list position i is LOUD iff d_peak[i] > quiet_bits, compared as unsigned integers - d_peak holds
+ *   bits(|y|), so that is the float comparison for every finite threshold, and a NaN peak is loud. Otherwise the position is quiet.
+ *   Taking in. Results are taken in strictly in order, each once, by mlgpu_tails_next_list and mlgpu_tails_wait only. Taking in launch
+ *   j does this for every v in L_j: if v is in S_j or v was loud, quiet[v] = 0; otherwise quiet[v] += n_vectors_j, saturating.
+ *   A list that was never noted - a second next_list with no note in between, a note that answered MLGPU_ERR_BUSY - is taken in, in
+ *   its turn, with no peaks and without waiting for anything: only its must-set's resets apply.
+ *   The next list. next_list first takes in every result that is complete: it asks each event in order and stops at the first that
+ *   is not. Let c be the last launch taken in and m the last list made. Then
+ *     L_m+1 = S_m+1  u  { v in L_m : quiet[v] < hold_vectors, or v in S_j for some c < j <= m },   ascending.
+ *   Consequences:
+ *   (a) Lateness only delays a drop. However late the device is, L_m+1 is a superset of what the same calls give when every result is
+ *       taken in before each next_list: a result not taken in leaves quiet[v] where it was or keeps v through the second clause.
+ *       (Under one hold_vectors, or one that was only raised: a lowered hold is a new rule from the list it first applies to.)
+ *   (b) A voice is dropped only after hold_vectors DSPVectors of consecutive quiet launches since it was last in a must-set or loud,
+ *       all of them taken in. A retriggered string is protected from its note-on, not only from its first loud sample; a voice that is
+ *       silent between two echoes stays when hold_vectors spans the gap.
+ *   (c) After mlgpu_tails_wait the next list is the synchronous one.
+ *
+ * mlgpu_tails_create(e, n_voices, max_listed, depth, &t): setup, the one call that allocates (and refused while a sequence is being
+ *   recorded). max_listed: the longest list it will make (at most n_voices); depth, 1 .. 8: the results that may be outstanding. Each
+ *   of the depth slots holds ceil(max_listed / 64) device words, as many pinned words, an event and the host's copy of the list. The
+ *   threshold starts as quiet_bits = the bits of 1e-4f, hold_vectors = 1.
+ * mlgpu_tails_destroy: the one release rule of C-API objects; it waits for the stream, and with it for the object's own copies.
+ * mlgpu_tails_set_threshold(t, quiet_bits, hold_vectors): quiet_bits holds for the notes, hold_vectors for the lists, from now on.
+ *   hold_vectors is 1 or more, else MLGPU_ERR_INVALID.
+ * mlgpu_tails_clear: no list, nothing outstanding, every voice as never listed. It does not wait: a result in flight lands in its
+ *   slot's words, and a later note of that slot is enqueued behind it.
+ * mlgpu_tails_next_list(t, h_must, n_must, h_list, capacity, &n): h_must is looked at completely before anything changes, with the
+ *   statuses of mlgpu_bank_set_voice_list - strictly ascending (MLGPU_ERR_INVALID), below n_voices (MLGPU_ERR_RANGE). MLGPU_ERR_RANGE
+ *   with *n set when the list is longer than capacity or max_listed: no list is made or numbered, and the call may be repeated.
+ *   (Results that were complete have been taken in by then, as the repeat would.) Otherwise h_list[0 .. *n) is L_m+1, which now
+ *   waits for its note.
+ * mlgpu_tails_note(t, n_vectors, d_peak): the last list made was run for n_vectors DSPVectors and d_peak has its K peak words
+ *   (4-byte aligned), written by work enqueued on the engine before this call. One launch of one lane per list position - a 64-bit
+ *   ballot per wavefront, one word per wavefront stored -, a copy of ceil(K / 64) words into the slot's pinned words, an event. K = 0
+ *   enqueues nothing and is complete at once. MLGPU_ERR_INVALID when no list is waiting for it (none made, or noted already), when
+ *   d_peak is null or misaligned, or while a sequence is being recorded; the list goes on waiting. MLGPU_ERR_BUSY, with nothing
+ *   enqueued, when depth results are outstanding: the list then stays without peaks.
+ * mlgpu_tails_pending: the launches noted whose result has not been taken in.
+ * mlgpu_tails_wait: tools and tests - waits for every noted result and takes it in.
+ * After create no call allocates. next_list and note never wait for the device: they query events. No call walks the n_voices: a
+ *   result taken in costs O(K), a list O(K + n_must). One caller thread, like every object of an engine. */
+typedef struct mlgpu_tails mlgpu_tails;
+int mlgpu_tails_create(mlgpu_engine* e, size_t n_voices, size_t max_listed, int depth, mlgpu_tails** out);
+int mlgpu_tails_destroy(mlgpu_tails* t);
+int mlgpu_tails_set_threshold(mlgpu_tails* t, uint32_t quiet_bits, uint32_t hold_vectors);
+int mlgpu_tails_clear(mlgpu_tails* t);
+int mlgpu_tails_next_list(mlgpu_tails* t, const uint32_t* h_must, size_t n_must, uint32_t* h_list, size_t capacity, size_t* n);
+int mlgpu_tails_note(mlgpu_tails* t, size_t n_vectors, const uint32_t* d_peak);
+size_t mlgpu_tails_pending(mlgpu_tails* t);
+int mlgpu_tails_wait(mlgpu_tails* t);
 
 /* ------------------------------------------------------------------------- */
 /* published signals                                                        */

@@ -884,6 +884,56 @@ class Resampler(_Handle):
         return res.download(np.float32, V * 64 * Tout).reshape(V, 64 * Tout)
 
 
+class VoiceTails(_Handle):
+    """Which listed voices have died away (mlgpu_tails): watches the peaks of every listed launch on the device, brings the loud bits
+    to the host behind an event it only queries, and makes the next list under the rule of include/mlgpu.h (VOICE TAILS), which never
+    drops a voice early however late the device is. The block: next_list(must) -> set_voice_list -> process_*listed*(d_peak=..) ->
+    note(n_vectors, d_peak)."""
+    _destroy = "mlgpu_tails_destroy"
+
+    def __init__(self, engine, n_voices, max_listed, depth=4):
+        self.engine, self.L = engine, engine.L
+        self.V, self.max_listed, self.depth = int(n_voices), min(int(max_listed), int(n_voices)), int(depth)
+        h = ctypes.c_void_p()
+        engine._check(self.L.mlgpu_tails_create(engine.h, self.V, int(max_listed), self.depth, ctypes.byref(h)))
+        self.h = h
+        self._list = np.zeros(max(self.max_listed, 1), np.uint32)
+        engine._children.add(self)
+
+    def set_threshold(self, quiet=1e-4, hold_vectors=1):
+        """A list position is loud when its peak is above `quiet` (a float, taken by its bits); a voice leaves after hold_vectors
+        DSPVectors of consecutive quiet launches since it was last in a must-set or loud."""
+        bits = int(np.float32(quiet).view(np.uint32))
+        self.engine._check(self.L.mlgpu_tails_set_threshold(self.h, bits, int(hold_vectors)))
+
+    def clear(self):
+        self.engine._check(self.L.mlgpu_tails_clear(self.h))
+
+    def next_list(self, must=()):
+        """The next list (ascending, uint32): `must` - strictly ascending voice indices, e.g. Events.sounding_graph_voices() - and the
+        voices of the last list that have not died away. Takes in the results that are there; never waits for the device."""
+        m = np.ascontiguousarray(must, np.uint32).reshape(-1)
+        n = ctypes.c_size_t()
+        self.engine._check(self.L.mlgpu_tails_next_list(self.h, _np_ptr(m) if m.size else None, m.size, _np_ptr(self._list), self._list.size,
+                                                        ctypes.byref(n)))
+        return self._list[:n.value].copy()
+
+    def note(self, n_vectors, d_peak):
+        """The last list was run for n_vectors DSPVectors and d_peak (device, K uint32 words by list position) has its peaks. Raises
+        MlgpuError with Status.ERR_BUSY, nothing enqueued, when `depth` results are outstanding."""
+        pp = ctypes.c_void_p(d_peak.ptr if hasattr(d_peak, "ptr") else int(d_peak))
+        self.engine._check(self.L.mlgpu_tails_note(self.h, int(n_vectors), pp))
+
+    @property
+    def pending(self):
+        """Launches noted whose result has not been taken in."""
+        return int(self.L.mlgpu_tails_pending(self.h))
+
+    def wait(self):
+        """Tools and tests: wait for every noted result and take it in."""
+        self.engine._check(self.L.mlgpu_tails_wait(self.h))
+
+
 class Update(ctypes.Structure):  # mlgpu_update
     """One record of Graph.apply_updates / Bank.apply_updates: `bits` to voices [first_voice, first_voice + n_voices) of one table
     row. The constructors take a float (param, coeff, input_const) or a state word; `node` is a graph's node id (Graph.ids) or a

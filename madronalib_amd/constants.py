@@ -14,6 +14,7 @@ class Status:
     ERR_OOM = 4
     ERR_UNSUPPORTED = 5
     ERR_RANGE = 6
+    ERR_BUSY = 7
 
 
 class Layout:
