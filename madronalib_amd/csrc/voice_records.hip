@@ -27,6 +27,7 @@ struct RecordArgs
   uint32_t* records;     // [records][W], 16-byte aligned
   uint64_t V, W, nEntries;
   uint32_t granule;      // 1, 8 or 16 ring words a voice owns in one piece
+  uint32_t padOff, padWords;  // the words between the table words and the next multiple of 4: export writes them as zeros
 };
 
 constexpr uint32_t kLaneQuads = 8;  // 16-byte quads of one record a lane moves per item (mlgpu_recorder_move sizes the grid by it)
@@ -156,6 +157,13 @@ __global__ __launch_bounds__(256) void voice_records_kernel(const RecordArgs a)
   const uint32_t seg = (uint32_t)__builtin_amdgcn_readfirstlane((int)blockIdx.y);
   const uint4 lo = a.segs[2u * seg], hi = a.segs[2u * seg + 1u];  // {base lo, base hi, rows, recOff}, {where, -, -, -}
   const uint64_t base = ((uint64_t)lo.y << 32) | lo.x;
+  // a record's words between its table words and its rings belong to no segment: the first segment's workgroups zero them on export
+  if (!kImport && seg == 0u && a.padWords != 0u)
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.nEntries * a.padWords; i += (uint64_t)gridDim.x * 256u)
+    {
+      const uint64_t e = i / a.padWords;
+      a.records[(uint64_t)a.entries[e].y * a.W + a.padOff + (i - e * a.padWords)] = 0u;
+    }
   // the most items a segment can have: a quad or a word per (row, entry); 32 bits with room for the loop's last step (at most 2^22)
   if ((uint64_t)lo.z * a.nEntries < ((uint64_t)1 << 31))
     move_segment<kImport, uint32_t>(a, base, lo.z, lo.w, hi.x);
@@ -230,6 +238,8 @@ int mlgpu_recorder_move(mlgpu_engine* e, mlgpu_recorder& r, uint32_t* const* tab
     a.W = r.plan.words();
     a.nEntries = r.plan.entries();
     a.granule = r.plan.granule();
+    a.padOff = (uint32_t)r.plan.tableWords();
+    a.padWords = (uint32_t)((0 - r.plan.tableWords()) & 3u);
     // grid.x: a lane per item of the largest segment, within 16 384 workgroups of a segment (the rest is the kernel's loop)
     uint64_t items = 1;
     for (const Segment& s : segs)

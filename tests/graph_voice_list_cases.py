@@ -4,7 +4,9 @@ tests/test_graph_voice_list_cpu.py and tests/test_gpu_graph_voice_list.py.
 The one rule: a listed call behaves as a graph of K voices with the same description, made of voices L[0] ... L[K-1]. For a graph
 without rings the expected values are graph_oracle.evaluate on the K gathered voices - params, coefficients, input rows and control
 columns gathered by L, the state taken from the full graph's state at L and scattered back there -, oracle.mixdown of those K rows and
-the peaks in numpy. Ring memory cannot be read back: for a graph with rings the expected value is a plain K-voice graph on the device."""
+the peaks in numpy. Ring memory cannot be read back from the device, so the ring cases of the voice-list tests take a plain K-voice graph
+on the device as their expected value; the host reference for graphs with rings is tests/session_model.py (graph_oracle.evaluate_stream on
+the gathered voices with per-voice ring memory), which tests/test_gpu_session_fuzz.py compares whole sessions with."""
 import types
 
 import numpy as np
