@@ -19,9 +19,9 @@
 #include "mldsp_kernels.hpp"
 
 using namespace mldev;
-static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip && kHostSegmentStripFloats == kSegmentStrip && kHostSegmentTailFloats == kSegmentTail && kHostTurnClockShift == kTurnClockShift &&
+static_assert(kHostMixStripFloats == kMixStrip && kHostGroup16StripFloats == kGroup16Strip && kHostSegmentStripFloats == kSegmentStrip && kHostSegmentTailFloats == kSegmentTail && kHostTurnClockShift == kTurnClockShift && mlparts::kLanesPerWorkgroup == (size_t)kChainBlock &&
                   kHostGraphMaxInputs == MLGPU_GRAPH_MAX_INPUTS && kHostGraphMaxOutputs == MLGPU_GRAPH_MAX_OUTPUTS,
-              "graph_codegen.hpp's copies of what the device headers fix");
+              "graph_codegen.hpp's and launch_parts.hpp's copies of what the device headers fix");
 
 namespace
 {

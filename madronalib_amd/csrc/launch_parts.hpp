@@ -15,7 +15,8 @@ namespace mlparts
 {
 // chain_kernel deals its workgroups to the XCDs in whole rounds of 8 (mldsp_kernels.hpp: remapped_block); a part whose workgroup
 // count is a multiple of 8 keeps that remap whole. 8 workgroups of 256 lanes:
-constexpr size_t kSplitUnit = 8 * 256;
+constexpr size_t kLanesPerWorkgroup = 256;  // (mldsp_kernels.hpp: kChainBlock; chains.hip asserts they agree)
+constexpr size_t kSplitUnit = 8 * kLanesPerWorkgroup;
 constexpr size_t kMaxPendingOutputs = 8;
 constexpr int kMaxParts = 4;
 // More than two kernels per launch only where the smallest of them still works on this many voice-samples (automatic mode). From the
@@ -51,6 +52,15 @@ struct Plan
   int firstSide;
 };
 Plan splitPlan(size_t V, size_t T, int mode, size_t cuCount, size_t lanesPerWorkgroup);
+
+// Is the kernel of a part of `voices` voices at most one workgroup per CU? Such a kernel is expected to have one wavefront on each
+// SIMD it uses - the dispatcher deals a kernel's workgroups out over the CUs, it does not promise to - and then takes no turns at the
+// priority levels (MLGPU_KFLAG_LONE_WAVEFRONTS, mlgpu_device_args.hpp). Only speed depends on the expectation: the bits are the
+// same with and without the turns.
+inline bool atMostAWorkgroupPerCu(size_t voices, size_t cuCount, size_t lanesPerWorkgroup)
+{
+  return voices / lanesPerWorkgroup + (voices % lanesPerWorkgroup != 0) <= cuCount;
+}
 
 // An output signal a pending launch writes: [base, base + bytes) in some layout over T DSPVectors. Two launches of the same bank
 // with the same base, layout and T write, part by part, exactly the same addresses.

@@ -111,6 +111,10 @@ __device__ __forceinline__ uint32_t stream_voice(CH& ch, const ChainArgs& a, siz
   const f32x4* pin = HAS_SIGNAL ? (const f32x4*)a.in.base + (vin >> inShift) * a.in.strideV : nullptr;
   const size_t inQ = a.in.strideQ;
   const uint32_t slot = wave_slot();
+  // a launch of at most one workgroup per CU (MLGPU_KFLAG_LONE_WAVEFRONTS): each SIMD should hold one wavefront of this kernel, there is
+  // nobody to take turns with, and the wavefront stays at priority 0 - one scalar branch per turn point instead of the clock read
+  // (a scalar memory round trip the wavefront waits for) and the choice of a level
+  const bool lone = (a.flags & MLGPU_KFLAG_LONE_WAVEFRONTS) != 0;
   for (size_t t = 0; t < a.T; ++t)
   {
     const f32x4* pi = HAS_SIGNAL ? pin + t * a.in.strideT : nullptr;
@@ -119,7 +123,7 @@ __device__ __forceinline__ uint32_t stream_voice(CH& ch, const ChainArgs& a, siz
 #pragma unroll 4
     for (int q = 0; q < 16; ++q)
     {
-      if ((q & 3) == 0) take_turns_by_clock(slot, kTurnClockShift);
+      if ((q & 3) == 0 && !lone) take_turns_by_clock(slot, kTurnClockShift);
       f32x4 y;
       if constexpr (HEAD == kHeadTrip)
       {

@@ -42,7 +42,12 @@ MLD void apply_fp_mode(uint32_t flags)
 // arrive together, and the SIMD keeps its full issue rate to the end. (s_setprio takes an immediate: hence the switch.)
 MLD uint32_t wave_slot() { return (uint32_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3u; }  // HW_REG_HW_ID.wave_id
 // the turns are told by the clock all wavefronts share (100 MHz): the four levels rotate every 2^shift ticks (kTurnClockShift)
-// whatever the wavefront's own progress
+// whatever the wavefront's own progress.
+// The turns are for the wavefronts of ONE kernel that share a SIMD. A kernel launched as at most one workgroup per CU - a part of
+// a bank launch in parts, where it is that small - has one wavefront per SIMD and takes none (MLGPU_KFLAG_LONE_WAVEFRONTS; mldsp_kernels.hpp: stream_voice):
+// the clock read is a scalar memory round trip the wavefront waits for on the spot, and a level held against another kernel's
+// wavefront equalises nothing. Reading the clock a turn ahead and setting the level only when the turn changes were measured too
+// and are not in: neither was a gain on the headline by the rule of profiles/turns_clock_ahead.md.
 MLD void take_turns_by_clock(uint32_t slot, int shift)
 {
   const uint32_t now = (uint32_t)(__builtin_amdgcn_s_memrealtime() >> shift);

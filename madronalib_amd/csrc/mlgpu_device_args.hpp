@@ -17,6 +17,9 @@ struct SignalView
 
 // bits of the `flags` word every arithmetic kernel receives
 #define MLGPU_KFLAG_FLUSH_DENORMALS 1u  // run with f32 denormal sources and results flushed (mlgpu_engine_set_flush_denormals)
+// the launch is at most one workgroup per CU, so each SIMD is expected to hold one wavefront of this kernel: they take no turns at the
+// priority levels (mldsp_kernels.hpp: stream_voice). Set by the host for the kernels of a bank launch that goes out in parts (capi.hip).
+#define MLGPU_KFLAG_LONE_WAVEFRONTS 2u
 // host-side only (read by the cascade launchers, chains.hip): which form of an SVF cascade to run (mlgpu_engine_set_cascade_lanes).
 // 0 = by bank size, 1 / 2 / 4 = that many wavefront lanes per channel, 7 = the round-2 kernel (cascade_kernel)
 #define MLGPU_KFLAG_CASCADE_SHIFT 8
