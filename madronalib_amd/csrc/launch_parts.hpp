@@ -1,6 +1,8 @@
 // launch_parts.hpp — the HOST bookkeeping of a bank launch that goes out in parts ("Launch parts"): where a
-// bank's voices are cut, and what the engine remembers of the parts that run on its side stream until the two streams meet again.
-// Plain C++ that never touches a device: built and tested without any HIP header; capi.hip is the caller.
+// bank's voices are cut, what the engine remembers of the parts that run on its side stream until the two streams meet again, and
+// the two-stream rule itself (Streams<Api>, below): the fork, the lazy join and the order the parts go out in, with the two raw
+// streams, which nothing outside it can reach. Plain C++ that never touches a device: built and tested without any HIP header
+// (mlgpu_internal.hpp binds Streams to HIP; tests/cpp/launch_streams_test.cpp to a fake); capi.hip is the caller.
 //
 // A plain launch of a bank's V voices may go out as two kernels, voices [0, v0) on the engine's stream and [v0, V) on a side stream.
 // Consecutive launches of the bank depend on each other only through each voice's own state, so each part is serial on its own
@@ -105,5 +107,143 @@ class Pending
   const void* owner_{nullptr};
   size_t n_{0};
   Output out_[kMaxPendingOutputs]{};
+};
+
+// The two streams themselves: the engine's main stream (adopted: made and destroyed by the engine), the side stream and the fork and
+// join events (made here on first use, destroyed here), the Pending book, and the one order in which they are used. The raw handles
+// have no accessor: stream() is the only way to the main stream and joins first, launch() the only way to the side stream, and
+// then only for the parts of a plan. `Api` supplies the stream and event calls (mlgpu_internal.hpp binds HIP,
+// tests/cpp/launch_streams_test.cpp a fake that logs every call and fails on demand):
+//   Stream, Event, Error;  static constexpr Error kSuccess;
+//   Error priority(Stream, int&);  Error createStream(Stream&, int priority) (non-blocking);  void destroyStream(Stream);
+//   Error createEvent(Event&) (no timing);  void destroyEvent(Event);  Error record(Event, Stream);  Error wait(Stream, Event);
+//   Error synchronize(Stream).
+template <class Api>
+class Streams
+{
+ public:
+  using Stream = typename Api::Stream;
+  using Error = typename Api::Error;
+
+  explicit Streams(Stream main) : main_(main) {}
+  Streams(const Streams&) = delete;
+  Streams& operator=(const Streams&) = delete;
+  ~Streams()
+  {
+    if (!made_) return;
+    Api::destroyStream(side_);
+    Api::destroyEvent(joinEvent_);
+    Api::destroyEvent(forkEvent_);
+  }
+
+  // The main stream, for everything that is enqueued on it, waits for it or hands it out: it first waits for what is pending on the
+  // side stream, so nobody can forget the join.
+  Stream stream()
+  {
+    if (pending_.any()) join();
+    return main_;
+  }
+
+  // One launch of `owner` into `out` as the kernels of `plan` (n > 1): launchPart(i, stream) -> Error enqueues part i. Where the
+  // pending launches do not admit this one the streams meet and part again first. The streams' kernels go out in turn - main 0,
+  // side 0, main 1, side 1 - so that both streams have work from the start, up to the first that fails; `call` names the caller for
+  // the report of what a later join cannot hand over (takeSideError). inParts false: no side stream to be had; nothing is pending,
+  // nothing was counted or launched, and the caller launches in one part on stream(), as it always could.
+  struct Launched
+  {
+    bool inParts;
+    Error error;
+  };
+  template <class LaunchPart>
+  Launched launch(const Plan& plan, const void* owner, const Output& out, const char* call, LaunchPart&& launchPart)
+  {
+    if (!pending_.admits(owner, out))
+    {
+      stream();  // (the main stream waits for what is pending, if anything is)
+      if (fork() != Api::kSuccess) return {false, Api::kSuccess};
+    }
+    pending_.launched(owner, out);
+    call_ = call;
+    Error err = Api::kSuccess;
+    for (int i = 0; err == Api::kSuccess && (i < plan.firstSide || plan.firstSide + i < plan.n); ++i)
+    {
+      if (i < plan.firstSide) err = launchPart(i, main_);
+      const int j = plan.firstSide + i;
+      if (err == Api::kSuccess && j < plan.n) err = launchPart(j, side_);
+    }
+    ++splitLaunches_;
+    return {true, err};
+  }
+
+  // What a join could not hand to the main stream, and the call whose part was pending then: told once, kSuccess from then on.
+  Error takeSideError(const char** call)
+  {
+    const Error err = sideError_;
+    sideError_ = Api::kSuccess;
+    *call = sideErrorCall_;
+    return err;
+  }
+
+  const Pending& pending() const { return pending_; }  // what runs on the side stream since the streams last met
+  uint64_t splitLaunches() const { return splitLaunches_; }  // launches (calls, not kernels) that went out in parts
+  uint64_t joins() const { return joins_; }                  // how often the streams met
+
+ private:
+  // The side stream takes up where the main stream is now. It is made on first use, with the main stream's priority, together with
+  // the two events: all three or none, so a failure leaves nothing half made and the next call tries again.
+  Error fork()
+  {
+    Error err = Api::kSuccess;
+    if (!made_)
+    {
+      int priority = 0;
+      Stream side{};
+      typename Api::Event forkEvent{}, joinEvent{};
+      if ((err = Api::priority(main_, priority)) != Api::kSuccess) return err;
+      if ((err = Api::createStream(side, priority)) != Api::kSuccess) return err;
+      if ((err = Api::createEvent(forkEvent)) != Api::kSuccess)
+      {
+        Api::destroyStream(side);
+        return err;
+      }
+      if ((err = Api::createEvent(joinEvent)) != Api::kSuccess)
+      {
+        Api::destroyStream(side);
+        Api::destroyEvent(forkEvent);
+        return err;
+      }
+      side_ = side;
+      forkEvent_ = forkEvent;
+      joinEvent_ = joinEvent;
+      made_ = true;
+    }
+    if ((err = Api::record(forkEvent_, main_)) != Api::kSuccess) return err;
+    return Api::wait(side_, forkEvent_);
+  }
+  // The main stream waits for the side stream's work; where the event cannot carry that, the host waits instead, and what failed is
+  // kept for takeSideError.
+  void join()
+  {
+    Error err = Api::record(joinEvent_, side_);
+    if (err == Api::kSuccess) err = Api::wait(main_, joinEvent_);
+    if (err != Api::kSuccess)
+    {
+      const Error waited = Api::synchronize(side_);
+      sideError_ = waited != Api::kSuccess ? waited : err;
+      sideErrorCall_ = call_;
+    }
+    pending_.joined();
+    ++joins_;
+  }
+
+  Stream main_;
+  Stream side_{};
+  typename Api::Event forkEvent_{}, joinEvent_{};
+  bool made_{false};  // the side stream and the two events
+  Pending pending_;
+  const char* call_{""};  // the call whose part is pending
+  Error sideError_{Api::kSuccess};
+  const char* sideErrorCall_{""};
+  uint64_t splitLaunches_{0}, joins_{0};
 };
 }  // namespace mlparts

@@ -87,8 +87,26 @@ inline hipError_t createTurn(StagingTurn& turn)  // (for the create functions, w
   return err != hipSuccess ? err : hipErrorUnknown;
 }
 
+// The two streams of launches that go out in parts fork and join by mlparts' rule (launch_parts.hpp; DESIGN.md §3.1, "Launch parts")
+struct HipStreamsApi
+{
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  using Error = hipError_t;
+  static constexpr Error kSuccess = hipSuccess;
+  static Error priority(Stream stream, int& priority) { return hipStreamGetPriority(stream, &priority); }
+  static Error createStream(Stream& stream, int priority) { return hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, priority); }
+  static void destroyStream(Stream stream) { hipStreamDestroy(stream); }
+  static Error createEvent(Event& ev) { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  static void destroyEvent(Event ev) { hipEventDestroy(ev); }
+  static Error record(Event ev, Stream stream) { return hipEventRecord(ev, stream); }
+  static Error wait(Stream stream, Event ev) { return hipStreamWaitEvent(stream, ev, 0); }
+  static Error synchronize(Stream stream) { return hipStreamSynchronize(stream); }
+};
+
 struct mlgpu_engine
 {
+  explicit mlgpu_engine(hipStream_t main) : streams(main) {}  // (createEngine: the engine's own stream or the caller's)
   int device{0};
   bool ownsStream{false};
   int cuCount{256};
@@ -144,77 +162,20 @@ struct mlgpu_engine
     return release(obj, what, [](T*) {});
   }
 
-  // ---- the engine's stream, and the side stream of launches that go out in two parts (launch_parts.hpp) ----
+  // ---- the engine's stream, and the side stream of launches that go out in parts (launch_parts.hpp) ----
   // Everything the engine enqueues, waits for or hands out goes through stream(), which first lets the main stream wait for
-  // what is pending on the side stream: nobody can forget the join. Only the two-part launch itself (capi.hip:
-  // mlgpu_bank_process) asks for the streams as they are.
-  hipStream_t stream()
-  {
-    if (parts.any()) join();
-    return mainStream;
-  }
-  hipStream_t streamAsIs() const { return mainStream; }
-  void adoptStream(hipStream_t s) { mainStream = s; }  // (createEngine)
-  // The side stream takes up where the main stream is now. It is made on first use, with the main stream's priority, together with
-  // the two events: all three or none, so a failure leaves nothing half made and the next call tries again. hipSuccess, or why
-  // not: nothing is pending then, and the caller launches in one part.
-  hipError_t fork(hipStream_t* side)
-  {
-    hipError_t err = hipSuccess;
-    if (!sideStream)
-    {
-      int prio = 0;
-      hipStream_t made = nullptr;
-      OwnedEvent fe, je;
-      if ((err = hipStreamGetPriority(mainStream, &prio)) != hipSuccess) return err;
-      if ((err = hipStreamCreateWithPriority(&made, hipStreamNonBlocking, prio)) != hipSuccess) return err;
-      if ((err = allocate(fe, hipEventDisableTiming)) != hipSuccess || (err = allocate(je, hipEventDisableTiming)) != hipSuccess)
-      {
-        hipStreamDestroy(made);
-        return err;
-      }
-      sideStream = made;
-      forkEvent = std::move(fe);
-      joinEvent = std::move(je);
-    }
-    if ((err = hipEventRecord(forkEvent.get(), mainStream)) != hipSuccess) return err;
-    if ((err = hipStreamWaitEvent(sideStream, forkEvent.get(), 0)) != hipSuccess) return err;
-    *side = sideStream;
-    return hipSuccess;
-  }
-  hipStream_t sideAsIs() const { return sideStream; }
-  // The main stream waits for the side stream's work; where the event cannot carry that, the host waits instead. What failed
-  // is kept in sideError, with the name of the call whose part was pending, for the next call that reports a status.
-  void join()
-  {
-    hipError_t err = hipEventRecord(joinEvent.get(), sideStream);
-    if (err == hipSuccess) err = hipStreamWaitEvent(mainStream, joinEvent.get(), 0);
-    if (err != hipSuccess)
-    {
-      const hipError_t waited = hipStreamSynchronize(sideStream);
-      sideError = waited != hipSuccess ? waited : err;
-      sideErrorCall = partsCall;
-    }
-    parts.joined();
-    ++joins;
-  }
-  ~mlgpu_engine()
-  {
-    if (sideStream) hipStreamDestroy(sideStream);
-  }
+  // what is pending on the side stream: nobody can forget the join. The rule - fork, lazy join, the order of the parts - and the
+  // two raw streams live in mlparts::Streams, which has no accessor for either: a launch in parts (capi.hip: mlgpu_bank_process)
+  // is handed each part's stream by streams.launch() and nothing else sees one.
+  hipStream_t stream() { return streams.stream(); }
+  // May a launch go out in parts at all: the engine's stream is its own and nobody else's (mlgpu_engine_launch_parts_possible) ...
+  bool ownsPrivateStream() const { return ownsStream && !streamHandedOut; }
+  // ... and now: nothing is being recorded (mlgpu_bank_process)
+  bool mayLaunchInPartsNow() const { return ownsPrivateStream() && !recording; }
 
-  mlparts::Pending parts;     // what runs on the side stream since the streams last met
-  const char* partsCall{""};  // ... and the call that put it there
   int launchParts{mlparts::kAuto};  // mlgpu_engine_set_launch_parts
   bool streamHandedOut{false};      // mlgpu_engine_stream has given the main stream away: every launch in one part from then on
-  uint64_t splitLaunches{0}, joins{0};  // mlgpu_engine_launch_stats
-  hipError_t sideError{hipSuccess};
-  const char* sideErrorCall{""};
-
- private:
-  hipStream_t mainStream{nullptr};
-  hipStream_t sideStream{nullptr};
-  OwnedEvent forkEvent, joinEvent;
+  mlparts::Streams<HipStreamsApi> streams;  // (the last member: its side stream and events go first, the main stream is not its to destroy)
 };
 
 struct mlgpu_fence  // mlgpu_engine_signal / mlgpu_engine_wait: a point in one engine's stream that another engine's stream can wait for
